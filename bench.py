@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — headline measurement of the rasterizer hot path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full [--full-json PATH]]
 
 A *step* is one pass of the hot path (preprocess -> bin -> per-tile sort -> composite) over one
 batch of synthetic input: ``--views`` target views (default 16) of one seeded random-init scene of
@@ -11,13 +11,20 @@ is shared by the views (scene-level inputs, per-view cameras), as in the decoder
 ``value`` = views rendered per second by the whole job (all ranks).  With N > 1 every rank renders
 its own scene (disjoint seeds), there is no data-path collective: weak scaling.
 
-The same JSON line also carries
+A plain run sets up, warms up, times exactly K steps and prints one JSON line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` = milliseconds of one timed step, ...).  ``--dump-outputs DIR`` then also
+writes what the last timed step returned (rank 0: color / feature / mask / depth / radii, whichever exist) as
+``DIR/<name>.npy`` in float32; the inputs are seeded, so two builds can be compared output for output.
+
+With ``--full`` the same JSON line also carries
   * ``fwdbwd``   : configs[2] (forward + backward) timed the same way right after the headline run;
   * ``roofline`` : the dominant kernel (k_render_fwd) against the HBM roofline — algorithmic bytes
                    of that kernel per launch / its mean duration measured live with hipEvents
                    on the launch stream (lsr_profile_* hook), see DESIGN.md §Measurement;
   * ``cpu_baseline`` : the CPU oracle (oracle/raster_oracle.c, OpenMP) timed on this box's host
-                   cores on a bounded sample of the same workload (rank 0, N = 1 only).
+                   cores on a bounded sample of the same workload (rank 0, N = 1 only);
+and the decoder / adapter / latent / chained-path, pipelined and latency legs and the parity gate below; the whole
+dictionary goes to ``--full-json`` (default ``bench_out/bench_full.json``).
 """
 from __future__ import annotations
 
@@ -214,6 +221,27 @@ def whole_job_views_per_s(views_per_step, steps, world, elapsed_max):
 
 def rank_seed(base, rank):
     return base + rank
+
+
+DUMP_BUDGET_BYTES = 60 * 10**6     # the .npy payloads of one --dump-outputs, headers aside (< 64 MB in all)
+
+
+def dump_outputs(out_dir, named, budget=DUMP_BUDGET_BYTES, seed=0):
+    """Write every tensor of `named` that is not None as out_dir/<name>.npy in float32 (radii: int32, exact in float32).
+    Should the whole exceed `budget`, each array keeps its proportional share of it as a fixed sample of its flattened
+    elements (seeded, sorted indices: the same shapes give the same sample in every run)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in named.items() if v is not None}
+    total = sum(4 * a.size for a in arrays.values())
+    for i, (name, a) in enumerate(arrays.items()):
+        if total > budget and a.size:
+            keep = max(1, a.size * budget // total)
+            if keep < a.size:
+                idx = np.sort(np.random.default_rng(seed + i).choice(a.size, keep, replace=False))
+                a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return sorted(arrays)
 
 
 def decoder_step_timing(dev, steps=40, scenes=1, encoder_shaped=False):
@@ -628,9 +656,16 @@ def main():
     ap.add_argument("--views", type=int, default=16, help="views per step (batch of the hot path)")
     ap.add_argument("--gaussians", type=int, default=300_000)
     ap.add_argument("--size", type=int, default=256)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-bwd", action="store_true")
-    ap.add_argument("--no-latency", action="store_true", help="skip the V=1 / V=4 latency section (profiling runs: keeps one launch shape per kernel)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32, rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other leg (per-kernel times, rooflines, fwd+bwd, decoder / adapter / latent / "
+                         "path steps, pipelined and latency legs, CPU baselines, parity gate); off: the headline alone")
+    ap.add_argument("--full-json", metavar="PATH", default=os.path.join(ROOT, "bench_out", "bench_full.json"),
+                    help="--full: where the whole result dictionary is written")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines and the parity gate")
+    ap.add_argument("--no-bwd", action="store_true", help="--full: skip every forward+backward leg")
+    ap.add_argument("--no-latency", action="store_true", help="--full: skip the V=1 / V=4 latency section (profiling runs: keeps one launch shape per kernel)")
     args = ap.parse_args()
 
     # `python bench.py --gpus N` without a launcher: start the N ranks ourselves (one process per GPU, the same
@@ -686,9 +721,9 @@ def main():
     def timed(fn, steps, warmup):
         return timed_region(fn, steps, warmup, dist, lambda: torch.cuda.synchronize(dev), "cpu" if share_gpu else dev)
 
-    # ---- headline: forward only (configs[1]).  In the timed region only the dominant kernel (the
+    # ---- headline: forward only (configs[1]).  With --full, in the timed region only the dominant kernel (the
     # roofline's) is bracketed by hipEvents; bracketing all five stages costs ~3 % of a step, so the
-    # other per-kernel times come from a second, untimed pass over the same steps. ----
+    # other per-kernel times come from a second, untimed pass over the same steps.  A plain run brackets nothing. ----
     # Clock warm-up (round 4): rounds 1-3 timed 3 + 20 steps (10 ms) on a device that had been idle, i.e. INSIDE the power
     # management's ramp — the compositing kernel measured 0.235 ms there and 0.200 ms in every later loop of the same run
     # (profiles/r04_clock_experiment.md).  The steps below are the same steps, untimed.
@@ -696,10 +731,34 @@ def main():
     while time.perf_counter() - t_warm < args.clock_warmup:
         fwd(False)
     torch.cuda.synchronize(dev)
-    _lib.profile_enable(True, only=("render_forward",))   # the roofline kernel: hipEvents over the timed region itself
-    _lib.profile_read()
-    el_fwd = timed(lambda: fwd(False), args.steps, args.warmup)
+    if args.full:
+        _lib.profile_enable(True, only=("render_forward",))   # the roofline kernel: hipEvents over the timed region itself
+        _lib.profile_read()
+    last = {}
+
+    def headline_step():
+        last["out"] = fwd(False)[0]       # what a caller of the path receives (--dump-outputs writes the last step's)
+    el_fwd = timed(headline_step, args.steps, args.warmup)
     per_rank_fwd = [1e3 * t / args.steps for t in PER_RANK_SECONDS]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(zip(("color", "feature", "mask", "depth", "radii"), last["out"])))
+    last.clear()
+    head = {
+        "metric": "rendered target views/sec at 256x256, ~300k Gaussians (forward); fwd+bwd ms/view in `fwdbwd`",
+        "value": whole_job_views_per_s(V, args.steps, world, el_fwd), "unit": "views/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": 1e3 * el_fwd / args.steps, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"BASELINE configs[1]: {G} latent Gaussians (4-ch features + opacity), "
+                               f"{S}x{S}, forward render; {V} views of one scene per step per GPU",
+                   "views_per_step": V, "gaussians": G, "image": [S, S],
+                   "parallelism": f"replicas x{world} (one scene per rank, no data-path collective)"},
+    }
+    if not args.full:         # a plain run: the headline figure alone
+        if rank == 0:
+            print(json.dumps(dict(head, per_rank_ms_per_step=[round(x, 4) for x in per_rank_fwd])))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     prof_render = _lib.profile_read()["render_forward"]
     _lib.profile_enable(True)
     timed(lambda: fwd(False), max(5, min(50, args.steps // 2)), 1)
@@ -707,7 +766,6 @@ def main():
     prof["render_forward"] = prof_render
     _lib.profile_enable(False)
     views_total = V * args.steps * world
-    value = whole_job_views_per_s(V, args.steps, world, el_fwd)
     # spread over single steps (outside the timed region: one device synchronisation per step)
     _lib.profile_enable(False)
     single = []
@@ -888,14 +946,7 @@ def main():
 
     if rank == 0:
         full = {
-            "metric": "rendered target views/sec at 256x256, ~300k Gaussians (forward); fwd+bwd ms/view in `fwdbwd`",
-            "value": value, "unit": "views/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * el_fwd / args.steps, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"BASELINE configs[1]: {G} latent Gaussians (4-ch features + opacity), "
-                                   f"{S}x{S}, forward render; {V} views of one scene per step per GPU",
-                       "views_per_step": V, "gaussians": G, "image": [S, S],
-                       "parallelism": f"replicas x{world} (one scene per rank, no data-path collective)"},
+            **head,
             "ms_per_view_fwd": 1e3 * el_fwd / (V * args.steps), "clock_warmup_s": args.clock_warmup,
             "kernel_ms_per_launch": {k: (ms / n if n else None) for k, (ms, n) in prof.items()},
             "per_rank_ms_per_step": per_rank_fwd, "ms_per_step_spread": step_spread,
@@ -907,8 +958,8 @@ def main():
         # that a driver record that truncates long lines still holds value / roofline / cpu_baseline / fwdbwd.
         side = None
         try:
-            os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-            side = os.path.join(ROOT, "gpurun_out", "bench_full.json")
+            side = os.path.abspath(args.full_json)
+            os.makedirs(os.path.dirname(side), exist_ok=True)
             with open(side, "w") as f:
                 json.dump(full, f, indent=1)
         except OSError:

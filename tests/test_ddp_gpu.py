@@ -137,7 +137,7 @@ def test_bench_multi_process_path_on_one_gpu():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
            "--gpus", "2", "--steps", "3", "--warmup", "1", "--gaussians", "20000", "--views", "4",
-           "--no-cpu-baseline", "--no-latency"]
+           "--no-cpu-baseline", "--no-latency", "--full"]
     env = dict(os.environ, LSR_BENCH_SHARE_GPU="1", MASTER_ADDR="127.0.0.1")
     r = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
@@ -146,7 +146,7 @@ def test_bench_multi_process_path_on_one_gpu():
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["steps"] == 3 and out["warmup"] == 1 and out["scaling"] == "weak"
     assert len(out["per_rank_ms_per_step"]) == 2 and max(out["per_rank_ms_per_step"]) == pytest.approx(out["ms_per_step"], abs=1e-4)
-    assert len(lines[0]) < 4096 and "roofline" in out and "fwdbwd" in out       # compact line; the full dictionary goes to gpurun_out/bench_full.json
+    assert len(lines[0]) < 4096 and "roofline" in out and "fwdbwd" in out       # compact line; the full dictionary goes to the --full-json file
     # the same job WITHOUT a launcher: `python bench.py --gpus 2` starts its own two ranks ...
     cmd2 = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--gaussians", "20000",
             "--views", "4", "--no-cpu-baseline", "--no-latency", "--no-bwd"]

@@ -148,7 +148,7 @@ def test_graph_capture_of_forward_and_backward(hip_device):
         assert float((v.grad - ref[k]).abs().max()) <= 1e-5 * scale, k
 
 
-def test_deterministic_backward_mode(hip_device):
+def test_deterministic_backward_mode(hip_device, tmp_path):
     """LSR_DETERMINISTIC=1 (read once per process, hence a subprocess): the cross-tile gradient sums use
     64-bit fixed-point atomics, so two runs give bitwise identical gradients, which agree with the
     default (float atomic) mode to the fixed-point resolution."""
@@ -173,7 +173,7 @@ torch.save(a.cpu(), sys.argv[1])
 ''' % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     outs = {}
     for det in ("1", "0"):
-        path = f"/tmp/lsr_det_{det}.pt"
+        path = str(tmp_path / f"lsr_det_{det}.pt")
         env = dict(os.environ, LSR_DETERMINISTIC=det)
         r = subprocess.run([sys.executable, "-c", code, path], env=env, capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stderr[-2000:]
