@@ -24,18 +24,35 @@ __device__ __forceinline__ int imax_sel(int a, int b) { return a > b ? a : b; }
 // associate left to right, so  p1 + p2 + p3 -> fma(a3, b3, fma(a1, b1, a2*b2)).
 // What nvcc / ptxas really emit for the fork cannot be known here; the switch exists to measure how much of the
 // "bit-exact" index contract depends on the answer, and to flip the default in one commit once fork vectors say so.
+// (contract(off) in each helper: the rule above holds in a unit built with contraction on, too — preprocess_backward.hip)
 template <bool FMA> __device__ __forceinline__ float dot3(float a0, float b0, float a1, float b1, float a2, float b2) {
+#pragma clang fp contract(off)
     return FMA ? __builtin_fmaf(a2, b2, __builtin_fmaf(a0, b0, a1 * b1)) : a0 * b0 + a1 * b1 + a2 * b2;
 }
 // glm's  w0*j0 + w1*0 + w2*j2  (a column of J with one zero): contracted, the zero term swallows the fusion of the
 // first product (fma(w0, j0, w1*0) = round(w0*j0)) and the LAST product is the fused one
 template <bool FMA> __device__ __forceinline__ float dot2z(float j0, float w0, float j2, float w2) {
+#pragma clang fp contract(off)
     return FMA ? __builtin_fmaf(w2, j2, w0 * j0) : j0 * w0 + j2 * w2;
 }
 template <bool FMA> __device__ __forceinline__ float ndc2pix(float v, int S) {
     return FMA ? (float)(__builtin_fma(v + 1.0, (double)S, -1.0) * 0.5) : (float)(((v + 1.0) * S - 1.0) * 0.5);
 }
 
+// The view-space mean bit for bit as project_gaussian<FMA> computes it.  The backward decides the clamp of the EWA Jacobian
+// from it with the forward's IEEE t / t.z (preprocess_backward.hip): the decision switches the whole dL/dt.x (dL/dt.y) term,
+// so a reciprocal or a contracted t, which move the ratio by an ulp, would change a Gaussian's dL/dmean by a full term
+// wherever the ratio sits within an ulp of 1.3 tanfov.
+struct ViewSpace { float t0, t1, t2; };
+template <bool FMA>
+__device__ __forceinline__ ViewSpace view_space(const float (&vm)[16], float p0, float p1, float p2) {
+#pragma clang fp contract(off)
+    ViewSpace r;
+    r.t0 = dot3<FMA>(vm[0], p0, vm[4], p1, vm[8], p2) + vm[12];
+    r.t1 = dot3<FMA>(vm[1], p0, vm[5], p1, vm[9], p2) + vm[13];
+    r.t2 = dot3<FMA>(vm[2], p0, vm[6], p1, vm[10], p2) + vm[14];
+    return r;
+}
 struct Projected {
     bool ok;                              // survives the near cull, has a finite conic and touches at least one tile
     float px, py;                         // pixel-space mean

@@ -12,9 +12,16 @@
 // broadcast vector loads per (view, Gaussian), which kept the texture addresser ~90 % busy).  Gradients
 // of inputs shared between views (stride 0) are summed in registers and combined across the PARTS
 // groups through LDS in a fixed order — no atomics, no read-modify-write.
-// Divisions are v_rcp_f32 (1 ulp) here: unlike the forward's, these results feed no bit-exact list.
+// Divisions are v_rcp_f32 (1 ulp) here: unlike the forward's, these results feed no bit-exact list — except the clamp
+// decision of the EWA Jacobian, which is the forward's bit for bit (lsr_project.h view_space<FMA>: the forward's t in the
+// projection convention of the call; IEEE t.x / t.z against 1.3f * tanfov).  The cull decision is the forward's radii.
+// Recomputed from the same inputs rather than stored by the forward: the geometry record keeps the layout the compositing
+// kernels read, and the two IEEE divisions cost ~1-2 % of this kernel (profiles/r07_fuzz_edges.md; taking them only near
+// the limit, behind a branch, measured slower).  (The convention is read again at launch: a call must not switch
+// lsr_set_projection_contraction between its forward and its backward.)
 // Spec: SURVEY.md Appendix A.6.
 #include "lsr_internal.h"
+#include "lsr_project.h"
 
 namespace lsr {
 
@@ -39,7 +46,7 @@ __device__ __forceinline__ float rcp(float x) { return __builtin_amdgcn_rcpf(x);
 constexpr int kPreBwdThreads = 256;
 constexpr int kPreBwdShared = 3 + 6 + 1 + kPreBwdFeat + 3;   // register accumulators of the shared inputs
 
-template <int PARTS>
+template <int PARTS, bool FMA>
 __global__ void __launch_bounds__(kPreBwdThreads, 4)
 k_preprocess_bwd(PreBwdParams pk) {
     // view groups: blockIdx.y = group; its inputs, gradient outputs and workspace slices (uniform: scalar arithmetic)
@@ -132,12 +139,11 @@ k_preprocess_bwd(PreBwdParams pk) {
         const float *mp = p.in.means3D + (size_t)v * d.vs_means + 3 * (size_t)i;
         const float p0 = mp[0] * scale, p1 = mp[1] * scale, p2 = mp[2] * scale;
         // ---- covariance path ----
-        const float t0 = vm[0] * p0 + vm[4] * p1 + vm[8] * p2 + vm[12];
-        const float t1 = vm[1] * p0 + vm[5] * p1 + vm[9] * p2 + vm[13];
-        const float tz = vm[2] * p0 + vm[6] * p1 + vm[10] * p2 + vm[14];
+        const ViewSpace vt = view_space<FMA>(vm, p0, p1, p2);   // the forward's t, bit for bit
+        const float tz = vt.t2;
         const float limx = 1.3f * tanfovx, limy = 1.3f * tanfovy;
         const float itz = rcp(tz), itz2 = itz * itz, itz3 = itz2 * itz;
-        const float txtz = t0 * itz, tytz = t1 * itz;
+        const float txtz = vt.t0 / tz, tytz = vt.t1 / tz;   // IEEE, as the forward: these decide the clamp
         const float xm = (txtz < -limx || txtz > limx) ? 0.0f : 1.0f;
         const float ym = (tytz < -limy || tytz > limy) ? 0.0f : 1.0f;
         const float tx = fminf(limx, fmaxf(-limx, txtz)) * tz;
@@ -320,9 +326,16 @@ hipError_t launch_preprocess_backward(const lsr_dims &d_all, const lsr_inputs &i
     const int parts = d.num_views >= 4 ? 4 : (d.num_views >= 2 ? 2 : 1);
     const int per_block = kPreBwdThreads / parts;   // Gaussians per block
     const dim3 grid((unsigned)((d.num_gaussians + per_block - 1) / per_block), (unsigned)num_view_groups(d_all));
-    if (parts == 4) hipLaunchKernelGGL(k_preprocess_bwd<4>, grid, dim3(kPreBwdThreads), 0, s, p);
-    else if (parts == 2) hipLaunchKernelGGL(k_preprocess_bwd<2>, grid, dim3(kPreBwdThreads), 0, s, p);
-    else hipLaunchKernelGGL(k_preprocess_bwd<1>, grid, dim3(kPreBwdThreads), 0, s, p);
+    // the projection convention of the forward (lsr_set_projection_contraction): the clamp decision must be its own
+    if (projection_contraction()) {
+        if (parts == 4) hipLaunchKernelGGL((k_preprocess_bwd<4, true>), grid, dim3(kPreBwdThreads), 0, s, p);
+        else if (parts == 2) hipLaunchKernelGGL((k_preprocess_bwd<2, true>), grid, dim3(kPreBwdThreads), 0, s, p);
+        else hipLaunchKernelGGL((k_preprocess_bwd<1, true>), grid, dim3(kPreBwdThreads), 0, s, p);
+    } else {
+        if (parts == 4) hipLaunchKernelGGL((k_preprocess_bwd<4, false>), grid, dim3(kPreBwdThreads), 0, s, p);
+        else if (parts == 2) hipLaunchKernelGGL((k_preprocess_bwd<2, false>), grid, dim3(kPreBwdThreads), 0, s, p);
+        else hipLaunchKernelGGL((k_preprocess_bwd<1, false>), grid, dim3(kPreBwdThreads), 0, s, p);
+    }
     prof_end(kStPreprocessBwd, s);
     return hipGetLastError();
 }

@@ -55,6 +55,12 @@ def get_fma_contraction() -> bool:
     return bool(lib().oracle_get_fma_contraction())
 
 
+def set_legacy_clamp_mask(on: bool) -> None:
+    """Tests only: True makes the backward decide the EWA Jacobian clamp in double against 1.3 * (double)tanfov, as it did
+    before it took the forward's float decision (raster_oracle.c, oracle_set_legacy_clamp_mask)."""
+    lib().oracle_set_legacy_clamp_mask(ctypes.c_int(1 if on else 0))
+
+
 def _p(a: Optional[np.ndarray]):
     if a is None:
         return ctypes.c_void_p(0)

@@ -46,6 +46,20 @@ def sh_basis(deg: int, d: torch.Tensor) -> torch.Tensor:
     return torch.stack(b, dim=-1)
 
 
+def _clamp_mask(vm, means3D, tanfovx, tanfovy):
+    """(inx, iny): the EWA Jacobian clamp decision of the C forward, bit for bit — t in float32 as
+    ((a0 b0 + a1 b1) + a2 b2) + b3, the IEEE float ratio t.x / t.z against the float limit 1.3f * tanfov (not the
+    matmul's t, nor a ratio or limit in double: within an ulp of the limit those decide differently, and the decision
+    switches a whole gradient term)."""
+    with torch.no_grad():
+        m, p = vm.to(torch.float32), means3D.detach().to(torch.float32)
+        t = [((m[0, k] * p[:, 0] + m[1, k] * p[:, 1]) + m[2, k] * p[:, 2]) + m[3, k] for k in range(3)]
+        f = lambda x: torch.tensor(x, dtype=torch.float32)
+        limx, limy = f(1.3) * f(tanfovx), f(1.3) * f(tanfovy)
+        rx, ry = t[0] / t[2], t[1] / t[2]
+        return (rx >= -limx) & (rx <= limx), (ry >= -limy) & (ry <= limy)
+
+
 def rasterize(H, W, tanfovx, tanfovy, bg, viewmatrix, projmatrix, campos, sh_degree, means3D, cov3D,
               opacities, shs=None, colors_precomp=None, features=None):
     """Returns (color|None, feature|None, mask(1,H,W), depth(1,H,W), radii). All torch CPU."""
@@ -61,8 +75,7 @@ def rasterize(H, W, tanfovx, tanfovy, bg, viewmatrix, projmatrix, campos, sh_deg
     tz = t[:, 2]
     limx, limy = 1.3 * tanfovx, 1.3 * tanfovy
     txtz, tytz = t[:, 0] / tz, t[:, 1] / tz
-    inx = (txtz >= -limx) & (txtz <= limx)
-    iny = (tytz >= -limy) & (tytz <= limy)
+    inx, iny = _clamp_mask(vm, means3D, tanfovx, tanfovy)
     tx = torch.where(inx, t[:, 0], (txtz.clamp(-limx, limx) * tz).detach())
     ty = torch.where(iny, t[:, 1], (tytz.clamp(-limy, limy) * tz).detach())
     fx, fy = W / (2.0 * tanfovx), H / (2.0 * tanfovy)

@@ -9,7 +9,11 @@ the draws go through the scene-level inputs of the decoder path — in-kernel sc
 colour SH, latent SH evaluated in-kernel, shared by all views (the fused projection + SH kernel) or per view; an eighth
 compare the no-sync (latency) forward bit for bit with the synchronous one).
 
-    python -m tests.fuzz_parity --seconds 240 --seed 1 [--out gpurun_out/fuzz_parity.json]
+    python -m tests.fuzz_parity --seconds 240 --seed 1 [--edges] [--out fuzz_parity.json]
+
+--edges draws instead from the frustum-edge scenes (tests/util.py make_edge_scene: the Jacobian clamp band to single ulps,
+the near cull, means outside the cone, border rectangles, wide-baseline targets), from a stream of its own: the default
+draws of every seed, and their `--only N` reproductions, are unchanged.
 
 The suite's BUDGETS for how much of a scene may sit next to a discontinuity (2 % of the pixels, 1 % of the Gaussians: tuned
 to its own scenes) are lifted here — a 7 x 50 image under 30-pixel splats has more — while every bar stays: pixels and
@@ -24,6 +28,7 @@ import random
 import time
 import traceback
 
+import numpy as np
 import torch
 
 from tests import test_parity_gpu as tp
@@ -44,6 +49,50 @@ def draw(rng: random.Random) -> dict:
     if fc:
         case["feature_sh_degree"] = rng.choice([0, 0, 1, 2])
     return case
+
+
+EDGE_SIDES = [16, 17, 31, 33, 48, 64, 70, 96]
+
+
+def draw_edges(rng: random.Random):
+    """One case of the `edges` mode (--edges): a frustum-edge scene of tests/util.py make_edge_scene and what to run on it.
+    Drawn from its own stream, so the default mode's draws of every seed stay what they were."""
+    pop = rng.choice(util.EDGE_POPS)
+    color = rng.choice([None, 0, 1, 2, 3])
+    fc = rng.choice([None, 1, 4, 5, 8, 12, 32])
+    if color is None and fc is None:
+        fc = 4
+    mode = rng.choice(["forward", "forward", "backward_aux", "backward_aux", "fused_shared", "fused_per_view"])
+    H, W = rng.choice(EDGE_SIDES), rng.choice(EDGE_SIDES)
+    if mode.startswith("fused"):
+        H = W
+    if pop == "border":   # rectangles that reach one edge tile of several
+        H, W = max(H, 48), max(W, 48)
+    case = dict(pop=pop, H=H, W=W, views=rng.choice([1, 2, 3, 4]), color_sh_degree=color, feature_channels=fc,
+                feature_sh_degree=rng.choice([0, 0, 1, 2]) if fc else 0, filler=rng.choice([0, 50, 200, 600]), seed=rng.randrange(1 << 30))
+    if mode.startswith("fused"):
+        case["feature_channels"] = fc or 4
+        while case["feature_channels"] * (case["feature_sh_degree"] + 1) ** 2 > 120:   # the fused latent-SH contract
+            case["feature_sh_degree"] -= 1
+    contracted = mode in ("forward", "backward_aux") and rng.random() < 0.4
+    return case, mode, contracted
+
+
+def run_edge_case(dev, case: dict, mode: str):
+    c = dict(case)
+    pop, H, W = c.pop("pop"), c.pop("H"), c.pop("W")
+    sc, lab = util.make_edge_scene(pop, H=H, W=W, **c)
+    if mode.startswith("fused"):
+        tp._fused_scene_check(dev, sc, H, mode == "fused_shared", near_spread=(1.0, 1.0))
+    elif mode == "forward":
+        bi = util.boundary_inputs(sc, H, W, bg=(0.2, 0.4, 0.6))
+        tp._check_forward(bi, util.HipRun(bi, dev))
+    else:
+        rows = None
+        if pop == "band":
+            band = lab["kind"] == 1
+            rows = {v: (np.flatnonzero(band & (lab["band_view"] == v)), {"means": 2e-4, "cov": 2e-3}) for v in (0, 1)}
+        tp._grad_scene(dev, sc, H, W, True, row_checks=rows)
 
 
 class lifted_budgets:
@@ -82,7 +131,9 @@ def run_case(dev, case: dict, mode: str, contracted: bool):
         if contracted:
             lib.lsr_set_projection_contraction(1)
             orc.set_fma_contraction(True)
-        if mode.startswith("fused"):   # scene-level inputs: in-kernel scene scale, 3x3 covariances, stored-layout colour SH, latent SH
+        if "pop" in case:   # --edges
+            run_edge_case(dev, case, mode)
+        elif mode.startswith("fused"):   # scene-level inputs: in-kernel scene scale, 3x3 covariances, stored-layout colour SH, latent SH
             cfg = dict(case, size=max(case["size"]), feature_channels=case["feature_channels"] or 4, views=max(1, case["views"] + (mode == "fused_shared")))
             cfg.setdefault("feature_sh_degree", 2)
             while cfg["feature_channels"] * (cfg["feature_sh_degree"] + 1) ** 2 > 120:   # the fused latent-SH contract (lsr_rasterizer.h); beyond it the
@@ -120,19 +171,22 @@ def run_case(dev, case: dict, mode: str, contracted: bool):
             orc.set_fma_contraction(False)
 
 
-def sweep(dev, seed: int, seconds: float, max_cases: int = 0, only: int = -1) -> dict:
-    rng = random.Random(seed)
+def sweep(dev, seed: int, seconds: float, max_cases: int = 0, only: int = -1, edges: bool = False) -> dict:
+    rng = random.Random(f"edges:{seed}") if edges else random.Random(seed)
     t0 = time.time()
     done, failures, by_mode = 0, [], {}
     worst_clean, over_suite_bar = 0.0, 0
     n = 0
     with lifted_budgets():
         while (time.time() - t0 < seconds and (not max_cases or done < max_cases)) or (only >= 0 and n <= only):
-            case = draw(rng)
-            mode = rng.choice(["forward", "forward", "forward", "backward", "backward_aux", "fused_shared", "fused_per_view", "nosync"])
-            contracted = mode == "forward" and rng.random() < 0.25
-            if mode != "forward":   # the gradient oracle is the slow part: keep its cases small
-                case["G"] = min(case["G"], 4097)
+            if edges:
+                case, mode, contracted = draw_edges(rng)
+            else:
+                case = draw(rng)
+                mode = rng.choice(["forward", "forward", "forward", "backward", "backward_aux", "fused_shared", "fused_per_view", "nosync"])
+                contracted = mode == "forward" and rng.random() < 0.25
+                if mode != "forward":   # the gradient oracle is the slow part: keep its cases small
+                    case["G"] = min(case["G"], 4097)
             n += 1
             if only >= 0 and n - 1 != only:
                 continue
@@ -154,7 +208,7 @@ def sweep(dev, seed: int, seconds: float, max_cases: int = 0, only: int = -1) ->
                 break
     failures = [f for f in failures if f["kind"] != "budget"]
     kinds = {k: sum(f["kind"] == k for f in failures) for k in ("exact", "bar", "other")}
-    return dict(seed=seed, seconds=round(time.time() - t0, 1), cases=done, passed=done - len(failures), passed_by_mode=by_mode,
+    return dict(seed=seed, edges=edges, seconds=round(time.time() - t0, 1), cases=done, passed=done - len(failures), passed_by_mode=by_mode,
                 failed_by_kind=kinds, worst_clean_row_over_scale=worst_clean, cases_over_suite_clean_bar=int(over_suite_bar), failures=failures)
 
 
@@ -163,9 +217,10 @@ def main():
     ap.add_argument("--seconds", type=float, default=120.0)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--only", type=int, default=-1, help="run only draw N of the seed")
+    ap.add_argument("--edges", action="store_true", help="the frustum-edge scenes of tests/util.py make_edge_scene (own draw stream)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
-    res = sweep(torch.device("cuda", 0), args.seed, args.seconds, only=args.only)
+    res = sweep(torch.device("cuda", 0), args.seed, args.seconds, only=args.only, edges=args.edges)
     print(json.dumps(res, indent=1, default=str))
     if args.out:
         with open(args.out, "w") as f:

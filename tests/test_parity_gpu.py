@@ -232,10 +232,17 @@ def test_forward_shared_scene_equals_per_view(hip_device):
 
 
 def _grad_case(hip_device, case, with_aux, edit_scene=None):
-    from latentsplat_amd.rasterizer import rasterize_views
     sc, H, W = _scene(case)
     if edit_scene is not None:
         edit_scene(sc)
+    _grad_scene(hip_device, sc, H, W, with_aux)
+
+
+def _grad_scene(hip_device, sc, H, W, with_aux, row_checks=None):
+    """Every input gradient of ``sc`` through rasterize_views against the oracle.  ``row_checks``: optional
+    {view: (rows, {"means": row_tol, "cov": row_tol})} — those rows of dL/dmeans3D / dL/dcov3D of that view are ALSO held,
+    on their own, to the per-row mixed bar (a row much smaller than the tensor's largest is not hidden by it)."""
+    from latentsplat_amd.rasterizer import rasterize_views
     bi = util.boundary_inputs(sc, H, W, bg=(0.3, 0.1, 0.5))
     V = bi["V"]
     dev = hip_device
@@ -291,6 +298,13 @@ def _grad_case(hip_device, case, with_aux, edit_scene=None):
         close_per_view(feats.grad, np.stack(exp["feat"]), "dL/dfeatures")
     if shs is not None:
         close_shared(shs.grad, exp_shs, "dL/dshs")
+    for v, (rows, tols) in (row_checks or {}).items():
+        rows = np.asarray(rows, np.int64)
+        local = lambda idx: np.flatnonzero(np.isin(rows, idx))
+        for name, got, want in (("means", means.grad, exp["means"]), ("cov", cov6.grad, exp["cov"])):
+            util.assert_grad_close_except_fragile(got[v].detach().cpu().numpy()[rows], want[v][rows], local(frag[v][0]),
+                                                  local(frag[v][1]), ABS_TOL, f"dL/d{name} rows[view {v}]", clean_tol=CLEAN_TOL,
+                                                  row_tol=tols[name])
 
 
 GRAD_CASES = {
@@ -320,13 +334,16 @@ def test_backward_parity(hip_device, name, with_aux):
     dict(G=1500, size=32, views=6, color_sh_degree=3, feature_channels=4, feature_sh_degree=2),   # > 1 view chunk in sh.hip
 ])
 def test_fused_scene_inputs_match_oracle(hip_device, cfg, shared):
-    from latentsplat_amd.decoder import cuda_splatting as cs
-    from latentsplat_amd.rasterizer import rasterize_views
     cfg = dict(cfg)
     G, size = cfg.pop("G"), cfg.pop("size")
-    sc = util.make_scene(G, image_size=size, **cfg)
+    _fused_scene_check(hip_device, util.make_scene(G, image_size=size, **cfg), size, shared)
+
+
+def _fused_scene_check(hip_device, sc, size, shared, near_spread=(1.0, 1.3)):
+    from latentsplat_amd.decoder import cuda_splatting as cs
+    from latentsplat_amd.rasterizer import rasterize_views
     V = sc.extrinsics.shape[0]
-    near = sc.near * torch.linspace(1.0, 1.3, V)          # per-view scene scales differ
+    near = sc.near * torch.linspace(*near_spread, V)      # per-view scene scales differ
     cams, scale = cs._scaled_cameras(sc.extrinsics, sc.intrinsics, near, sc.far, True)
     from latentsplat_amd.rasterizer import make_view_table
     bg = torch.tensor([[0.2, 0.1, 0.4]]).expand(V, 3)

@@ -382,3 +382,324 @@ def oracle_rasterize_views(views, image_height, image_width, sh_degree, means3D,
         radii.append(o["radii"])
     st = lambda xs: None if xs[0] is None else torch.from_numpy(np.stack(xs))
     return st(cols), st(feats), st(masks), st(depths), st(radii)
+
+
+# ---- frustum-edge scenes (tests/test_frustum_edges_*.py, tests/fuzz_parity.py mode "edges") ------------------------
+# The projection has two geometric discontinuities the synthetic scenes above never reach: the clamp of the EWA
+# Jacobian at |t.x / t.z| = 1.3 tanfov (t.y likewise) and the near cull t.z <= 0.2.  The builder below places Gaussians
+# on and around both, with labels computed by float32 replicas of the forward's own expressions (lsr_project.h with
+# FMA = false, raster_oracle.c): t = ((a0 b0 + a1 b1) + a2 b2) + b3, then the IEEE ratio t.x / t.z against 1.3f * tanfov.
+EDGE_POPS = ("band", "outside", "near", "border", "wide", "wide_encoder")
+NEAR_CULL = np.float32(0.2)
+_F = np.float32
+
+
+def f32_view_space(vm, p):
+    """(G,3) view-space means of the forward: vm the (16,) view matrix in memory order, p (G,3) (scaled) means, all float32."""
+    vm = np.asarray(vm, np.float32).reshape(16)
+    p = np.asarray(p, np.float32)
+    return np.stack([((vm[k] * p[:, 0] + vm[4 + k] * p[:, 1]) + vm[8 + k] * p[:, 2]) + vm[12 + k] for k in range(3)], -1)
+
+
+def clamp_replica(bi: dict) -> dict:
+    """Per (view, Gaussian) decisions of the forward for boundary inputs ``bi``: t (V,G,3); ratio = fl(t.x / t.z),
+    fl(t.y / t.z) (V,G,2); lim = 1.3f * tanfov (V,2); clamped (V,G,2); clamped_rcp: the same decision taken on
+    fl(t.x * fl(1 / t.z)) (a reciprocal formulation); clamped_f64: on the double ratio against 1.3 * (double)tanfov;
+    culled (V,G): t.z <= 0.2."""
+    c = bi["cams"]
+    V = bi["V"]
+    t = np.stack([f32_view_space(c.view_matrix[v].contiguous().numpy(), bi["means"][v].numpy()) for v in range(V)])
+    tan = np.stack([c.tan_fov_x.numpy(), c.tan_fov_y.numpy()], -1).astype(np.float32)
+    lim = _F(1.3) * tan
+    with np.errstate(all="ignore"):
+        ratio = t[..., :2] / t[..., 2:3]
+        ratio_rcp = t[..., :2] * (_F(1.0) / t[..., 2:3])
+        ratio64 = t[..., :2].astype(np.float64) / t[..., 2:3].astype(np.float64)
+    L, L64 = lim[:, None, :], (1.3 * tan.astype(np.float64))[:, None, :]
+    out = lambda r, l: (r < -l) | (r > l)
+    return dict(t=t, ratio=ratio, lim=lim, clamped=out(ratio, L), clamped_rcp=out(ratio_rcp, L),
+                clamped_f64=out(ratio64, L64), culled=~(t[..., 2] > NEAR_CULL))
+
+
+def _rot(yaw, pitch, roll):
+    cx, sx, cy, sy, cz, sz = np.cos(pitch), np.sin(pitch), np.cos(yaw), np.sin(yaw), np.cos(roll), np.sin(roll)
+    Rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
+    Ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
+    Rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
+    return Rz @ Ry @ Rx
+
+
+def _edge_extrinsics(views, rng):
+    """(V,4,4) camera-to-world float64: view 0 the identity, view 1 a fixed turned and shifted camera, further views random."""
+    ext = np.tile(np.eye(4), (views, 1, 1))
+    for v in range(1, views):
+        if v == 1:
+            ang, tr = (0.35, -0.2, 0.15), (0.3, -0.2, 0.1)
+        else:
+            ang, tr = rng.uniform(-0.4, 0.4, 3), rng.uniform(-0.3, 0.3, 3)
+        ext[v, :3, :3] = _rot(*ang)
+        ext[v, :3, 3] = tr
+    return ext
+
+
+def _wide_extrinsics(views, rng, depth):
+    """Target cameras of a wide baseline: turned by up to +-35 degrees (yaw, pitch; roll +-10) and moved by about half the
+    scene depth ``depth``, mostly forwards into the cloud."""
+    ext = np.tile(np.eye(4), (views, 1, 1))
+    for v in range(views):
+        a = np.radians(35.0)
+        ext[v, :3, :3] = _rot(rng.uniform(-a, a), rng.uniform(-a, a), rng.uniform(-np.radians(10), np.radians(10)))
+        ext[v, :3, 3] = depth * np.array([rng.uniform(-0.25, 0.25), rng.uniform(-0.25, 0.25), rng.uniform(0.35, 0.65)])
+    return ext
+
+
+def _edge_cameras(ext: np.ndarray):
+    """The float32 view matrices / tangents boundary_inputs will hand to the rasterizer (near = 1: scene scale 1, so the
+    world means ARE the rasterizer's means)."""
+    V = ext.shape[0]
+    e = torch.from_numpy(ext).float()
+    intr = torch.tensor([[0.8, 0, 0.5], [0, 0.8, 0.5], [0, 0, 1.0]]).repeat(V, 1, 1)
+    near, far = torch.ones(V), torch.full((V,), 100.0)
+    e2, nr, fr, _, _ = cs._scale_scene(e, near, far, torch.zeros(V, 1, 3), torch.zeros(V, 1, 3, 3))
+    fov_x, fov_y = get_fov(intr).unbind(-1)
+    return e, intr, near, far, cs._cameras(e2, nr, fr, fov_x, fov_y)
+
+
+def _iso_cov(sig, rng, aniso=(0.5, 1.0)):
+    """(G,3,3) float64 covariances with major standard deviation ``sig`` (G,), random orientation and axis ratios."""
+    G = len(sig)
+    q = rng.normal(size=(G, 4))
+    q /= np.linalg.norm(q, axis=1, keepdims=True)
+    w, x, y, z = q.T
+    R = np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
+                  2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+                  2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], -1).reshape(G, 3, 3)
+    s = sig[:, None] * np.concatenate([np.ones((G, 1)), rng.uniform(*aniso, (G, 2))], 1)
+    cov = R @ (s[:, :, None] ** 2 * np.eye(3)) @ R.transpose(0, 2, 1)
+    return 0.5 * (cov + cov.transpose(0, 2, 1))
+
+
+def _payload_sh(G, rng, color_sh_degree, feature_channels, feature_sh_degree):
+    def att(deg):
+        a = np.ones((deg + 1) ** 2)
+        for d in range(1, deg + 1):
+            a[d * d:(d + 1) ** 2] = 0.1 * 0.25 ** d
+        return a
+    csh = None if color_sh_degree is None else torch.from_numpy(rng.normal(size=(G, 3, (color_sh_degree + 1) ** 2)) * att(color_sh_degree)).float()
+    fsh = None if not feature_channels else torch.from_numpy(
+        0.3 * rng.normal(size=(G, feature_channels, (feature_sh_degree + 1) ** 2)) * att(feature_sh_degree)).float()
+    return csh, fsh
+
+
+def _band_means(cams, v, axis, sign, k, z, q, rng, n_cand=96):
+    """World means (float32) of Gaussians whose forward ratio on ``axis`` in view v is exactly sign * (lim + k ulps),
+    at depths ~z and perpendicular ratios ~q.  Among the hits, prefers the ones on which a reciprocal formulation
+    (fl(t.x * fl(1 / t.z))) or a decision in double decides differently from the forward."""
+    vm = cams.view_matrix[v].contiguous().numpy().reshape(16)
+    tan = np.array([float(cams.tan_fov_x[v]), float(cams.tan_fov_y[v])], np.float32)
+    lim = _F(1.3) * tan[axis]
+    target = lim
+    for _ in range(abs(k)):
+        target = np.nextafter(target, _F(np.inf) if k > 0 else _F(0.0))
+    target = _F(sign) * target
+    c2w = np.linalg.inv(vm.astype(np.float64).reshape(4, 4).T)   # memory order is the transposed world-to-camera matrix
+    picks = []
+    for zi, qi in zip(z, q):
+        zz = zi * (1.0 + 1e-3 * rng.uniform(-1, 1, n_cand))
+        r = np.float64(target) * (1.0 + 2.0 ** -23 * rng.uniform(-3, 3, n_cand))
+        cam = np.zeros((n_cand, 4))
+        cam[:, axis], cam[:, 1 - axis], cam[:, 2], cam[:, 3] = r * zz, qi * tan[1 - axis] * zz, zz, 1.0
+        w = (cam @ c2w.T)[:, :3].astype(np.float32)
+        t = f32_view_space(vm, w)
+        rat = t[:, axis] / t[:, 2]
+        hit = rat.view(np.uint32) == np.asarray(target, np.float32).view(np.uint32)
+        if not hit.any():
+            continue
+        out_f = np.abs(rat) > lim
+        out_rcp = np.abs(t[:, axis] * (_F(1.0) / t[:, 2])) > lim
+        out_64 = np.abs(t[:, axis].astype(np.float64) / t[:, 2].astype(np.float64)) > 1.3 * np.float64(tan[axis])
+        score = np.where(hit, 1 + 2 * (out_rcp != out_f) + (out_64 != out_f), 0)
+        picks.append(w[int(np.argmax(score))])
+    return picks
+
+
+def make_edge_scene(pop: str, H: int = 64, W: int = 64, views: int = 2, seed: int = 0, color_sh_degree=None,
+                    feature_channels=4, feature_sh_degree: int = 0, filler: int = 200):
+    """A Scene at the frustum edges plus its labels.  ``pop``:
+      band    — for each side (+-x, +-y) of view 0 (identity: t = mean exactly) and view 1 (turned: t is rounded) and
+                k = -4..4, a Gaussian whose forward ratio fl(t.x / t.z) is exactly sign * (fl(1.3f tanfov) + k ulps); footprints
+                of tens of pixels reaching into the image, in front of everything else (`filler` Gaussians behind);
+      outside — means at 1.3-3x tanfov off each side of views 0 and 1 (clamped Jacobian) whose footprints cover the border;
+      near    — view-0 depths prev(0.2f), 0.2f, next(0.2f), 0.21, 0.25, 0.3, 0.5, on- and off-axis, footprints from a few
+                pixels to several images;
+      border  — view-0 centres off-screen whose tile rectangle reaches exactly one edge tile row / column, and footprints
+                covering every tile;
+      wide / wide_encoder — a make_scene cloud / an encoder-shaped cloud seen from wide-baseline targets (turned up to
+                +-35 degrees, moved by half the scene depth): some Gaussians behind the camera, some clamped, some near the cull.
+    Returns (scene, labels): labels = clamp_replica(...) of the scene's boundary inputs plus per-Gaussian `kind`
+    ("filler" 0, "band" 1, "outside" 2, "near" 3, "border" 4, "cover" 5, "cloud" 6) and, for band Gaussians, band_view /
+    band_axis / band_sign / band_k (-99 elsewhere)."""
+    from latentsplat_amd.synthetic import make_encoder_scene
+    assert pop in EDGE_POPS, pop
+    rng = np.random.default_rng(seed)
+    size = max(H, W)
+    if pop in ("wide", "wide_encoder"):
+        if pop == "wide":
+            sc = make_scene(10 * max(filler, 100), image_size=size, views=1, color_sh_degree=color_sh_degree,
+                            feature_channels=feature_channels, feature_sh_degree=feature_sh_degree, seed=seed)
+        else:
+            sc = make_encoder_scene(context_views=2, size=max(8, size // 4), samples=2, views=1, color_sh_degree=color_sh_degree,
+                                    feature_channels=feature_channels, feature_sh_degree=feature_sh_degree, seed=seed)
+        depth = float(np.median(sc.means[:, 2].numpy()))
+        sc.extrinsics = torch.from_numpy(_wide_extrinsics(views, rng, depth)).float()
+        sc.intrinsics = sc.intrinsics[:1].repeat(views, 1, 1)
+        sc.near, sc.far = sc.near[:1].repeat(views), sc.far[:1].repeat(views)
+        G = sc.means.shape[0]
+        kind = np.full(G, 6, np.int32)
+        lab = dict(kind=kind)
+    else:
+        views = max(views, 2 if pop in ("band", "outside") else 1)
+        ext = _edge_extrinsics(views, rng)
+        e, intr, near, far, cams = _edge_cameras(ext)
+        c2w = [np.linalg.inv(cams.view_matrix[v].double().numpy().T) for v in range(views)]
+        tan = np.stack([cams.tan_fov_x.numpy(), cams.tan_fov_y.numpy()], -1).astype(np.float64)
+        focal = np.stack([W / (2 * tan[:, 0]), H / (2 * tan[:, 1])], -1)
+        means, sig, opac, kind = [], [], [], []
+        band = dict(band_view=[], band_axis=[], band_sign=[], band_k=[])
+
+        def cam_to_world(v, cam):   # (n,3) camera space of view v -> float32 world
+            c = np.concatenate([cam, np.ones((len(cam), 1))], 1)
+            return (c @ c2w[v].T)[:, :3].astype(np.float32)
+
+        if pop == "band":
+            for v in (0, 1):
+                for axis in (0, 1):
+                    for sign in (1, -1):
+                        for k in range(-4, 5):
+                            z = rng.uniform(2.5, 4.0, 3)
+                            w = _band_means(cams, v, axis, sign, k, z, rng.uniform(-0.6, 0.6, 3), rng)
+                            assert w, f"band: no mean found for view {v} axis {axis} sign {sign} k {k}"
+                            means.append(w[0][None])
+                            zc = 3.25
+                            sig.append([rng.uniform(0.12, 0.22) * size * zc / focal[v, axis]])
+                            opac.append([rng.uniform(0.4, 0.8)])
+                            kind.append([1])
+                            for key, val in zip(band, (v, axis, sign, k)):
+                                band[key].append(val)
+        elif pop == "outside":
+            for v in (0, 1):
+                for axis in (0, 1):
+                    for sign in (1, -1):
+                        n = 5
+                        z = rng.uniform(2.5, 4.0, n)
+                        r = rng.uniform(1.3, 3.0, n) * tan[v, axis]
+                        cam = np.zeros((n, 3))
+                        cam[:, axis], cam[:, 1 - axis], cam[:, 2] = sign * r * z, rng.uniform(-0.6, 0.6, n) * tan[v, 1 - axis] * z, z
+                        means.append(cam_to_world(v, cam))
+                        d_px = (r / tan[v, axis] - 1.0) * (W if axis == 0 else H) / 2   # centre to image edge
+                        sig.append((d_px + rng.uniform(0.05, 0.3, n) * size) / 3.0 * z / focal[v, axis])
+                        opac.append(rng.uniform(0.2, 0.7, n))
+                        kind.append(np.full(n, 2))
+        elif pop == "near":
+            zs = [np.nextafter(NEAR_CULL, _F(0)), NEAR_CULL, np.nextafter(NEAR_CULL, _F(1)), _F(0.21), _F(0.25), _F(0.3), _F(0.5)]
+            for z in zs:
+                for rx, ry in ((0.0, 0.0), (0.45, -0.3), (-0.7, 0.55), (1.1, 0.2)):
+                    for s_px in (2.0, 8.0, 40.0, 200.0):
+                        s_px *= size / 64
+                        # the mean exactly: view 0 is the identity, so t = mean and t.z = z bit for bit
+                        means.append(np.array([[_F(rx * tan[0, 0] * z), _F(ry * tan[0, 1] * z), z]], np.float32))
+                        sig.append([s_px * float(z) / focal[0, 0]])
+                        opac.append([rng.uniform(0.3, 0.8) if s_px < size else rng.uniform(0.03, 0.15)])
+                        kind.append([3])
+        else:   # border: candidates, kept by what the oracle's forward makes of them
+            cand = []
+            for side in range(4):   # left, right, top, bottom
+                n = 48
+                d = rng.uniform(0.3, 30.0, n)                  # centre this far outside the image, pixels
+                r = d + rng.uniform(1.0, 15.0, n)              # radius aimed at one edge tile
+                along = rng.uniform(0.2, 0.8, n) * (H if side < 2 else W)
+                pxy = np.zeros((n, 2))
+                if side < 2:
+                    pxy[:, 0], pxy[:, 1] = (-d if side == 0 else W - 1 + d), along
+                else:
+                    pxy[:, 0], pxy[:, 1] = along, (-d if side == 2 else H - 1 + d)
+                cand.append((pxy, r / 3.0, np.full(n, 4)))
+            pxy = np.array([[-20.0, -30.0], [W + 25.0, -10.0], [-5.0, H + 40.0], [W + 60.0, H + 60.0]])
+            cand.append((pxy, np.full(4, 1.2 * size), np.full(4, 5)))
+            for pxy, s_px, kd in cand:
+                z = rng.uniform(3.0, 5.0, len(pxy))
+                cam = np.stack([((2 * pxy[:, 0] + 1) / W - 1) * tan[0, 0] * z, ((2 * pxy[:, 1] + 1) / H - 1) * tan[0, 1] * z, z], -1)
+                means.append(cam_to_world(0, cam))
+                sig.append(s_px * z / focal[0, 0])
+                opac.append(rng.uniform(0.2, 0.7, len(pxy)))
+                kind.append(kd)
+        m_edge = np.concatenate(means).astype(np.float32)
+        sig = np.concatenate([np.asarray(s, np.float64) for s in sig])
+        n_edge = len(m_edge)
+        # filler: an ordinary cloud behind the edge Gaussians (view-0 pixel uniform in [-0.1, 1.1]^2, depth 5-12)
+        u, vv = rng.uniform(-0.1, 1.1, (2, filler))
+        zf = rng.uniform(5.0, 12.0, filler)
+        m_fill = cam_to_world(0, np.stack([(2 * u - 1) * tan[0, 0] * zf, (2 * vv - 1) * tan[0, 1] * zf, zf], -1))
+        s_fill = rng.uniform(0.5, 4.0, filler) * size / 64 * zf / focal[0, 0]
+        G = n_edge + filler
+        cov = _iso_cov(np.concatenate([sig, s_fill]), rng)
+        op = np.concatenate([np.concatenate([np.atleast_1d(o) for o in opac]), rng.uniform(0.05, 0.4, filler)])
+        csh, fsh = _payload_sh(G, rng, color_sh_degree, feature_channels, feature_sh_degree)
+        sc = Scene(torch.from_numpy(np.concatenate([m_edge, m_fill])), torch.from_numpy(cov).float(),
+                   torch.from_numpy(op).float(), csh, fsh, e, intr, near, far)
+        kind = np.concatenate([np.concatenate([np.atleast_1d(k) for k in kind]), np.zeros(filler)]).astype(np.int32)
+        lab = dict(kind=kind)
+        for key, val in band.items():
+            a = np.full(G, -99, np.int32)
+            a[:len(val)] = val
+            lab[key] = a
+        if pop == "border":   # keep the candidates whose rectangle does what they were made for (per-Gaussian results)
+            o = oracle_forward(boundary_inputs(sc, H, W), 0)
+            gx, gy = (W + 15) // 16, (H + 15) // 16
+            rect, xy = o["rect"], o["xy"]
+            one_col = ((rect[:, 2] - rect[:, 0]) == 1) & ((rect[:, 0] == 0) | (rect[:, 2] == gx))
+            one_row = ((rect[:, 3] - rect[:, 1]) == 1) & ((rect[:, 1] == 0) | (rect[:, 3] == gy))
+            off = (xy[:, 0] < -0.5) | (xy[:, 0] > W - 0.5) | (xy[:, 1] < -0.5) | (xy[:, 1] > H - 0.5)
+            edge_ok = (o["radii"] > 0) & off & (one_col | one_row)
+            cover_ok = (o["radii"] > 0) & off & (rect == np.array([0, 0, gx, gy])).all(1)
+            keep = np.flatnonzero(((kind == 4) & edge_ok) | ((kind == 5) & cover_ok) | (kind == 0))
+            sc = Scene(sc.means[keep], sc.covariances[keep], sc.opacities[keep], None if csh is None else csh[keep],
+                       None if fsh is None else fsh[keep], e, intr, near, far)
+            lab = {k: v[keep] for k, v in lab.items()}
+    lab.update(clamp_replica(boundary_inputs(sc, H, W)))
+    _check_edge_labels(pop, lab)
+    return sc, lab
+
+
+def _check_edge_labels(pop, lab):
+    """What each population claims, on the float32 replicas (the builder asserts it; tests/test_frustum_edges_cpu.py too)."""
+    kind = lab["kind"]
+    if pop == "band":
+        b = np.flatnonzero(kind == 1)
+        v, ax, sg, k = (lab[n][b] for n in ("band_view", "band_axis", "band_sign", "band_k"))
+        rat = lab["ratio"][v, b, ax]
+        lim = lab["lim"][v, ax]
+        steps = np.rint((np.abs(rat).astype(np.float64) - lim) / np.spacing(lim)).astype(int)
+        assert (np.sign(rat) == sg).all() and (steps == k).all(), "band: ratio is not lim + k ulps"
+        assert (lab["clamped"][v, b, ax] == (k > 0)).all() and not lab["culled"][v, b].any()
+        assert (lab["clamped_rcp"][v, b, ax] != lab["clamped"][v, b, ax]).any(), \
+            "band: no Gaussian on which fl(x / z) and fl(x fl(1 / z)) decide differently"
+        for side in ((0, 0, 1), (0, 0, -1), (0, 1, 1), (0, 1, -1), (1, 0, 1), (1, 0, -1), (1, 1, 1), (1, 1, -1)):
+            sel = (v == side[0]) & (ax == side[1]) & (sg == side[2])
+            assert set(k[sel]) == set(range(-4, 5)), side
+    elif pop == "outside":
+        b = np.flatnonzero(kind == 2)
+        assert lab["clamped"][:2, b].any(-1).any(0).all() and not lab["culled"][0, b].any()
+    elif pop == "near":
+        b = kind == 3
+        z = lab["t"][0, :, 2]
+        assert (lab["culled"][0, b] == (z[b] <= NEAR_CULL)).all()
+        assert lab["culled"][0, b].any() and (~lab["culled"][0, b]).any()
+        assert (z[b] == np.nextafter(NEAR_CULL, _F(1))).any() and (z[b] == NEAR_CULL).any()
+    elif pop == "border":
+        assert (kind == 4).sum() >= 4 and (kind == 5).sum() >= 1, "border: too few candidates kept"
+    else:
+        vis = ~lab["culled"]
+        assert (lab["t"][..., 2] < 0).any(), f"{pop}: no Gaussian behind a camera"
+        assert (lab["clamped"].any(-1) & vis).any(), f"{pop}: no clamped Gaussian in front of a camera"
+        assert (vis & (lab["t"][..., 2] < 0.9)).any(), f"{pop}: no Gaussian in the band 0.2 < z < 0.9"
