@@ -353,6 +353,36 @@ int lsr_backward(const lsr_dims *d, const lsr_inputs *in, const void *geom_ws,
                  const int32_t *radii, const lsr_outputs *fwd, const lsr_out_grads *gout,
                  void *grad_ws, const lsr_in_grads *gin, lsr_stream_t stream);
 
+/* ---- camera gradient: lsr_backward plus dL/d(view record).  Every argument of lsr_backward, then
+ *   grad_views   [V][LSR_VIEW_FLOATS], WRITTEN (not accumulated); NULL: exactly lsr_backward (the same kernels);
+ *   view_grad_ws lsr_view_grad_workspace_bytes(d) bytes (host-only sizing; monotone in V and G).
+ * Async, no allocation, no host wait, everything on `stream`; the other gradients are bit for bit those of lsr_backward.
+ * A camera-only instance of the geometry backward kernel runs next to the plain one and the SH backward kernel runs its
+ * camera-gradient instance; both plain-store one partial record per (view, 64 Gaussians), and two small kernels add them
+ * in a fixed order (no float atomics: the camera gradient is bitwise reproducible whenever the rest of the backward is,
+ * e.g. under LSR_DETERMINISTIC=1).  Slot by slot:
+ *   [0..15]  viewmatrix: t = Wr p + vm[12..14] (Wr[k][c] = vm[4c + k], p = scene scale * mean) and M = J Wr give
+ *            dL/dvm[4c + k] = sum dL/dt_k p_c + (J^T dL/dM)[k][c], dL/dvm[12 + k] = sum dL/dt_k (dL/dt.z includes the
+ *            depth output); vm[3, 7, 11, 15] are never read: 0
+ *   [16..31] projmatrix: dL/dpm[4c + j] = sum dL/dh_j p_c, dL/dpm[12 + j] = sum dL/dh_j for the clip coordinates
+ *            h_0, h_1, h_3; column 2 is never read: 0
+ *   [32..34] campos: through the SH direction normalize(s m - campos) of colour (either axis convention) and fused
+ *            latent-feature harmonics; 0 without harmonics
+ *   [35, 36] tanfovx / tanfovy: through focal = size / (2 tanfov) in the EWA Jacobian only.  Where the 1.3 tanfov clamp
+ *            is active the clamped t.x / t.y is a constant, as in the forward's gradient convention: no gradient
+ *            through the limit
+ *   [37..39] bg: sum over the pixels of dL/dcolour * final transmittance (0 without a colour gradient)
+ *   [40]     scene scale: sum dL/dp . mean + 2 s dL/dSigma : cov, plus the SH direction's term
+ *   [41..43] 0
+ * Sums run over the visible (view, Gaussian) pairs; culled Gaussians, radii, tile rectangles and list membership
+ * contribute nothing.  With G == 0 only bg is non-zero (final transmittance 1). */
+size_t lsr_view_grad_workspace_bytes(const lsr_dims *d);
+int lsr_backward_views(const lsr_dims *d, const lsr_inputs *in, const void *geom_ws,
+                       const void *bin_ws, const void *img_ws, int64_t num_pairs,
+                       const int32_t *radii, const lsr_outputs *fwd, const lsr_out_grads *gout,
+                       void *grad_ws, const lsr_in_grads *gin, float *grad_views, void *view_grad_ws,
+                       lsr_stream_t stream);
+
 /* ---- optional measurement hook (bench.py): when enabled, every stage kernel is bracketed by
  * hipEvents on the caller's stream; lsr_profile_read() waits for them, returns the accumulated
  * milliseconds and launch counts per stage since the previous read, and resets the totals.

@@ -122,7 +122,7 @@ EXPORTS = (
     "lsr_abi_version", "lsr_error_string", "lsr_last_hip_error", "lsr_geom_workspace_bytes",
     "lsr_image_workspace_bytes", "lsr_binning_workspace_bytes", "lsr_grad_workspace_bytes",
     "lsr_get_layout", "lsr_build_views", "lsr_pack_view", "lsr_forward_prepare", "lsr_forward_render", "lsr_forward_nosync", "lsr_forward_speculative", "lsr_forward_front",
-    "lsr_forward_status", "lsr_forward_abandon", "lsr_backward",
+    "lsr_forward_status", "lsr_forward_abandon", "lsr_backward", "lsr_view_grad_workspace_bytes", "lsr_backward_views",
     "lsr_profile_enable", "lsr_profile_num_stages", "lsr_profile_stage_name", "lsr_profile_read",
     "lsr_debug_set_knob", "lsr_set_projection_contraction", "lsr_get_projection_contraction",
     "lsr_adapter_forward", "lsr_adapter_backward", "lsr_latent_forward", "lsr_latent_backward",
@@ -171,7 +171,8 @@ def load():
     lib.lsr_error_string.restype = C.c_char_p
     lib.lsr_error_string.argtypes = [C.c_int]
     lib.lsr_last_hip_error.restype = C.c_int
-    for name in ("lsr_geom_workspace_bytes", "lsr_image_workspace_bytes", "lsr_grad_workspace_bytes"):
+    for name in ("lsr_geom_workspace_bytes", "lsr_image_workspace_bytes", "lsr_grad_workspace_bytes",
+                 "lsr_view_grad_workspace_bytes"):
         getattr(lib, name).restype = SZ
         getattr(lib, name).argtypes = [C.POINTER(Dims)]
     lib.lsr_binning_workspace_bytes.restype = SZ
@@ -202,6 +203,9 @@ def load():
     lib.lsr_backward.restype = C.c_int
     lib.lsr_backward.argtypes = [C.POINTER(Dims), C.POINTER(Inputs), P, P, P, I64, P, C.POINTER(Outputs),
                                  C.POINTER(OutGrads), P, C.POINTER(InGrads), P]
+    lib.lsr_backward_views.restype = C.c_int
+    lib.lsr_backward_views.argtypes = [C.POINTER(Dims), C.POINTER(Inputs), P, P, P, I64, P, C.POINTER(Outputs),
+                                       C.POINTER(OutGrads), P, C.POINTER(InGrads), P, P, P]
     lib.lsr_profile_enable.argtypes = [C.c_int]
     lib.lsr_profile_stage_name.restype = C.c_char_p
     lib.lsr_profile_stage_name.argtypes = [C.c_int]

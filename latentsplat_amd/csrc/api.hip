@@ -314,7 +314,8 @@ int lsr_profile_num_stages(void) { return lsr::kNumStages; }
 const char *lsr_profile_stage_name(int stage) {
     static const char *names[lsr::kNumStages] = {"preprocess", "tile_scan", "scatter", "sort_tiles",
                                                   "render_forward", "render_backward", "preprocess_backward",
-                                                  "sh_forward", "sh_backward", "adapter_forward", "adapter_backward", "latent_forward", "latent_backward"};
+                                                  "sh_forward", "sh_backward", "adapter_forward", "adapter_backward", "latent_forward", "latent_backward",
+                                                  "view_grad"};
     return (stage >= 0 && stage < lsr::kNumStages) ? names[stage] : "?";
 }
 int lsr_profile_read(double *ms_out, int64_t *launches_out) {
@@ -720,6 +721,68 @@ int lsr_forward_status(const lsr_dims *d, const void *geom_ws, int64_t *num_pair
     return LSR_OK;
 }
 
+}  // extern "C"
+
+// the body of lsr_backward (checked arguments, G > 0); cam != nullptr: the camera-gradient instances of the geometry and
+// SH backward kernels, which also store the partial records of dL/d(view record)
+static int backward_impl(const lsr_dims *d, const lsr_inputs *in, const void *geom_ws, const void *bin_ws,
+                         const void *img_ws, int64_t num_pairs, const int32_t *radii, const lsr_outputs *fwd,
+                         const lsr_out_grads *gout, void *grad_ws, const lsr_in_grads *gin, const CamGrad *cam,
+                         hipStream_t s) {
+    if ((gout->color && d->color_mode != LSR_COLOR_NONE && !fwd->color) || (gout->feature && d->feat_channels > 0 && !fwd->feature) ||
+        (gout->depth && !fwd->depth))
+        return LSR_ENULL;
+    if (!radii || !gin->means3D || !gin->cov3D || !gin->opacities) return LSR_ENULL;
+    if (d->color_mode != LSR_COLOR_NONE && !gin->color) return LSR_ENULL;
+    if (d->feat_channels > 0 && !gin->features) return LSR_ENULL;
+    if (num_pairs > 0 && !bin_ws) return LSR_ENULL;
+    // zero the packed gradient records the compositing backward accumulates into (unless the forward did: LSR_FWD_CLEARS_GRAD)
+    if (!(d->forward_flags & LSR_FWD_CLEARS_GRAD)) LSR_HIP(launch_clear_grad(*d, radii, (char *)grad_ws, s));
+    if (num_pairs > 0)
+        LSR_STAGE("render_backward", s, launch_render_backward(*d, *in, (const char *)geom_ws, (const char *)bin_ws, num_pairs,
+                                       (const char *)img_ws, *fwd, *gout, (char *)grad_ws, *gin, s));
+    // Geometry and SH backward: one launch each, all scenes (view groups) of the call at once (the scene in
+    // blockIdx.y).  Both add into the scene's mean gradients, hence in stream order.
+    if (!cam) {
+        LSR_STAGE("preprocess_backward", s, launch_preprocess_backward(*d, *in, (const char *)geom_ws, radii, (const char *)grad_ws, *gin, s));
+        LSR_STAGE("sh_backward", s, launch_sh_backward(*d, *in, (const char *)geom_ws, (const char *)grad_ws, *gin, s));
+    } else {
+        LSR_STAGE("preprocess_backward", s, launch_preprocess_backward(*d, *in, (const char *)geom_ws, radii, (const char *)grad_ws, *gin, s, *cam));
+        LSR_STAGE("sh_backward", s, launch_sh_backward_cam(*d, *in, (const char *)geom_ws, (const char *)grad_ws, *gin, *cam, s));
+    }
+    return LSR_OK;
+}
+
+extern "C" {
+
+size_t lsr_view_grad_workspace_bytes(const lsr_dims *d) { return check_dims(d) ? 0 : view_grad_layout(*d).total; }
+
+int lsr_backward_views(const lsr_dims *d, const lsr_inputs *in, const void *geom_ws, const void *bin_ws,
+                       const void *img_ws, int64_t num_pairs, const int32_t *radii, const lsr_outputs *fwd,
+                       const lsr_out_grads *gout, void *grad_ws, const lsr_in_grads *gin,
+                       float *grad_views, void *view_grad_ws, lsr_stream_t stream) {
+    if (!grad_views) return lsr_backward(d, in, geom_ws, bin_ws, img_ws, num_pairs, radii, fwd, gout, grad_ws, gin, stream);
+    g_last_hip_error = 0;
+    int rc = check_dims(d);
+    if (rc) return rc;
+    rc = check_inputs(d, in);
+    if (rc) return rc;
+    if (!gout || !gin || !geom_ws || !img_ws || !grad_ws || !fwd || !view_grad_ws) return LSR_ENULL;
+    hipStream_t s = (hipStream_t)stream;
+    if (d->num_gaussians == 0) {   // nothing but the background: final T is 1 everywhere
+        LSR_STAGE("view_grad", s, launch_view_grad_reduce(*d, (char *)view_grad_ws, false, nullptr,
+                                                          d->color_mode != LSR_COLOR_NONE ? gout->color : nullptr, grad_views, s));
+        return LSR_OK;
+    }
+    const CamGrad cam{(float *)((char *)view_grad_ws + view_grad_layout(*d).part), cam_chunks(*d)};
+    rc = backward_impl(d, in, geom_ws, bin_ws, img_ws, num_pairs, radii, fwd, gout, grad_ws, gin, &cam, s);
+    if (rc) return rc;
+    const float *final_T = (const float *)((const char *)img_ws + img_layout(*d).final_T);
+    LSR_STAGE("view_grad", s, launch_view_grad_reduce(*d, (char *)view_grad_ws, sh_backward_runs(*d), final_T,
+                                                      d->color_mode != LSR_COLOR_NONE ? gout->color : nullptr, grad_views, s));
+    return LSR_OK;
+}
+
 int lsr_backward(const lsr_dims *d, const lsr_inputs *in, const void *geom_ws, const void *bin_ws,
                  const void *img_ws, int64_t num_pairs, const int32_t *radii, const lsr_outputs *fwd,
                  const lsr_out_grads *gout, void *grad_ws, const lsr_in_grads *gin,
@@ -731,24 +794,7 @@ int lsr_backward(const lsr_dims *d, const lsr_inputs *in, const void *geom_ws, c
     if (rc) return rc;
     if (!gout || !gin || !geom_ws || !img_ws || !grad_ws || !fwd) return LSR_ENULL;
     if (d->num_gaussians == 0) return LSR_OK;
-    if ((gout->color && d->color_mode != LSR_COLOR_NONE && !fwd->color) || (gout->feature && d->feat_channels > 0 && !fwd->feature) ||
-        (gout->depth && !fwd->depth))
-        return LSR_ENULL;
-    if (!radii || !gin->means3D || !gin->cov3D || !gin->opacities) return LSR_ENULL;
-    if (d->color_mode != LSR_COLOR_NONE && !gin->color) return LSR_ENULL;
-    if (d->feat_channels > 0 && !gin->features) return LSR_ENULL;
-    if (num_pairs > 0 && !bin_ws) return LSR_ENULL;
-    hipStream_t s = (hipStream_t)stream;
-    // zero the packed gradient records the compositing backward accumulates into (unless the forward did: LSR_FWD_CLEARS_GRAD)
-    if (!(d->forward_flags & LSR_FWD_CLEARS_GRAD)) LSR_HIP(launch_clear_grad(*d, radii, (char *)grad_ws, s));
-    if (num_pairs > 0)
-        LSR_STAGE("render_backward", s, launch_render_backward(*d, *in, (const char *)geom_ws, (const char *)bin_ws, num_pairs,
-                                       (const char *)img_ws, *fwd, *gout, (char *)grad_ws, *gin, s));
-    // Geometry and SH backward: one launch each, all scenes (view groups) of the call at once (the scene in
-    // blockIdx.y).  Both add into the scene's mean gradients, hence in stream order.
-    LSR_STAGE("preprocess_backward", s, launch_preprocess_backward(*d, *in, (const char *)geom_ws, radii, (const char *)grad_ws, *gin, s));
-    LSR_STAGE("sh_backward", s, launch_sh_backward(*d, *in, (const char *)geom_ws, (const char *)grad_ws, *gin, s));
-    return LSR_OK;
+    return backward_impl(d, in, geom_ws, bin_ws, img_ws, num_pairs, radii, fwd, gout, grad_ws, gin, nullptr, (hipStream_t)stream);
 }
 
 }  // extern "C"

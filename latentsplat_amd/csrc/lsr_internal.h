@@ -247,7 +247,7 @@ enum { kHdrPairs = 0, kHdrMaxTile = 1, kHdrNumItems = 3, kHdrOverflow = 4, kHdrP
        kHdrLongTiles = 16 /* + 0, + 1: number of tiles beyond the first sort tier / beyond the second */ };
 
 // ---- optional per-stage hipEvent timing (api.hip); no-ops unless lsr_profile_enable(1) ----
-enum Stage { kStPreprocess = 0, kStTileScan, kStScatter, kStSort, kStRenderFwd, kStRenderBwd, kStPreprocessBwd, kStShFwd, kStShBwd, kStAdapterFwd, kStAdapterBwd, kStLatentFwd, kStLatentBwd, kNumStages };
+enum Stage { kStPreprocess = 0, kStTileScan, kStScatter, kStSort, kStRenderFwd, kStRenderBwd, kStPreprocessBwd, kStShFwd, kStShBwd, kStAdapterFwd, kStAdapterBwd, kStLatentFwd, kStLatentBwd, kStViewGrad, kNumStages };
 void prof_begin(int stage, hipStream_t s);
 void prof_end(int stage, hipStream_t s);
 void note_hip_error(int hip_error);   // what lsr_last_hip_error() returns for this thread
@@ -334,8 +334,57 @@ hipError_t launch_render_backward(const lsr_dims &d, const lsr_inputs &in, const
                                   const char *bin, int64_t num_pairs, const char *img,
                                   const lsr_outputs &fwd, const lsr_out_grads &gout, char *grad,
                                   const lsr_in_grads &gin, hipStream_t s);
+// ---- camera gradients (lsr_backward_views) ----
+// The geometry and SH backward kernels plain-store one partial record of dL/d(view record) per (view, 64-Gaussian chunk)
+// (the wave's sum: the view is wave-uniform in both); two small kernels (views.hip) add them up in a fixed order.  No float
+// atomics anywhere, so the camera gradient is as reproducible as the rest of the backward.  Slots of a partial record:
+//   [0, 12)  viewmatrix vm[4c + k] at 3c + k (c = 0..3, k = 0..2; vm[3, 7, 11, 15] are never read)
+//   [12, 24) projmatrix pm[4c + j] at 12 + 3c + (0, 1, 2 for j = 0, 1, 3; column 2 is never read)
+//   24, 25   tanfovx, tanfovy;  26 scene scale (geometry);  27..29 campos, 30 scene scale (SH direction);  31 unused
+constexpr int kCamSlots = 32;
+enum { kCamVm = 0, kCamPm = 12, kCamTanX = 24, kCamTanY = 25, kCamScaleGeo = 26, kCamPos = 27, kCamScaleSh = 30 };
+constexpr int kCamSplit = 64;    // workgroups per view of the first reduction step
+constexpr int kCamL2 = 36;       // floats of its records: the 32 slots, background (3), pad
+struct CamGrad {
+    float *part;                 // [V][chunks][kCamSlots], or nullptr: no camera gradient (the unchanged kernels)
+    int chunks;                  // ceil(G / 64)
+};
+inline int cam_chunks(const lsr_dims &d) { return (d.num_gaussians + LSR_WAVE - 1) / LSR_WAVE; }
+struct ViewGradLayout {
+    size_t part, l2, total;
+};
+inline ViewGradLayout view_grad_layout(const lsr_dims &d) {
+    ViewGradLayout L;
+    L.part = 0;
+    L.l2 = align_up((size_t)d.num_views * (size_t)cam_chunks(d) * kCamSlots * 4);
+    L.total = L.l2 + align_up((size_t)d.num_views * kCamSplit * kCamL2 * 4);
+    return L;
+}
+// Sum of v[0..31] over the 64 lanes of a wave (all lanes active): recursive halving, 32 exchanges instead of 6 per value.
+// Lane l returns the total of slot l & 31.  A fixed exchange pattern: bitwise reproducible.
+// (one template instance per step: every index is a constant, the array stays in registers)
+template <int H>
+__device__ __forceinline__ void wave_halve(float (&v)[32], int lane) {
+    const bool up = (lane & H) != 0;
+#pragma unroll
+    for (int k = 0; k < H; ++k) {
+        const float send = up ? v[k] : v[k + H], keep = up ? v[k + H] : v[k];
+        v[k] = keep + __shfl_xor(send, H);
+    }
+}
+__device__ __forceinline__ float wave_sum32(float (&v)[32]) {
+    const int lane = (int)(threadIdx.x & (LSR_WAVE - 1));
+    wave_halve<16>(v, lane); wave_halve<8>(v, lane); wave_halve<4>(v, lane); wave_halve<2>(v, lane); wave_halve<1>(v, lane);
+    return v[0] + __shfl_xor(v[0], 32);
+}
 hipError_t launch_preprocess_backward(const lsr_dims &d, const lsr_inputs &in, const char *geom,
                                       const int32_t *radii, const char *grad,
-                                      const lsr_in_grads &gin, hipStream_t s);
+                                      const lsr_in_grads &gin, hipStream_t s, const CamGrad &cam = CamGrad{nullptr, 0});
+hipError_t launch_sh_backward_cam(const lsr_dims &d, const lsr_inputs &in, const char *geom, const char *grad,
+                                  const lsr_in_grads &gin, const CamGrad &cam, hipStream_t s);
+bool sh_backward_runs(const lsr_dims &d);
+// partial records + background (sum over pixels of dL/dcolour * final T) -> grad_views [V][LSR_VIEW_FLOATS] (written)
+hipError_t launch_view_grad_reduce(const lsr_dims &d, char *ws, bool sh, const float *final_T, const float *g_color,
+                                   float *grad_views, hipStream_t s);
 
 }  // namespace lsr

@@ -36,6 +36,7 @@ struct PreBwdParams {
     int rec_floats;
     lsr_in_grads g;
     GroupStrides gs;        // view groups (blockIdx.y): element offsets of the next group's slices
+    CamGrad cam;            // camera-gradient instances (CAM): the partial records of dL/d(view record)
 };
 
 constexpr int kPreBwdFeat = 8;   // shared direct-feature gradients kept in registers up to this many channels
@@ -46,7 +47,12 @@ __device__ __forceinline__ float rcp(float x) { return __builtin_amdgcn_rcpf(x);
 constexpr int kPreBwdThreads = 256;
 constexpr int kPreBwdShared = 3 + 6 + 1 + kPreBwdFeat + 3;   // register accumulators of the shared inputs
 
-template <int PARTS, bool FMA>
+// CAM: the camera-gradient instance (lsr_backward_views), launched NEXT TO the plain one: per (view, Gaussian) the
+// derivative of the loss w.r.t. the view record from the same quantities, summed over the wave (one view, 64 Gaussians) and
+// stored as one partial record (lsr_internal.h kCam*); it stores nothing else.  (Folded into the plain instance, the extra
+// uses changed how the compiler contracted the Gaussian gradients — no longer bit for bit those of lsr_backward — and the
+// 32 live partial sums spilled inside the view loop.)  The plain instances are the code they were.
+template <int PARTS, bool FMA, bool CAM = false>
 __global__ void __launch_bounds__(kPreBwdThreads, 4)
 k_preprocess_bwd(PreBwdParams pk) {
     // view groups: blockIdx.y = group; its inputs, gradient outputs and workspace slices (uniform: scalar arithmetic)
@@ -82,7 +88,9 @@ k_preprocess_bwd(PreBwdParams pk) {
     // Occupancy, not prefetching, hides the memory latency here: holding the NEXT view's record in
     // registers (round 1) cost 175 VGPRs = 2 waves per SIMD (0.155 ms per 16 views; 0.137 without it).
     const bool pay16 = feat_reg && p.rec_floats == 16;
-    const int v_first = feat_rmw ? 0 : part, v_step = feat_rmw ? 1 : PARTS, v_end = (feat_rmw && part != 0) ? 0 : V;   // all wave-uniform
+    // (all wave-uniform; the camera-gradient instance stores no features: its parts always split the views)
+    const bool one_part = feat_rmw && !CAM;
+    const int v_first = one_part ? 0 : part, v_step = one_part ? 1 : PARTS, v_end = (one_part && part != 0) ? 0 : V;
     for (int v = v_first; v < v_end; v += v_step) {
         const size_t o = (size_t)v * G + i;
         const bool vis = p.radii[o] > 0;
@@ -94,6 +102,7 @@ k_preprocess_bwd(PreBwdParams pk) {
         if (pay16) { q0 = *(const float4 *)(rc + 8); q1 = *(const float4 *)(rc + 12); }
         // opacity: the record holds m0 = sum opacity * G * dL/dalpha; dL/dopacity = m0 / opacity
         // (m0 != 0 implies opacity >= 1/255)
+        if constexpr (!CAM) {   // (the camera-gradient instance stores nothing but its partial records)
         if (d.vs_opac != 0) {
             const float o_in = p.in.opacities[(size_t)v * d.vs_opac + i];
             if (live) p.g.opacities[(size_t)v * d.vs_opac + i] = r1.y != 0.0f ? r1.y * rcp(o_in) : 0.0f;
@@ -126,6 +135,7 @@ k_preprocess_bwd(PreBwdParams pk) {
             } else {
                 for (int c = 0; c < 3; ++c) acol[c] += rc[8 + c];
             }
+        }
         }
         // ---- geometry: every lane runs the arithmetic (culled lanes on whatever they hold; IEEE special
         // values are harmless), `vis` masks the results where they are accumulated or stored ----
@@ -227,6 +237,49 @@ k_preprocess_bwd(PreBwdParams pk) {
         for (int cc = 0; cc < 3; ++cc)
             gm[cc] += (pm[4 * cc + 0] * m_w - pm[4 * cc + 3] * mul1) * m2x +
                       (pm[4 * cc + 1] * m_w - pm[4 * cc + 3] * mul2) * m2y;
+        if constexpr (CAM) {
+            // gm / gc are still the gradients w.r.t. the SCALED mean / covariance here
+            float cg[kCamSlots];
+            const float pp[3] = {p0, p1, p2};
+            // t = Wr p + vm[12..14] and M = J Wr (Wr[k][c] = vm[4c + k]): dL/dWr = dt p^T + J^T dM
+#pragma unroll
+            for (int cc = 0; cc < 3; ++cc) {
+                cg[kCamVm + 3 * cc + 0] = dL_dtx * pp[cc] + j00 * dM[0][cc];
+                cg[kCamVm + 3 * cc + 1] = dL_dty * pp[cc] + j11 * dM[1][cc];
+                cg[kCamVm + 3 * cc + 2] = dL_dtz * pp[cc] + j02 * dM[0][cc] + j12 * dM[1][cc];
+            }
+            cg[kCamVm + 9] = dL_dtx; cg[kCamVm + 10] = dL_dty; cg[kCamVm + 11] = dL_dtz;
+            // (h0, h1, h3) = p^T pm[.., 0 / 1 / 3] + pm[12 + j]; ndc = (h0, h1) * m_w
+            const float dh[3] = {m2x * m_w, m2y * m_w, -(m2x * mul1 + m2y * mul2)};
+#pragma unroll
+            for (int cc = 0; cc < 3; ++cc)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) cg[kCamPm + 3 * cc + j] = dh[j] * pp[cc];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) cg[kCamPm + 9 + j] = dh[j];
+            // focal = size / (2 tanfov) enters J only; the clamped t.x / t.y are constants (no gradient through the limit)
+            cg[kCamTanX] = -(dJ00 * itz - dJ02 * tx * itz2) * focal_x * rcp(tanfovx);
+            cg[kCamTanY] = -(dJ11 * itz - dJ12 * ty * itz2) * focal_y * rcp(tanfovy);
+            // scene scale s: p = s mean, Sigma = s^2 cov (packed off-diagonals: gc holds both halves)
+            const float ci[6] = {c6[0], c6[1], c6[2], c6[ce == 9 ? 4 : 3], c6[ce == 9 ? 5 : 4], c6[ce == 9 ? 8 : 5]};
+            float sc = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) sc += gc[k] * ci[k];
+            cg[kCamScaleGeo] = gm[0] * mp[0] + gm[1] * mp[1] + gm[2] * mp[2] + 2.0f * scale * sc;
+#pragma unroll
+            for (int k = kCamScaleGeo + 1; k < kCamSlots; ++k) cg[k] = 0.0f;
+            // culled slots and idle lanes contribute nothing (their arithmetic may have produced anything)
+            const bool cv = live && vis;
+#pragma unroll
+            for (int k = 0; k <= kCamScaleGeo; ++k) cg[k] = cv ? cg[k] : 0.0f;
+            const float r = wave_sum32(cg);
+            const int lane = (int)threadIdx.x & (LSR_WAVE - 1);
+            const int chunk = (int)blockIdx.x * (LPP / LSR_WAVE) + slot / LSR_WAVE;
+            const size_t vg = (size_t)blockIdx.y * V + v;     // the view in the whole call
+            if (lane <= kCamScaleGeo && chunk < p.cam.chunks)
+                p.cam.part[(vg * p.cam.chunks + chunk) * kCamSlots + lane] = r;
+        }
+        if constexpr (CAM) continue;
         // gradients are w.r.t. the UNSCALED inputs: mean_scaled = s * mean, cov_scaled = s^2 * cov;
         // a culled Gaussian's values are discarded here (its arithmetic may have produced anything)
 #pragma unroll
@@ -257,6 +310,7 @@ k_preprocess_bwd(PreBwdParams pk) {
             o2[0] = vis ? m2x : 0.0f; o2[1] = vis ? m2y : 0.0f; o2[2] = 0.0f;
         }
     }
+    if constexpr (CAM) return;
     // ---- shared inputs: groups 1.. leave their partial sums in LDS, group 0 adds them in order and stores ----
     float *acc[kPreBwdShared];
     {
@@ -310,7 +364,7 @@ k_preprocess_bwd(PreBwdParams pk) {
 
 hipError_t launch_preprocess_backward(const lsr_dims &d_all, const lsr_inputs &in, const char *geom,
                                       const int32_t *radii, const char *grad,
-                                      const lsr_in_grads &gin, hipStream_t s) {
+                                      const lsr_in_grads &gin, hipStream_t s, const CamGrad &cam) {
     if (d_all.num_gaussians == 0) return hipSuccess;
     const GeomLayout L = geom_layout(d_all);
     const GradLayout R = grad_layout(d_all);
@@ -322,11 +376,20 @@ hipError_t launch_preprocess_backward(const lsr_dims &d_all, const lsr_inputs &i
     p.rec = (const float *)(grad + R.rec); p.rec_floats = R.rec_floats;
     p.zero_rec = (const float *)(grad + R.fixed - 256);
     p.g = gin;
+    p.cam = cam;
     prof_begin(kStPreprocessBwd, s);
     const int parts = d.num_views >= 4 ? 4 : (d.num_views >= 2 ? 2 : 1);
     const int per_block = kPreBwdThreads / parts;   // Gaussians per block
     const dim3 grid((unsigned)((d.num_gaussians + per_block - 1) / per_block), (unsigned)num_view_groups(d_all));
     // the projection convention of the forward (lsr_set_projection_contraction): the clamp decision must be its own
+    if (cam.part) {   // the camera gradient: a second launch over the same records (the plain instance follows below)
+#define LSR_PREBWD_CAM(FM) do { \
+            if (parts == 4) hipLaunchKernelGGL((k_preprocess_bwd<4, FM, true>), grid, dim3(kPreBwdThreads), 0, s, p); \
+            else if (parts == 2) hipLaunchKernelGGL((k_preprocess_bwd<2, FM, true>), grid, dim3(kPreBwdThreads), 0, s, p); \
+            else hipLaunchKernelGGL((k_preprocess_bwd<1, FM, true>), grid, dim3(kPreBwdThreads), 0, s, p); } while (0)
+        if (projection_contraction()) LSR_PREBWD_CAM(true); else LSR_PREBWD_CAM(false);
+#undef LSR_PREBWD_CAM
+    }
     if (projection_contraction()) {
         if (parts == 4) hipLaunchKernelGGL((k_preprocess_bwd<4, true>), grid, dim3(kPreBwdThreads), 0, s, p);
         else if (parts == 2) hipLaunchKernelGGL((k_preprocess_bwd<2, true>), grid, dim3(kPreBwdThreads), 0, s, p);

@@ -56,6 +56,7 @@ struct ShParams {
     uint32_t mdiv[2];         // ceil(2^22 / ks): x / ks == (x * mdiv) >> 22 for x < 8192
     uint32_t mdivK, mdivKf;   // same for K (coefficients per colour channel) and Kf
     GroupStrides gs;          // view groups: blockIdx.y = group, every pointer above advances by the group's slices
+    CamGrad cam;              // backward, camera-gradient instances: the partial records (campos / scene-scale slots)
 };
 // the launch's parameters as seen by view group blockIdx.y (uniform: scalar arithmetic)
 __device__ __forceinline__ ShParams group_params(const ShParams &pk) {
@@ -543,7 +544,9 @@ k_preprocess_sh(ShParams pk, PreShArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------
-template <int DEGC, int COFF>
+// CAM: also the campos / scene-scale terms of the camera gradient (lsr_backward_views): the wave (one view, 64 Gaussians)
+// sums them and stores slots kCamPos.. of its partial record.  The instances without it are the code they were.
+template <int DEGC, int COFF, bool CAM = false>
 __global__ void __launch_bounds__(kShThreads, 4)
 k_sh_bwd(ShParams pk) {
     const ShParams p = group_params(pk);
@@ -596,6 +599,7 @@ k_sh_bwd(ShParams pk) {
         float *mg = s_gch + (wave * LSR_WAVE + lane) * cs;
         staged_barrier();
         const bool vis = wave < nv && active && visf > 0.0f;
+        float cq[4] = {0.0f, 0.0f, 0.0f, 0.0f};   // CAM: dL/dcampos, dL/d(scene scale) of this (view, Gaussian)
         if (pay8) {   // channel gradients (clamped colour channels zeroed) go to this thread's LDS row first;
                       // the rolled channel loops below read them back by index
             const float gv[8] = {gq0.x, gq0.y, gq0.z, gq0.w, gq1.x, gq1.y, gq1.z, gq1.w};
@@ -663,6 +667,13 @@ k_sh_bwd(ShParams pk) {
             const float dot = ddx * dir.dx + ddy * dir.dy + ddz * dir.dz;
             const float f = dir.sc / dir.len;
             const float gm[3] = {(ddx - dir.dx * dot) * f, (ddy - dir.dy * dot) * f, (ddz - dir.dz * dot) * f};
+            if constexpr (CAM) {
+                // d(unnormalised direction s m - campos): -> campos with a minus sign, -> s through m
+                const float il = 1.0f / dir.len;
+                const float gx = (ddx - dir.dx * dot) * il, gy = (ddy - dir.dy * dot) * il, gz = (ddz - dir.dz * dot) * il;
+                cq[0] = -gx; cq[1] = -gy; cq[2] = -gz;
+                cq[3] = pos.x * gx + pos.y * gy + pos.z * gz;
+            }
             if (d.vs_means != 0) {
                 float *o3 = p.g.means3D + (size_t)v * d.vs_means + 3 * (size_t)i;
                 o3[0] += gm[0]; o3[1] += gm[1]; o3[2] += gm[2];
@@ -671,6 +682,17 @@ k_sh_bwd(ShParams pk) {
             }
         } else {
             for (int j = 0; j < ntot; ++j) mg[j] = 0.0f;
+        }
+        if constexpr (CAM) {   // (wave-uniform: every lane takes part in the exchanges)
+#pragma unroll
+            for (int m = LSR_WAVE / 2; m >= 1; m >>= 1)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) cq[k] += __shfl_xor(cq[k], m);
+            if (lane < 4 && wave < nv) {
+                const size_t vg = (size_t)blockIdx.y * V + v;   // the view in the whole call
+                p.cam.part[(vg * p.cam.chunks + blockIdx.x) * kCamSlots + kCamPos + lane] =
+                    lane == 0 ? cq[0] : (lane == 1 ? cq[1] : (lane == 2 ? cq[2] : cq[3]));
+            }
         }
         __syncthreads();   // every thread is done reading the coefficient rows
         {   // the SH bases go where the coefficients were (recomputed here rather than kept live
@@ -833,6 +855,7 @@ static ShParams make_params(const lsr_dims &d, const lsr_inputs &in, const GeomL
     p.offF = (LSR_WAVE * p.ks[0] + 3) & ~3;
     for (int g = 0; g < 2; ++g) p.mdiv[g] = mdiv_of(p.ks[g]);
     p.mdivK = mdiv_of(d.sh_coeffs); p.mdivKf = mdiv_of(d.feat_sh_coeffs);
+    p.cam = CamGrad{nullptr, 0};
     return p;
 }
 
@@ -938,36 +961,55 @@ hipError_t launch_preprocess_sh(const lsr_dims &d, const lsr_inputs &in, char *g
     return hipGetLastError();
 }
 
-template <int DEGC, int COFF>
+template <int DEGC, int COFF, bool CAM = false>
 static void allow_big_lds(size_t shm) {
     // function attributes are per device: set on every launch that needs it (a process may drive several GPUs)
     if (shm > 65536)
-        (void)hipFuncSetAttribute((const void *)k_sh_bwd<DEGC, COFF>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
+        (void)hipFuncSetAttribute((const void *)k_sh_bwd<DEGC, COFF, CAM>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
 }
 
-hipError_t launch_sh_backward(const lsr_dims &d, const lsr_inputs &in, const char *geom, const char *grad,
-                              const lsr_in_grads &gin, hipStream_t s) {
-    if (d.num_gaussians == 0) return hipSuccess;
-    if (!group_enabled(d, 0) && !group_enabled(d, 1)) return hipSuccess;
+bool sh_backward_runs(const lsr_dims &d) { return d.num_gaussians > 0 && (group_enabled(d, 0) || group_enabled(d, 1)); }
+
+template <bool CAM>
+static hipError_t sh_backward(const lsr_dims &d, const lsr_inputs &in, const char *geom, const char *grad,
+                              const lsr_in_grads &gin, const CamGrad &cam, hipStream_t s) {
+    if (!sh_backward_runs(d)) return hipSuccess;
     const GeomLayout L = geom_layout(d);
     const GradLayout R = grad_layout(d);
     ShParams p = make_params(d, in, L, geom);
     p.grec = (const float *)(grad + R.rec); p.g = gin;
+    p.cam = cam;
     const int degc = p.has[0] ? d.sh_degree : -1, coff = d.color_mode != LSR_COLOR_NONE ? 3 : 0;
     const dim3 grid((d.num_gaussians + LSR_WAVE - 1) / LSR_WAVE, num_view_groups(d)), block(kShThreads);
     const int cs = (coff + d.feat_channels) | 1;
     const int area = std::max(p.offF + LSR_WAVE * p.ks[1], kShWaves * LSR_WAVE * kShBasisC);
     const size_t shm = ((size_t)area + (size_t)kShWaves * LSR_WAVE * cs) * 4;
     if (shm > 65536) {   // many direct channels next to an SH group
-        if (degc == 4) allow_big_lds<4, 3>(shm); else if (degc == 3) allow_big_lds<3, 3>(shm);
-        else if (degc == 2) allow_big_lds<2, 3>(shm); else if (degc == 1) allow_big_lds<1, 3>(shm);
-        else if (degc == 0) allow_big_lds<0, 3>(shm); else if (coff == 3) allow_big_lds<-1, 3>(shm);
-        else allow_big_lds<-1, 0>(shm);
+        if (degc == 4) allow_big_lds<4, 3, CAM>(shm); else if (degc == 3) allow_big_lds<3, 3, CAM>(shm);
+        else if (degc == 2) allow_big_lds<2, 3, CAM>(shm); else if (degc == 1) allow_big_lds<1, 3, CAM>(shm);
+        else if (degc == 0) allow_big_lds<0, 3, CAM>(shm); else if (coff == 3) allow_big_lds<-1, 3, CAM>(shm);
+        else allow_big_lds<-1, 0, CAM>(shm);
     }
     prof_begin(kStShBwd, s);
-    LSR_SH_DISPATCH(k_sh_bwd, degc, coff, grid, block, shm, s, p);
+    if (degc == 4) hipLaunchKernelGGL((k_sh_bwd<4, 3, CAM>), grid, block, shm, s, p);
+    else if (degc == 3) hipLaunchKernelGGL((k_sh_bwd<3, 3, CAM>), grid, block, shm, s, p);
+    else if (degc == 2) hipLaunchKernelGGL((k_sh_bwd<2, 3, CAM>), grid, block, shm, s, p);
+    else if (degc == 1) hipLaunchKernelGGL((k_sh_bwd<1, 3, CAM>), grid, block, shm, s, p);
+    else if (degc == 0) hipLaunchKernelGGL((k_sh_bwd<0, 3, CAM>), grid, block, shm, s, p);
+    else if (coff == 3) hipLaunchKernelGGL((k_sh_bwd<-1, 3, CAM>), grid, block, shm, s, p);
+    else hipLaunchKernelGGL((k_sh_bwd<-1, 0, CAM>), grid, block, shm, s, p);
     prof_end(kStShBwd, s);
     return hipGetLastError();
+}
+
+hipError_t launch_sh_backward(const lsr_dims &d, const lsr_inputs &in, const char *geom, const char *grad,
+                              const lsr_in_grads &gin, hipStream_t s) {
+    return sh_backward<false>(d, in, geom, grad, gin, CamGrad{nullptr, 0}, s);
+}
+
+hipError_t launch_sh_backward_cam(const lsr_dims &d, const lsr_inputs &in, const char *geom, const char *grad,
+                                  const lsr_in_grads &gin, const CamGrad &cam, hipStream_t s) {
+    return sh_backward<true>(d, in, geom, grad, gin, cam, s);
 }
 
 }  // namespace lsr

@@ -119,4 +119,88 @@ hipError_t launch_pack_view(const float *viewmatrix, const float *projmatrix, co
     return hipGetLastError();
 }
 
+// ---- camera gradient: the fixed-order sum of the partial records (lsr_backward_views) ----
+// Step 1, workgroup (s, v): chunks and pixels of slice s of view v.  Thread (q, j) adds slot j of every 8th partial record
+// of the slice (coalesced 128-byte rows); the 8 row sums and the background sums (dL/dcolour * final T over the slice's
+// pixels) are combined in a fixed order and stored as one second-level record.
+constexpr int kCamThreads = 256;
+__global__ void __launch_bounds__(kCamThreads)
+k_view_grad_partial(const float *__restrict__ part, int chunks, int sh, const float *__restrict__ final_T,
+                    const float *__restrict__ g_color, int HW, float *__restrict__ l2) {
+    const int s = blockIdx.x, v = blockIdx.y, tid = threadIdx.x;
+    __shared__ float s_row[kCamThreads / kCamSlots][kCamSlots];
+    __shared__ float s_bg[kCamThreads / LSR_WAVE][3];
+    const int j = tid & (kCamSlots - 1), q = tid / kCamSlots;
+    // slots a kernel of this call wrote: the geometry's always, the SH direction's when the SH backward ran
+    const bool used = j <= kCamScaleGeo || (sh && j < kCamScaleSh + 1);
+    const int per = (chunks + kCamSplit - 1) / kCamSplit, c0 = s * per, c1 = min(chunks, c0 + per);
+    float a = 0.0f;
+    if (used) {
+#pragma unroll 4
+        for (int c = c0 + q; c < c1; c += kCamThreads / kCamSlots) a += part[((size_t)v * chunks + c) * kCamSlots + j];
+    }
+    s_row[q][j] = a;
+    float b[3] = {0.0f, 0.0f, 0.0f};
+    if (g_color) {
+        const int pper = (HW + kCamSplit - 1) / kCamSplit, p0 = s * pper, p1 = min(HW, p0 + pper);
+#pragma unroll 4
+        for (int px = p0 + tid; px < p1; px += kCamThreads) {
+            const float T = final_T ? final_T[(size_t)v * HW + px] : 1.0f;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) b[c] += g_color[((size_t)v * 3 + c) * HW + px] * T;
+        }
+    }
+#pragma unroll
+    for (int m = LSR_WAVE / 2; m >= 1; m >>= 1)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) b[c] += __shfl_xor(b[c], m);
+    if ((tid & (LSR_WAVE - 1)) == 0)
+        for (int c = 0; c < 3; ++c) s_bg[tid / LSR_WAVE][c] = b[c];
+    __syncthreads();
+    float *o = l2 + ((size_t)v * kCamSplit + s) * kCamL2;
+    if (tid < kCamSlots) {
+        float t = 0.0f;
+        for (int r = 0; r < kCamThreads / kCamSlots; ++r) t += s_row[r][tid];
+        o[tid] = t;
+    } else if (tid < kCamSlots + 3) {
+        float t = 0.0f;
+        for (int w = 0; w < kCamThreads / LSR_WAVE; ++w) t += s_bg[w][tid - kCamSlots];
+        o[tid] = t;
+    }
+}
+
+// Step 2, one 64-thread workgroup per view: the kCamSplit second-level records in order -> the 44 slots of dL/d(view record)
+__global__ void __launch_bounds__(LSR_WAVE)
+k_view_grad_final(const float *__restrict__ l2, float *__restrict__ grad_views) {
+    const int v = blockIdx.x, t = threadIdx.x;
+    if (t >= LSR_VIEW_FLOATS) return;
+    int a = -1, b = -1;      // second-level slots summed into record slot t (-1: none)
+    if (t < 16) { if ((t & 3) != 3) a = kCamVm + 3 * (t >> 2) + (t & 3); }
+    else if (t < 32) { const int k = t - 16, jj = k & 3; if (jj != 2) a = kCamPm + 3 * (k >> 2) + (jj == 3 ? 2 : jj); }
+    else if (t < 35) a = kCamPos + (t - 32);
+    else if (t == 35) a = kCamTanX;
+    else if (t == 36) a = kCamTanY;
+    else if (t < 40) a = kCamSlots + (t - 37);
+    else if (t == 40) { a = kCamScaleGeo; b = kCamScaleSh; }
+    float x = 0.0f, y = 0.0f;
+    for (int s = 0; s < kCamSplit; ++s) {
+        const float *r = l2 + ((size_t)v * kCamSplit + s) * kCamL2;
+        if (a >= 0) x += r[a];
+        if (b >= 0) y += r[b];
+    }
+    grad_views[(size_t)v * LSR_VIEW_FLOATS + t] = x + y;
+}
+
+hipError_t launch_view_grad_reduce(const lsr_dims &d, char *ws, bool sh, const float *final_T, const float *g_color,
+                                   float *grad_views, hipStream_t s) {
+    const ViewGradLayout L = view_grad_layout(d);
+    float *l2 = (float *)(ws + L.l2);
+    prof_begin(kStViewGrad, s);
+    hipLaunchKernelGGL(k_view_grad_partial, dim3(kCamSplit, d.num_views), dim3(kCamThreads), 0, s, (const float *)(ws + L.part),
+                       cam_chunks(d), sh ? 1 : 0, final_T, g_color, d.height * d.width, l2);
+    hipLaunchKernelGGL(k_view_grad_final, dim3(d.num_views), dim3(LSR_WAVE), 0, s, (const float *)l2, grad_views);
+    prof_end(kStViewGrad, s);
+    return hipGetLastError();
+}
+
 }  // namespace lsr

@@ -30,12 +30,12 @@ from ..rasterizer import build_view_table, fused_feature_sh_supported, make_view
 from .geometry import depth_to_relative_disparity, eval_sh, get_fov, homogenize_points
 
 
-def get_projection_matrix(near: Tensor, far: Tensor, fov_x: Tensor, fov_y: Tensor) -> Tensor:
+def get_projection_matrix(near: Tensor, far: Tensor, fov_x: Tensor, fov_y: Tensor, dtype=torch.float32) -> Tensor:
     """(B,) x4 -> (B,4,4) perspective matrix: x,y to (-1,1), z to (0,1), +z forward (no flip)."""
     tan_x, tan_y = (0.5 * fov_x).tan(), (0.5 * fov_y).tan()
     right, top = tan_x * near, tan_y * near
     left, bottom = -right, -top
-    P = near.new_zeros((near.shape[0], 4, 4), dtype=torch.float32)
+    P = near.new_zeros((near.shape[0], 4, 4), dtype=dtype)
     P[:, 0, 0] = 2 * near / (right - left)
     P[:, 1, 1] = 2 * near / (top - bottom)
     P[:, 0, 2] = (right + left) / (right - left)
@@ -64,8 +64,9 @@ class _Cameras:
 
 
 def _cameras(extrinsics: Tensor, near: Tensor, far: Tensor, fov_x: Tensor, fov_y: Tensor) -> _Cameras:
-    proj_t = get_projection_matrix(near, far, fov_x, fov_y).transpose(1, 2)
-    view_t = torch.linalg.inv(extrinsics).transpose(1, 2)
+    # (float64 cameras get a float64 projection: the float32 one could not be multiplied with their view matrix)
+    proj_t = get_projection_matrix(near, far, fov_x, fov_y, torch.promote_types(extrinsics.dtype, torch.float32)).transpose(1, 2)
+    view_t = torch.linalg.inv_ex(extrinsics)[0].transpose(1, 2)   # (no host synchronisation on a device tensor)
     return _Cameras(view_t, view_t @ proj_t, extrinsics[:, :3, 3], (0.5 * fov_x).tan(), (0.5 * fov_y).tan())
 
 
@@ -149,8 +150,10 @@ def _scaled_cameras(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: T
     scale = None
     if scale_invariant:
         scale = 1 / near
-        extrinsics = extrinsics.clone()
-        extrinsics[..., :3, 3] = extrinsics[..., :3, 3] * scale[:, None]
+        # (out of place: the in-place write into a clone broke autograd when `near` requires grad — build_view_table
+        # differentiates this statement of the camera table)
+        translation = extrinsics[..., :3, 3:] * scale[:, None, None]
+        extrinsics = torch.cat([torch.cat([extrinsics[..., :3, :3], translation], -1), extrinsics[..., 3:, :]], -2)
         near, far = near * scale, far * scale
     fov_x, fov_y = get_fov(intrinsics).unbind(dim=-1)
     return _cameras(extrinsics, near, far, fov_x, fov_y), scale

@@ -20,7 +20,7 @@ def homogenize_points(points: Tensor) -> Tensor:
 def get_fov(intrinsics: Tensor) -> Tensor:
     """Field of view (radians) of normalised intrinsics (B,3,3) -> (B,2) as (fov_x, fov_y):
     the angle between the rays through the midpoints of opposite image edges."""
-    inv = torch.linalg.inv(intrinsics)
+    inv = torch.linalg.inv_ex(intrinsics)[0]   # (inv_ex: the same values, without inv's host-side singularity check)
     edge_mid = intrinsics.new_tensor([[0.0, 0.5, 1.0], [1.0, 0.5, 1.0], [0.5, 0.0, 1.0], [0.5, 1.0, 1.0]])
     rays = torch.einsum("bij,ej->bei", inv, edge_mid)          # (B,4,3): left, right, top, bottom
     rays = rays / rays.norm(dim=-1, keepdim=True)

@@ -39,13 +39,14 @@ class GaussianRasterizationSettings(NamedTuple):
 
 
 def make_view_table(viewmatrix: Tensor, projmatrix: Tensor, campos: Tensor, tanfovx, tanfovy,
-                    bg: Tensor, scene_scale=None) -> Tensor:
+                    bg: Tensor, scene_scale=None, dtype=torch.float32) -> Tensor:
     """(V,44) device table: viewmatrix(16) projmatrix(16) campos(3) tanfovx tanfovy bg(3)
     scene_scale(1) reserved(3).  All arguments batched over V; tanfov / scene_scale may be python
     floats or tensors (no host sync).  ``scene_scale`` (default 1) is applied to the Gaussians'
-    means (and squared to their covariances) inside the kernel."""
+    means (and squared to their covariances) inside the kernel.  (``dtype``: float32, what the kernels
+    read; float64 for checking the table's gradient.)"""
     V = viewmatrix.shape[0]
-    dev, dt = viewmatrix.device, torch.float32
+    dev, dt = viewmatrix.device, dtype
 
     def col(t):
         if not torch.is_tensor(t):
@@ -62,8 +63,39 @@ def build_view_table(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: 
                      scale_invariant: bool = True) -> Tensor:
     """(V,44) camera table computed on the device by one kernel (``lsr_build_views``): what the
     reference derives per call with get_fov / get_projection_matrix / inverse / matmul
-    (cuda_splatting.py:75-82,111-118).  ``background`` is ``(3,)`` or ``(V,3)``.  No gradient flows
-    to the cameras (the reference's rasterizer has none either)."""
+    (cuda_splatting.py:75-82,111-118).  ``background`` is ``(3,)`` or ``(V,3)``.
+    Differentiable: when an input requires grad (and grad mode is on) the values are still this kernel's, and the
+    gradient of the table flows back through the same math in PyTorch (``_scaled_cameras`` + :func:`make_view_table`)
+    into extrinsics, intrinsics, near, far and background."""
+    table = _build_view_table(extrinsics, intrinsics, near, far, background, scale_invariant)
+    if torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad
+                                       for t in (extrinsics, intrinsics, near, far, background)):
+        from .decoder.cuda_splatting import _scaled_cameras
+        cams, scale = _scaled_cameras(extrinsics, intrinsics, near, far, scale_invariant)
+        torch_table = make_view_table(cams.view_matrix, cams.full_projection, cams.campos, cams.tan_fov_x,
+                                      cams.tan_fov_y, background.to(table.device), scale)
+        return _straight_through(table, torch_table)
+    return table
+
+
+class _StraightThrough(torch.autograd.Function):
+    """``values`` forward (bit for bit), the gradient to ``carrier`` (same shape)."""
+
+    @staticmethod
+    def forward(ctx, values, carrier):
+        return values.clone()
+
+    @staticmethod
+    def backward(ctx, grad):
+        return None, grad
+
+
+def _straight_through(values: Tensor, carrier: Tensor) -> Tensor:
+    return _StraightThrough.apply(values.detach(), carrier)
+
+
+def _build_view_table(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor, background: Tensor,
+                      scale_invariant: bool) -> Tensor:
     lib = _lib.load()
     dev = extrinsics.device
     if dev.type != "cuda":
@@ -431,10 +463,21 @@ class _RasterizeViews(torch.autograd.Function):
                       None, _ptr(f_depth), None)
         gin = InGrads(_ptr(d_means), _ptr(d_cov), _ptr(d_opac), _ptr(d_color), _ptr(d_feat), _ptr(d_m2d))
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        d_views = None
         with torch.cuda.device(dev):
-            _lib.check(lib.lsr_backward(C.byref(d), C.byref(inp), _ptr(plan.geom), _ptr(plan.bin),
-                                        _ptr(plan.img), plan.num_pairs, _ptr(plan.radii), C.byref(fwd),
-                                        C.byref(gout), _ptr(gradws), C.byref(gin), stream), "lsr_backward")
+            if ctx.needs_input_grad[0]:
+                # the camera gradient as well (lsr_backward_views): the same kernels' camera-gradient instances, then a
+                # fixed-order reduction of their partial records
+                d_views = torch.empty((V, _lib.VIEW_FLOATS), **f32)
+                vgws = torch.empty(lib.lsr_view_grad_workspace_bytes(C.byref(d)), dtype=torch.uint8, device=dev)
+                _lib.check(lib.lsr_backward_views(C.byref(d), C.byref(inp), _ptr(plan.geom), _ptr(plan.bin),
+                                                  _ptr(plan.img), plan.num_pairs, _ptr(plan.radii), C.byref(fwd),
+                                                  C.byref(gout), _ptr(gradws), C.byref(gin), _ptr(d_views), _ptr(vgws),
+                                                  stream), "lsr_backward_views")
+            else:
+                _lib.check(lib.lsr_backward(C.byref(d), C.byref(inp), _ptr(plan.geom), _ptr(plan.bin),
+                                            _ptr(plan.img), plan.num_pairs, _ptr(plan.radii), C.byref(fwd),
+                                            C.byref(gout), _ptr(gradws), C.byref(gin), stream), "lsr_backward")
             if ctx.debug:
                 torch.cuda.synchronize(dev)
         if not want_m2d:
@@ -443,7 +486,7 @@ class _RasterizeViews(torch.autograd.Function):
             d_m2d = d_m2d.sum(0) if V > 1 else d_m2d[0]
         # order: views, means3D, means2D, cov3D, opacities, shs, colors_precomp, features, H, W, deg,
         #        debug, feat_sh_degree, shs_channel_major
-        return (None, d_means, d_m2d, d_cov, d_opac, d_color if has_shs else None,
+        return (d_views, d_means, d_m2d, d_cov, d_opac, d_color if has_shs else None,
                 d_color if has_cp else None, d_feat, None, None, None, None, None, None, None, None, None)
 
 
@@ -457,6 +500,8 @@ def rasterize_views(views: Tensor, image_height: int, image_width: int, sh_degre
     per-Gaussian tensor is either shared ``(G,...)`` or per view ``(V,G,...)``.
     Returns ``(color (V,3,H,W)|None, feature (V,C,H,W)|None, mask (V,H,W), depth (V,H,W), radii (V,G))``.
     ``means2D`` (optional, ``(V,G,3)``) only exists to receive the NDC-space mean gradient.
+    A ``views`` table that requires grad receives dL/d(view record) (``lsr_backward_views``; slot by slot in
+    include/lsr_rasterizer.h): viewmatrix, projmatrix, campos, tan(fov), background and scene scale.
 
     Scene-level (fused) inputs, all optional: ``cov3D_precomp`` may be full ``(...,3,3)`` matrices;
     ``feature_sh (..., C, Kf)`` (instead of ``features``) makes the kernel evaluate the latent
@@ -531,7 +576,21 @@ def _covariance_from_scale_rotation(scales: Tensor, rotations: Tensor, modifier:
 
 def _pack_view(rs: GaussianRasterizationSettings, dev) -> Tensor:
     """(1,44) view record of one settings tuple: one small launch (lsr_pack_view) instead of ~8 PyTorch
-    ops; tan(fov) goes by value when it is a Python number and stays on the device when it is a tensor."""
+    ops; tan(fov) goes by value when it is a Python number and stays on the device when it is a tensor.
+    Differentiable in viewmatrix, projmatrix, campos, bg and tensor tan(fov) (the values stay this launch's)."""
+    out = _pack_view_dev(rs, dev)
+    cam = (rs.viewmatrix, rs.projmatrix, rs.campos, rs.bg, rs.tanfovx, rs.tanfovy)
+    if torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in cam):
+        f = lambda t: t.to(device=dev, dtype=torch.float32) if torch.is_tensor(t) else t
+        tx, ty = f(rs.tanfovx), f(rs.tanfovy)
+        carrier = make_view_table(f(rs.viewmatrix).reshape(1, 16), f(rs.projmatrix).reshape(1, 16),
+                                  f(rs.campos).reshape(1, 3), tx.reshape(1) if torch.is_tensor(tx) else tx,
+                                  ty.reshape(1) if torch.is_tensor(ty) else ty, f(rs.bg).reshape(1, 3))
+        return _straight_through(out, carrier)
+    return out
+
+
+def _pack_view_dev(rs: GaussianRasterizationSettings, dev) -> Tensor:
     if dev.type != "cuda":
         raise LsrError("latentsplat_amd rasterizer runs on MI355X only: tensors must be on a ROCm ('cuda') device; "
                        "there is no CPU fallback")
