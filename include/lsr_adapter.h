@@ -18,8 +18,8 @@
  *         means = origin + normalize(K^-1 [x y 1]) rotated to world * depth
  *   - src/model/decoder/cuda_splatting.py:148,157   the per-view `triu_indices` gather of the
  *         covariance: cov_elems = 6 emits the packed upper triangle (xx,xy,xz,yy,yz,zz) directly.
- * Not covered (stays in PyTorch): the SH coefficient masks and `rotate_sh` (e3nn Wigner-D,
- * gaussian_adapter.py:92-94,107-108) — e3nn is not a dependency of this library.
+ * The SH coefficient masks and `rotate_sh` (gaussian_adapter.py:90-93,107-108) are the companion
+ * kernels of include/lsr_sh_rotate.h.
  *
  * Element indexing.  `num_cameras` context cameras (b*v); per camera `rays` parameter rows
  * (r*srf); per row `samples` depth samples (spp) that share the row's raw scale / rotation /

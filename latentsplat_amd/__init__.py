@@ -2,6 +2,17 @@
 
 Only what the hot path needs: ``csrc/`` (HIP kernels + C ABI), ``rasterizer`` (drop-in
 ``GaussianRasterizer`` API + batched multi-view op), ``decoder`` (mirror of the reference's
-``src/model/decoder`` surface) and ``synthetic`` (seeded scenes for tests / bench).
+``src/model/decoder`` surface), ``gaussian_adapter`` / ``sh_rotate`` (the encoder's adapter tail:
+geometry and SH coefficient rotation) and ``synthetic`` (seeded scenes for tests / bench).
 """
 __version__ = "0.1.0"
+
+_LAZY = {"rotate_sh": "sh_rotate", "GaussianAdapter": "gaussian_adapter", "GaussianAdapterCfg": "gaussian_adapter",
+         "Gaussians": "gaussian_adapter"}
+
+
+def __getattr__(name):     # torch is imported only when one of these is first used
+    if name in _LAZY:
+        from importlib import import_module
+        return getattr(import_module(f"{__name__}.{_LAZY[name]}"), name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

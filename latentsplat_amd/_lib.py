@@ -1,4 +1,5 @@
-"""ctypes binding of ``liblsr_hip.so`` (C ABI: include/lsr_rasterizer.h, include/lsr_adapter.h, include/lsr_latent.h, include/lsr_ply.h).
+"""ctypes binding of ``liblsr_hip.so`` (C ABI: include/lsr_rasterizer.h, include/lsr_adapter.h, include/lsr_latent.h, include/lsr_ply.h,
+include/lsr_sh_rotate.h).
 
 The library is built in-tree by ``latentsplat_amd/csrc/Makefile`` (``__graft_entry__.build()``).
 There is no CPU fallback: if the shared object is missing or not loadable this module raises, and
@@ -118,6 +119,21 @@ class PlyInputs(C.Structure):        # lsr_ply_inputs (include/lsr_ply.h)
 
 PLY_VERTEX_FLOATS = 17
 
+
+class ShRotateDims(C.Structure):     # lsr_sh_rotate_dims (include/lsr_sh_rotate.h)
+    _fields_ = [("num_cameras", C.c_int32), ("rays", C.c_int32), ("samples", C.c_int32),
+                ("color_coeffs", C.c_int32), ("feat_channels", C.c_int32), ("feat_coeffs", C.c_int32),
+                ("table_stride", C.c_int32), ("reserved0", C.c_int32), ("row_stride", C.c_int64)]
+
+
+SH_ROTATE_MAX_DEGREE = 4
+
+
+def sh_rotate_table_floats(degree: int) -> int:
+    """LSR_SH_ROTATE_TABLE_FLOATS: sum of (2l+1)^2 over l <= degree."""
+    return (degree + 1) * (2 * degree + 1) * (2 * degree + 3) // 3
+
+
 EXPORTS = (
     "lsr_abi_version", "lsr_error_string", "lsr_last_hip_error", "lsr_geom_workspace_bytes",
     "lsr_image_workspace_bytes", "lsr_binning_workspace_bytes", "lsr_grad_workspace_bytes",
@@ -127,6 +143,7 @@ EXPORTS = (
     "lsr_debug_set_knob", "lsr_set_projection_contraction", "lsr_get_projection_contraction",
     "lsr_adapter_forward", "lsr_adapter_backward", "lsr_latent_forward", "lsr_latent_backward",
     "lsr_ply_pack", "lsr_ply_write_host",
+    "lsr_sh_rotation_matrices", "lsr_sh_rotate_forward", "lsr_sh_rotate_backward",
 )
 
 _lib = None
@@ -232,6 +249,12 @@ def load():
     lib.lsr_ply_pack.argtypes = [I64, I32, C.POINTER(PlyInputs), P, P]
     lib.lsr_ply_write_host.restype = C.c_int
     lib.lsr_ply_write_host.argtypes = [C.c_char_p, P, I64]
+    lib.lsr_sh_rotation_matrices.restype = C.c_int
+    lib.lsr_sh_rotation_matrices.argtypes = [I32, P, I64, I64, I32, P, P]
+    lib.lsr_sh_rotate_forward.restype = C.c_int
+    lib.lsr_sh_rotate_forward.argtypes = [C.POINTER(ShRotateDims), P, P, P, P, P, P, P]
+    lib.lsr_sh_rotate_backward.restype = C.c_int
+    lib.lsr_sh_rotate_backward.argtypes = [C.POINTER(ShRotateDims), P, P, P, P, P, P, P]
     _lib = lib
     return lib
 

@@ -5,21 +5,27 @@ scale map, quaternion → rotation, covariance, camera-to-world rotation, ray un
 kernel forward and one backward (csrc/adapter.hip, C ABI include/lsr_adapter.h) instead of ~45
 PyTorch ops each way.
 
+The colour and feature harmonics — degree masks, broadcast over the depth samples and ``rotate_sh``
+(:90-93,107-108; src/misc/sh_utils.py:100-120) — are one more HIP kernel each way
+(csrc/sh_rotate.hip, include/lsr_sh_rotate.h), which reads ``raw_gaussians[..., 7:]`` in place; its
+rotation matrices are computed from the camera rotation itself, so e3nn is not needed.
+
 Same names, argument meaning and return type as the reference.  ROCm tensors only — there is no
-CPU fallback.  ``rotate_sh`` (e3nn Wigner-D, gaussian_adapter.py:107-108) is not part of the
-kernel: it is taken from e3nn when that is installed, or injected through ``rotate_sh=``.
+CPU fallback.  A callable injected through ``rotate_sh=`` takes precedence over the fused kernel
+and is applied to the masked, broadcast coefficients with stock PyTorch ops, as the reference does.
 """
 from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from math import isqrt, prod
+from math import prod
 from typing import Callable, Optional
 
 import torch
 from torch import Tensor, nn
 
 from . import _lib
+from .sh_rotate import rotate_harmonics
 from ._lib import AdapterDims, AdapterInGrads, AdapterInputs, AdapterOutGrads, AdapterOutputs
 
 
@@ -133,24 +139,6 @@ def adapter_geometry(extrinsics: Tensor, intrinsics: Tensor, coordinates: Tensor
                                   float(scale_min), float(scale_max), float(eps), 6 if packed_covariance else 9)
 
 
-def _e3nn_rotate_sh(sh_coefficients: Tensor, rotations: Tensor) -> Tensor:
-    """SH coefficient rotation by per-degree Wigner-D matrices (what gaussian_adapter.py:107-108
-    obtains from src/misc/sh_utils.py:100-120); requires e3nn."""
-    try:
-        from e3nn.o3 import matrix_to_angles, wigner_D
-    except ImportError as e:  # pragma: no cover - e3nn is absent from the build image
-        raise _lib.LsrError("rotate_sh needs e3nn; install it or pass rotate_sh= to GaussianAdapter") from e
-    n = sh_coefficients.shape[-1]
-    angles = matrix_to_angles(rotations)
-    bands = []
-    for degree in range(isqrt(n)):
-        with torch.device(sh_coefficients.device):
-            D = wigner_D(degree, *angles).to(sh_coefficients.dtype)
-        band = sh_coefficients[..., degree * degree:(degree + 1) * (degree + 1)]
-        bands.append((D @ band[..., None])[..., 0])
-    return torch.cat(bands, dim=-1)
-
-
 class GaussianAdapter(nn.Module):     # gaussian_adapter.py:32-139
     cfg: GaussianAdapterCfg
 
@@ -159,7 +147,7 @@ class GaussianAdapter(nn.Module):     # gaussian_adapter.py:32-139
         super().__init__()
         self.cfg = cfg
         self.n_feature_channels = n_feature_channels
-        self._rotate_sh = rotate_sh or _e3nn_rotate_sh
+        self._rotate_sh = rotate_sh      # None: the fused HIP path
         for name, degree, size in (("color_sh_mask", cfg.color_sh_degree, self.d_color_sh),
                                    ("feature_sh_mask", cfg.feature_sh_degree, self.d_feature_sh)):
             mask = torch.ones((size,), dtype=torch.float32)
@@ -219,19 +207,34 @@ class GaussianAdapter(nn.Module):     # gaussian_adapter.py:32-139
         means, cov, scales, rot = adapter_geometry(ext, itr, coords, dep, raw7, image_shape,
                                                    self.cfg.gaussian_scale_min, self.cfg.gaussian_scale_max, eps)
 
-        color_sh, feature_sh = raw_gaussians[..., 7:].split(
-            (3 * self.d_color_sh, self.n_feature_channels * self.d_feature_sh), dim=-1)
-        color_sh = color_sh.reshape(*color_sh.shape[:-1], 3, self.d_color_sh)
-        feature_sh = feature_sh.reshape(*feature_sh.shape[:-1], self.n_feature_channels, self.d_feature_sh)
-        color_sh = color_sh.broadcast_to((*batch, 3, self.d_color_sh)) * self.color_sh_mask
-        feature_sh = feature_sh.broadcast_to((*batch, self.n_feature_channels, self.d_feature_sh)) * self.feature_sh_mask
-        c2w = extrinsics[..., :3, :3]
         rot = rot.reshape(row_batch + ((1,) if shared_over_samples else ()) + (4,))
+        if self._rotate_sh is None:
+            # masks, camera-to-world rotation of both tensors and the sample broadcast: one launch each way
+            width = 3 * self.d_color_sh + self.n_feature_channels * self.d_feature_sh
+            if raw_gaussians.shape[-1] != 7 + width:
+                raise _lib.LsrError(f"raw_gaussians has {raw_gaussians.shape[-1]} columns, expected d_in = {7 + width}")
+            color_sh, feature_sh = rotate_harmonics(
+                rows(raw_gaussians[..., 7:], rb, width), ext, samples, self.d_color_sh,
+                self.n_feature_channels, self.d_feature_sh if self.n_feature_channels > 0 else 0,
+                self.color_sh_mask, self.feature_sh_mask)
+            color_sh = color_sh.reshape(batch + (3, self.d_color_sh))
+            feature_sh = (feature_sh.reshape(batch + (self.n_feature_channels, self.d_feature_sh))
+                          if feature_sh is not None else color_sh.new_zeros(batch + (0, self.d_feature_sh)))
+        else:
+            color_sh, feature_sh = raw_gaussians[..., 7:].split(
+                (3 * self.d_color_sh, self.n_feature_channels * self.d_feature_sh), dim=-1)
+            color_sh = color_sh.reshape(*color_sh.shape[:-1], 3, self.d_color_sh)
+            feature_sh = feature_sh.reshape(*feature_sh.shape[:-1], self.n_feature_channels, self.d_feature_sh)
+            color_sh = color_sh.broadcast_to((*batch, 3, self.d_color_sh)) * self.color_sh_mask
+            feature_sh = feature_sh.broadcast_to((*batch, self.n_feature_channels, self.d_feature_sh)) * self.feature_sh_mask
+            c2w = extrinsics[..., :3, :3]
+            color_sh = self._rotate_sh(color_sh, c2w[..., None, :, :])
+            feature_sh = self._rotate_sh(feature_sh, c2w[..., None, :, :])
         return Gaussians(
             means=means.reshape(batch + (3,)),
             covariances=cov.reshape(batch + (3, 3)),
-            color_harmonics=self._rotate_sh(color_sh, c2w[..., None, :, :]),
-            feature_harmonics=self._rotate_sh(feature_sh, c2w[..., None, :, :]),
+            color_harmonics=color_sh,
+            feature_harmonics=feature_sh,
             opacities=opacities,
             scales=scales.reshape(batch + (3,)),
             rotations=rot.broadcast_to(batch + (4,)),

@@ -24,6 +24,10 @@ Every call is made exactly like the reference makes it (cuda_splatting.py:132-15
 `GaussianRasterizationSettings` with the 12 keyword fields and one `GaussianRasterizer(settings)(...)`
 call per view, `means2D` a zero tensor that requires grad, 5-tuple unpacked.
 
+One more case needs e3nn instead of the fork: `--only e3nn_rotate_sh` writes tests/golden/e3nn_rotate_sh.npz, the reference's
+`rotate_sh` (e3nn Wigner-D) on random and near-gimbal-lock rotations; `tests/test_sh_rotate_e3nn_cpu.py` pins this
+repository's e3nn-free SH rotation to it.
+
 What the vectors decide (SURVEY.md Appendix A.4 "fork deltas", all [INF]/[UNK] today):
   * mask = 1 - T_final?  depth = sum alpha T z, un-normalised?      -> case fork_probe_layers
   * colour SH axis convention at degree >= 1 and the degree-4 band   -> case fork_probe_sh_axes
@@ -179,6 +183,47 @@ def run_case(mod, name, scene, H, W, bg, device, seed=0):
     return rec
 
 
+E3NN_CASE = "e3nn_rotate_sh"
+
+
+def dump_e3nn_rotate_sh(out_dir, prefix=""):
+    """tests/golden/e3nn_rotate_sh.npz: what e3nn's Wigner-D route (the reference's rotate_sh, src/misc/sh_utils.py:100-120:
+    matrix_to_angles, wigner_D per degree, one matmul per band) gives for random proper rotations, rotations near the gimbal
+    lock of its Y-X-Y angles, and random coefficients — all in float64.  Needs e3nn, nothing else; consumed by
+    tests/test_sh_rotate_e3nn_cpu.py, which pins this repository's e3nn-free rotation to it."""
+    from e3nn.o3 import matrix_to_angles, wigner_D
+    import e3nn
+    rng = np.random.default_rng(2024)
+    q = rng.normal(size=(48, 4))
+    q /= np.linalg.norm(q, axis=-1, keepdims=True)
+    x, y, z, w = q.T
+    rots = [np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
+                      2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
+                      2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], -1).reshape(-1, 3, 3)]
+
+    def about(axis, angle):
+        c, s = np.cos(angle), np.sin(angle)
+        i, j = [(1, 2), (2, 0), (0, 1)][axis]
+        R = np.eye(3)
+        R[i, i] = c; R[i, j] = -s; R[j, i] = s; R[j, j] = c
+        return R
+    near = [about(1, a) @ about(0, b) @ about(1, g) for b in (1e-6, 3e-7, np.pi - 1e-6, np.pi - 2e-7)
+            for a, g in ((0.3, -1.1), (2.0, 2.5))]
+    rots.append(np.stack([np.eye(3)] + [about(a, np.pi) for a in range(3)] + near))
+    R = torch.tensor(np.concatenate(rots))                    # float64
+    coeffs = torch.tensor(rng.normal(size=(R.shape[0], 3, 25)))
+    alpha, beta, gamma = matrix_to_angles(R)
+    bands = []
+    for degree in range(5):
+        D = wigner_D(degree, alpha, beta, gamma).to(torch.float64)
+        bands.append(torch.einsum("nij,ncj->nci", D, coeffs[..., degree * degree:(degree + 1) ** 2]))
+    path = os.path.join(out_dir, prefix + E3NN_CASE + ".npz")
+    np.savez_compressed(path, format_version=np.int32(FORMAT_VERSION), rotations=R.numpy(), coefficients=coeffs.numpy(),
+                        rotated=torch.cat(bands, dim=-1).numpy(), num_near_gimbal=np.int32(len(near)),
+                        meta_json=np.array(json.dumps(dict(e3nn=e3nn.__version__, torch=torch.__version__))))
+    print(f"wrote {path} ({os.path.getsize(path) / 1024:.0f} KiB)")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden"))
@@ -187,8 +232,14 @@ def main(argv=None):
     ap.add_argument("--prefix", default="", help="file name prefix (tests use it to keep self-test dumps apart)")
     ap.add_argument("--only", default="", help="comma-separated case names")
     args = ap.parse_args(argv)
-    mod = importlib.import_module(args.module)
     os.makedirs(args.out, exist_ok=True)
+    # the e3nn vectors need e3nn only (no rasterizer module) and are written on request: `--only e3nn_rotate_sh`
+    only = [n for n in args.only.split(",") if n]
+    if E3NN_CASE in only:
+        dump_e3nn_rotate_sh(args.out, args.prefix)
+        if only == [E3NN_CASE]:
+            return
+    mod = importlib.import_module(args.module)
     meta = dict(module=args.module, module_file=getattr(mod, "__file__", "?"), torch=torch.__version__,
                 device=(torch.cuda.get_device_name(0) if args.device.startswith("cuda") and torch.cuda.is_available() else args.device))
     for name, (scene, H, W, bg) in cases().items():
