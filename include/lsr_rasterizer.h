@@ -56,8 +56,22 @@ extern "C" {
  *   [40]     scene scale — means3D are multiplied by it and covariances by its square before
  *                          projection (the `1/near` scale invariance of cuda_splatting.py:75-82
  *                          applied in-kernel; 1.0 when the caller already scaled its inputs)
- *   [41..43] reserved (0)                                                                      */
+ *   [41]     depth mode  — LSR_DEPTH_* as a float; 0.0 (LSR_DEPTH_NATIVE, what lsr_build_views / lsr_pack_view write):
+ *                          the depth output blends the view-space z of the scaled scene, as it always did
+ *   [42], [43] near, far — the caller's UNSCALED near / far (cuda_splatting.py:298-340 `render_depth_cuda`); read only
+ *                          when [41] != 0, 0.0 otherwise
+ * Depth modes (all in one pass: the projection kernels write d instead of z into the screen record, the compositing
+ * kernels blend it with the weights, skips and early stop of every other channel; no background term).  The
+ * reference renders a per-Gaussian value u as a grey degree-0 SH colour and takes the channel mean, hence
+ *   d = max(0, C0 u + 0.5),  C0 = 0.28209479177387814,  z = tz / view[40] (camera-space depth of the unscaled scene),
+ *   n = view[42], f = view[43], e = 1e-10:
+ *   LSR_DEPTH_DEPTH               u = z
+ *   LSR_DEPTH_DISPARITY           u = 1 / z
+ *   LSR_DEPTH_RELATIVE_DISPARITY  u = 1 - (1 / (z + e) - 1 / (f + e)) / (1 / (n + e) - 1 / (f + e) + e)
+ *   LSR_DEPTH_LOG                 u = log(max(min(z, n), f))   — the reference's expression, literally: log(f) when n < f
+ * Colour, features, mask, radii, n_contrib, the lists and the sort keys do not depend on the mode.                 */
 #define LSR_VIEW_FLOATS 44
+enum { LSR_DEPTH_NATIVE = 0, LSR_DEPTH_DEPTH = 1, LSR_DEPTH_DISPARITY = 2, LSR_DEPTH_RELATIVE_DISPARITY = 3, LSR_DEPTH_LOG = 4 };
 
 enum { LSR_COLOR_NONE = 0, LSR_COLOR_SH = 1, LSR_COLOR_PRECOMP = 2 };
 enum { LSR_FEAT_DIRECT = 0, LSR_FEAT_SH = 1 };
@@ -175,7 +189,7 @@ typedef struct lsr_outputs {
     float *color;    /* [V][3][H][W] or NULL */
     float *feature;  /* [V][C][H][W] or NULL */
     float *mask;     /* [V][H][W]  = 1 - T_final */
-    float *depth;    /* [V][H][W]  = sum_i alpha_i T_i z_i */
+    float *depth;    /* [V][H][W]  = sum_i alpha_i T_i z_i (z_i: the view's depth mode applied, views[41..43]) */
     int32_t *radii;  /* [V][G] screen radius in pixels, 0 = culled (5th tuple element) */
     void *grad_ws;   /* (ABI v9) forward calls with LSR_FWD_CLEARS_GRAD: the gradient workspace to zero; else ignored (NULL) */
 } lsr_outputs;
@@ -246,6 +260,13 @@ int lsr_get_layout(const lsr_dims *d, int64_t num_pairs, lsr_layout *out);
 int lsr_build_views(int32_t num_views, const float *extrinsics, const float *intrinsics, const float *near,
                     const float *far, const float *bg, int32_t bg_view_stride, int32_t scale_invariant,
                     float *views_out, lsr_stream_t stream);
+
+/* ---- the same table with a depth mode (LSR_DEPTH_*, one for all views of the call): slot [41] = the mode and, for a
+ * mode other than LSR_DEPTH_NATIVE, slots [42] / [43] = near / far as given (before the 1/near scaling).  Still one tiny
+ * launch; depth_mode == LSR_DEPTH_NATIVE writes what lsr_build_views writes.  LSR_EINVAL for an unknown mode. */
+int lsr_build_views_depth(int32_t num_views, const float *extrinsics, const float *intrinsics, const float *near,
+                          const float *far, const float *bg, int32_t bg_view_stride, int32_t scale_invariant,
+                          int32_t depth_mode, float *views_out, lsr_stream_t stream);
 
 /* ---- one view record straight from the 12-field `GaussianRasterizationSettings` of the reference's
  * per-view call (cuda_splatting.py:132-145): device pointers to `viewmatrix` [16], `projmatrix` [16],
@@ -372,8 +393,13 @@ int lsr_backward(const lsr_dims *d, const lsr_inputs *in, const void *geom_ws,
  *            is active the clamped t.x / t.y is a constant, as in the forward's gradient convention: no gradient
  *            through the limit
  *   [37..39] bg: sum over the pixels of dL/dcolour * final transmittance (0 without a colour gradient)
- *   [40]     scene scale: sum dL/dp . mean + 2 s dL/dSigma : cov, plus the SH direction's term
- *   [41..43] 0
+ *   [40]     scene scale: sum dL/dp . mean + 2 s dL/dSigma : cov, plus the SH direction's term and, under a depth mode,
+ *            the explicit term of z = tz / s: sum dL/dd dd/dz (-tz / s^2)
+ *   [41]     depth mode: 0 (no gradient)
+ *   [42, 43] near / far of the depth modes: sum dL/dd dd/dn, sum dL/dd dd/df (dL/dd: the depth output's gradient on the
+ *            Gaussian's payload; dd/du = C0 where C0 u + 0.5 >= 0, else 0; min / max pass their gradient to the selected
+ *            argument); exactly 0 for LSR_DEPTH_NATIVE, LSR_DEPTH_DEPTH and LSR_DEPTH_DISPARITY
+ * (dL/dt.z above carries dL/dd dd/dz / s under a depth mode instead of the depth output's own gradient.)
  * Sums run over the visible (view, Gaussian) pairs; culled Gaussians, radii, tile rectangles and list membership
  * contribute nothing.  With G == 0 only bg is non-zero (final transmittance 1). */
 size_t lsr_view_grad_workspace_bytes(const lsr_dims *d);

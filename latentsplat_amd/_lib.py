@@ -19,6 +19,7 @@ VIEW_FLOATS = 44
 COLOR_NONE, COLOR_SH, COLOR_PRECOMP = 0, 1, 2
 FEAT_DIRECT, FEAT_SH = 0, 1
 SH_AXES_3DGS, SH_AXES_REFERENCE = 0, 1   # lsr_dims.color_sh_convention
+DEPTH_NATIVE, DEPTH_DEPTH, DEPTH_DISPARITY, DEPTH_RELATIVE_DISPARITY, DEPTH_LOG = 0, 1, 2, 3, 4   # LSR_DEPTH_*: view slot 41
 FWD_FOR_BACKWARD = 1                      # lsr_dims.forward_flags
 FWD_CLEARS_GRAD = 2
 FWD_REACHED_ONLY = 4
@@ -137,7 +138,7 @@ def sh_rotate_table_floats(degree: int) -> int:
 EXPORTS = (
     "lsr_abi_version", "lsr_error_string", "lsr_last_hip_error", "lsr_geom_workspace_bytes",
     "lsr_image_workspace_bytes", "lsr_binning_workspace_bytes", "lsr_grad_workspace_bytes",
-    "lsr_get_layout", "lsr_build_views", "lsr_pack_view", "lsr_forward_prepare", "lsr_forward_render", "lsr_forward_nosync", "lsr_forward_speculative", "lsr_forward_front",
+    "lsr_get_layout", "lsr_build_views", "lsr_build_views_depth", "lsr_pack_view", "lsr_forward_prepare", "lsr_forward_render", "lsr_forward_nosync", "lsr_forward_speculative", "lsr_forward_front",
     "lsr_forward_status", "lsr_forward_abandon", "lsr_backward", "lsr_view_grad_workspace_bytes", "lsr_backward_views",
     "lsr_profile_enable", "lsr_profile_num_stages", "lsr_profile_stage_name", "lsr_profile_read",
     "lsr_debug_set_knob", "lsr_set_projection_contraction", "lsr_get_projection_contraction",
@@ -198,6 +199,9 @@ def load():
     lib.lsr_get_layout.argtypes = [C.POINTER(Dims), I64, C.POINTER(Layout)]
     lib.lsr_build_views.restype = C.c_int
     lib.lsr_build_views.argtypes = [I32, P, P, P, P, P, I32, I32, P, P]
+    if hasattr(lib, "lsr_build_views_depth"):  # (absent from an earlier build selected with LSR_LIB for an A/B)
+        lib.lsr_build_views_depth.restype = C.c_int
+        lib.lsr_build_views_depth.argtypes = [I32, P, P, P, P, P, I32, I32, I32, P, P]
     lib.lsr_pack_view.restype = C.c_int
     lib.lsr_pack_view.argtypes = [P, P, P, P, C.c_float, C.c_float, P, P, P, P]
     lib.lsr_forward_prepare.restype = C.c_int

@@ -404,6 +404,18 @@ int lsr_build_views(int32_t num_views, const float *extrinsics, const float *int
     return LSR_OK;
 }
 
+int lsr_build_views_depth(int32_t num_views, const float *extrinsics, const float *intrinsics, const float *near,
+                          const float *far, const float *bg, int32_t bg_view_stride, int32_t scale_invariant,
+                          int32_t depth_mode, float *views_out, lsr_stream_t stream) {
+    g_last_hip_error = 0;
+    if (num_views < 1 || (bg_view_stride != 0 && bg_view_stride != 3)) return LSR_EINVAL;
+    if (depth_mode < LSR_DEPTH_NATIVE || depth_mode > LSR_DEPTH_LOG) return LSR_EINVAL;
+    if (!extrinsics || !intrinsics || !near || !far || !bg || !views_out) return LSR_ENULL;
+    LSR_HIP(launch_build_views(num_views, extrinsics, intrinsics, near, far, bg, bg_view_stride,
+                               scale_invariant != 0, views_out, (hipStream_t)stream, depth_mode));
+    return LSR_OK;
+}
+
 int lsr_pack_view(const float *viewmatrix, const float *projmatrix, const float *campos, const float *bg,
                   float tanfovx, float tanfovy, const float *tanfovx_dev, const float *tanfovy_dev, float *view_out,
                   lsr_stream_t stream) {
@@ -774,7 +786,8 @@ int lsr_backward_views(const lsr_dims *d, const lsr_inputs *in, const void *geom
                                                           d->color_mode != LSR_COLOR_NONE ? gout->color : nullptr, grad_views, s));
         return LSR_OK;
     }
-    const CamGrad cam{(float *)((char *)view_grad_ws + view_grad_layout(*d).part), cam_chunks(*d)};
+    const CamGrad cam{(float *)((char *)view_grad_ws + view_grad_layout(*d).part), cam_chunks(*d),
+                      (float *)((char *)view_grad_ws + view_grad_layout(*d).dpart)};
     rc = backward_impl(d, in, geom_ws, bin_ws, img_ws, num_pairs, radii, fwd, gout, grad_ws, gin, &cam, s);
     if (rc) return rc;
     const float *final_T = (const float *)((const char *)img_ws + img_layout(*d).final_T);

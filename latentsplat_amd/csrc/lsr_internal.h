@@ -61,7 +61,8 @@ inline int64_t num_tiles(const lsr_dims &d) { return (int64_t)tiles_x(d) * tiles
 
 // Screen-space record of one (view, Gaussian), written by k_preprocess and gathered (one 64-byte
 // line for <= 8 payload channels) by the compositing kernels:
-//   [0] x_pix [1] y_pix [2] conicA [3] conicB [4] conicC [5] opacity [6] view z [7] unused (0)
+//   [0] x_pix [1] y_pix [2] conicA [3] conicB [4] conicC [5] opacity [6] view z, or the view's depth mode applied to it
+//   (lsr_depth.h): payload of the depth image, nothing else reads it  [7] unused (0)
 //   [8 + c] payload channel c: rgb first when colour is rendered, then the feature channels; zero padded.
 // The packed gradient record of the backward pass (GradLayout) uses the same slot numbering.
 inline int rec_floats(const lsr_dims &d) {
@@ -282,7 +283,7 @@ hipError_t launch_pack_view(const float *viewmatrix, const float *projmatrix, co
                             hipStream_t s);
 hipError_t launch_build_views(int V, const float *extrinsics, const float *intrinsics, const float *near,
                               const float *far, const float *bg, int bg_stride, int scale_invariant,
-                              float *out, hipStream_t s);
+                              float *out, hipStream_t s, int depth_mode = LSR_DEPTH_NATIVE);
 // Stages that sum over views (SH kernels, geometry backward) work per view group (lsr_dims::views_per_group:
 // b scenes x n views in one call).  They take the WHOLE call's dims / inputs and run all groups in ONE launch,
 // the group in blockIdx.y: inside the kernel a group looks like a call of its own n views with shared inputs
@@ -341,23 +342,27 @@ hipError_t launch_render_backward(const lsr_dims &d, const lsr_inputs &in, const
 //   [0, 12)  viewmatrix vm[4c + k] at 3c + k (c = 0..3, k = 0..2; vm[3, 7, 11, 15] are never read)
 //   [12, 24) projmatrix pm[4c + j] at 12 + 3c + (0, 1, 2 for j = 0, 1, 3; column 2 is never read)
 //   24, 25   tanfovx, tanfovy;  26 scene scale (geometry);  27..29 campos, 30 scene scale (SH direction);  31 unused
+// The depth modes' near / far gradients (view slots 42, 43) do not fit the 32 slots: the geometry kernel stores them as one
+// pair per (view, chunk) in an array of their own (CamGrad::dpart), summed by the same two kernels in the same fixed order.
 constexpr int kCamSlots = 32;
 enum { kCamVm = 0, kCamPm = 12, kCamTanX = 24, kCamTanY = 25, kCamScaleGeo = 26, kCamPos = 27, kCamScaleSh = 30 };
 constexpr int kCamSplit = 64;    // workgroups per view of the first reduction step
-constexpr int kCamL2 = 36;       // floats of its records: the 32 slots, background (3), pad
+constexpr int kCamL2 = 40;       // floats of its records: the 32 slots, background (3), depth-mode near / far (2), pad
 struct CamGrad {
     float *part;                 // [V][chunks][kCamSlots], or nullptr: no camera gradient (the unchanged kernels)
     int chunks;                  // ceil(G / 64)
+    float *dpart;                // [V][chunks][2]: dL/dnear, dL/dfar of the depth modes (0 in the native mode)
 };
 inline int cam_chunks(const lsr_dims &d) { return (d.num_gaussians + LSR_WAVE - 1) / LSR_WAVE; }
 struct ViewGradLayout {
-    size_t part, l2, total;
+    size_t part, l2, dpart, total;
 };
 inline ViewGradLayout view_grad_layout(const lsr_dims &d) {
     ViewGradLayout L;
     L.part = 0;
     L.l2 = align_up((size_t)d.num_views * (size_t)cam_chunks(d) * kCamSlots * 4);
-    L.total = L.l2 + align_up((size_t)d.num_views * kCamSplit * kCamL2 * 4);
+    L.dpart = L.l2 + align_up((size_t)d.num_views * kCamSplit * kCamL2 * 4);
+    L.total = L.dpart + align_up((size_t)d.num_views * (size_t)cam_chunks(d) * 2 * 4);
     return L;
 }
 // Sum of v[0..31] over the 64 lanes of a wave (all lanes active): recursive halving, 32 exchanges instead of 6 per value.
@@ -379,7 +384,7 @@ __device__ __forceinline__ float wave_sum32(float (&v)[32]) {
 }
 hipError_t launch_preprocess_backward(const lsr_dims &d, const lsr_inputs &in, const char *geom,
                                       const int32_t *radii, const char *grad,
-                                      const lsr_in_grads &gin, hipStream_t s, const CamGrad &cam = CamGrad{nullptr, 0});
+                                      const lsr_in_grads &gin, hipStream_t s, const CamGrad &cam = CamGrad{nullptr, 0, nullptr});
 hipError_t launch_sh_backward_cam(const lsr_dims &d, const lsr_inputs &in, const char *geom, const char *grad,
                                   const lsr_in_grads &gin, const CamGrad &cam, hipStream_t s);
 bool sh_backward_runs(const lsr_dims &d);

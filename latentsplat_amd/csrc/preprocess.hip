@@ -9,6 +9,7 @@
 #include <algorithm>
 
 #include "lsr_blend.h"
+#include "lsr_depth.h"
 #include "lsr_project.h"
 #include "lsr_tile_scan.h"
 
@@ -140,8 +141,13 @@ k_preprocess(lsr_dims d, lsr_inputs in, float *__restrict__ rec, int RF, char *_
             const float my_radius = pj.radius;
             const int rminx = pj.rminx, rminy = pj.rminy, rmaxx = pj.rmaxx, rmaxy = pj.rmaxy;
 
+            // slot 6, what the compositing kernels blend into the depth image: the view z, or the view's depth mode applied
+            // to it (lsr_depth.h; the mode is uniform: a scalar branch, not taken by tables without a mode).  The bin
+            // record's depth word — sort key, visibility — stays tz.
+            float zpay = tz;
+            if (vw[41] != 0.0f) zpay = depth_mode_payload((int)vw[41], tz, scale, vw[42], vw[43]);
             const float4 rr0 = make_float4(px, py, conic_a, conic_b);
-            const float4 rr1 = make_float4(conic_c, opacity, ok ? tz : 0.0f, 0.0f);   // view z 0 marks a culled record
+            const float4 rr1 = make_float4(conic_c, opacity, ok ? zpay : -1.0f, 0.0f);   // a negative slot 6 marks a culled record (staging only)
             // footprint span for the half-tile render lists (k_scatter / k_sort_tiles); not part of the bit-exact contract
             const uint32_t span = ok ? footprint_cells(px, py, conic_a, conic_b, conic_c, opacity, rminx, rminy) : kSpanNone;
             if (ok) {
@@ -188,8 +194,9 @@ k_preprocess(lsr_dims d, lsr_inputs in, float *__restrict__ rec, int RF, char *_
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const int idx = k * kPreThreads + threadIdx.x;      // float4 index inside the run
-                    // culled Gaussians (view z == 0 in their staged record) are never read: skip them
-                    if (idx < nrec * 4 && s_rec[kRecRow + (idx >> 2)].z > 0.0f) dst[idx] = s_rec[(idx & 3) * kRecRow + (idx >> 2)];
+                    // culled Gaussians (slot 6 < 0 in their staged record; a visible one holds z > 0.2 or a mode's d >= 0) are
+                    // never read: skip them
+                    if (idx < nrec * 4 && s_rec[kRecRow + (idx >> 2)].z >= 0.0f) dst[idx] = s_rec[(idx & 3) * kRecRow + (idx >> 2)];
                 }
                 __syncthreads();
             }

@@ -20,6 +20,7 @@
 // the limit, behind a branch, measured slower).  (The convention is read again at launch: a call must not switch
 // lsr_set_projection_contraction between its forward and its backward.)
 // Spec: SURVEY.md Appendix A.6.
+#include "lsr_depth.h"
 #include "lsr_internal.h"
 #include "lsr_project.h"
 
@@ -151,6 +152,17 @@ k_preprocess_bwd(PreBwdParams pk) {
         // ---- covariance path ----
         const ViewSpace vt = view_space<FMA>(vm, p0, p1, p2);   // the forward's t, bit for bit
         const float tz = vt.t2;
+        // ---- depth modes (view slots 41..43, uniform): the record's gz is dL/dd of the payload d(z), z = tz / s; what joins
+        // dL/dt.z below is gz dd/dz / s.  A scalar branch in front of all the arithmetic of the native path: no product of that
+        // path feeds a sum across it, so tables without a mode get the gradients they always got.
+        float gz_t = r1.z;
+        [[maybe_unused]] float gz_s = 0.0f, gz_n = 0.0f, gz_f = 0.0f;   // CAM: explicit scale term, dL/dnear, dL/dfar
+        if (vw[41] != 0.0f) {
+            const float is = rcp(scale), z = tz * is;
+            const DepthGrad dg = depth_mode_grad((int)vw[41], z, vw[42], vw[43]);
+            gz_t = r1.z * dg.dz * is;
+            if constexpr (CAM) { gz_s = -(r1.z * dg.dz) * z * is; gz_n = r1.z * dg.dn; gz_f = r1.z * dg.df; }
+        }
         const float limx = 1.3f * tanfovx, limy = 1.3f * tanfovy;
         const float itz = rcp(tz), itz2 = itz * itz, itz3 = itz2 * itz;
         const float txtz = vt.t0 / tz, tytz = vt.t1 / tz;   // IEEE, as the forward: these decide the clamp
@@ -220,7 +232,7 @@ k_preprocess_bwd(PreBwdParams pk) {
         const float dL_dty = ym * (-focal_y * itz2) * dJ12;
         float dL_dtz = -focal_x * itz2 * dJ00 - focal_y * itz2 * dJ11 +
                        (2.0f * focal_x * tx) * itz3 * dJ02 + (2.0f * focal_y * ty) * itz3 * dJ12;
-        dL_dtz += r1.z;
+        dL_dtz += gz_t;
         // t = Wr p + trans  =>  dL/dp[cc] = sum_k Wr[k][cc] dt[k] = vm[4cc + k] dt[k]
 #pragma unroll
         for (int cc = 0; cc < 3; ++cc)
@@ -265,7 +277,7 @@ k_preprocess_bwd(PreBwdParams pk) {
             float sc = 0.0f;
 #pragma unroll
             for (int k = 0; k < 6; ++k) sc += gc[k] * ci[k];
-            cg[kCamScaleGeo] = gm[0] * mp[0] + gm[1] * mp[1] + gm[2] * mp[2] + 2.0f * scale * sc;
+            cg[kCamScaleGeo] = gm[0] * mp[0] + gm[1] * mp[1] + gm[2] * mp[2] + 2.0f * scale * sc + gz_s;
 #pragma unroll
             for (int k = kCamScaleGeo + 1; k < kCamSlots; ++k) cg[k] = 0.0f;
             // culled slots and idle lanes contribute nothing (their arithmetic may have produced anything)
@@ -278,6 +290,11 @@ k_preprocess_bwd(PreBwdParams pk) {
             const size_t vg = (size_t)blockIdx.y * V + v;     // the view in the whole call
             if (lane <= kCamScaleGeo && chunk < p.cam.chunks)
                 p.cam.part[(vg * p.cam.chunks + chunk) * kCamSlots + lane] = r;
+            // near / far of the depth modes: a pair of their own per (view, chunk), zeros in the native mode
+            float dn = cv ? gz_n : 0.0f, df = cv ? gz_f : 0.0f;
+#pragma unroll
+            for (int m = LSR_WAVE / 2; m >= 1; m >>= 1) { dn += __shfl_xor(dn, m); df += __shfl_xor(df, m); }
+            if (lane == 0 && chunk < p.cam.chunks) *(float2 *)(p.cam.dpart + (vg * p.cam.chunks + chunk) * 2) = make_float2(dn, df);
         }
         if constexpr (CAM) continue;
         // gradients are w.r.t. the UNSCALED inputs: mean_scaled = s * mean, cov_scaled = s^2 * cov;

@@ -29,6 +29,7 @@
 #include <type_traits>
 
 #include "lsr_blend.h"
+#include "lsr_depth.h"
 #include "lsr_project.h"
 #include "lsr_sh.h"
 #include "lsr_tile_scan.h"
@@ -377,6 +378,9 @@ k_preprocess_sh(ShParams pk, PreShArgs a) {
                 }
             }
             if (!ok) continue;
+            // slot 6 of the record: the view z, or the view's depth mode applied to it (as in k_preprocess; uniform branch)
+            float zpay = pj.tz;
+            if (vw[41] != 0.0f) zpay = depth_mode_payload((int)vw[41], pj.tz, scale, vw[42], vw[43]);
             // ---- payload from the harmonics (the arithmetic of k_sh_fwd, operation for operation) ----
             const ShDir dir = sh_direction(p, v, ShPos{q0, q1, q2});
             float basF[9];
@@ -412,7 +416,7 @@ k_preprocess_sh(ShParams pk, PreShArgs a) {
             }
             float4 *R = (float4 *)(p.rec + o * (size_t)RF);
             R[0] = make_float4(pj.px, pj.py, pj.conic_a, pj.conic_b);
-            R[1] = make_float4(pj.conic_c, opacity, pj.tz, 0.0f);
+            R[1] = make_float4(pj.conic_c, opacity, zpay, 0.0f);
             // payload slots 8.. : rgb (COFF = 3) then the feature channels, zero padded to the record
             auto slot = [&](int ch) -> float { return ch < COFF ? col[ch < 3 ? ch : 0] : (hasF ? feat(ch - COFF) : 0.0f); };
 #pragma unroll 1
@@ -855,7 +859,7 @@ static ShParams make_params(const lsr_dims &d, const lsr_inputs &in, const GeomL
     p.offF = (LSR_WAVE * p.ks[0] + 3) & ~3;
     for (int g = 0; g < 2; ++g) p.mdiv[g] = mdiv_of(p.ks[g]);
     p.mdivK = mdiv_of(d.sh_coeffs); p.mdivKf = mdiv_of(d.feat_sh_coeffs);
-    p.cam = CamGrad{nullptr, 0};
+    p.cam = CamGrad{nullptr, 0, nullptr};
     return p;
 }
 
@@ -1004,7 +1008,7 @@ static hipError_t sh_backward(const lsr_dims &d, const lsr_inputs &in, const cha
 
 hipError_t launch_sh_backward(const lsr_dims &d, const lsr_inputs &in, const char *geom, const char *grad,
                               const lsr_in_grads &gin, hipStream_t s) {
-    return sh_backward<false>(d, in, geom, grad, gin, CamGrad{nullptr, 0}, s);
+    return sh_backward<false>(d, in, geom, grad, gin, CamGrad{nullptr, 0, nullptr}, s);
 }
 
 hipError_t launch_sh_backward_cam(const lsr_dims &d, const lsr_inputs &in, const char *geom, const char *grad,

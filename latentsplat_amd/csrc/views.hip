@@ -41,7 +41,7 @@ __device__ static void inv4(const double m[16], double inv[16]) {
 
 __global__ void k_build_views(int V, const float *__restrict__ extrinsics, const float *__restrict__ intrinsics,
                               const float *__restrict__ near, const float *__restrict__ far,
-                              const float *__restrict__ bg, int bg_stride, int scale_invariant,
+                              const float *__restrict__ bg, int bg_stride, int scale_invariant, int depth_mode,
                               float *__restrict__ out) {
     const int v = blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= V) return;
@@ -82,14 +82,16 @@ __global__ void k_build_views(int V, const float *__restrict__ extrinsics, const
     o[32] = (float)E[3]; o[33] = (float)E[7]; o[34] = (float)E[11];
     o[35] = (float)tan_x; o[36] = (float)tan_y;
     o[37] = bg[(size_t)v * bg_stride]; o[38] = bg[(size_t)v * bg_stride + 1]; o[39] = bg[(size_t)v * bg_stride + 2];
-    o[40] = scale_f; o[41] = o[42] = o[43] = 0.0f;
+    // depth mode (lsr_build_views_depth) and the caller's near / far, which only the modes read
+    o[40] = scale_f; o[41] = (float)depth_mode;
+    o[42] = depth_mode != LSR_DEPTH_NATIVE ? near[v] : 0.0f; o[43] = depth_mode != LSR_DEPTH_NATIVE ? far[v] : 0.0f;
 }
 
 hipError_t launch_build_views(int V, const float *extrinsics, const float *intrinsics, const float *near,
                               const float *far, const float *bg, int bg_stride, int scale_invariant,
-                              float *out, hipStream_t s) {
+                              float *out, hipStream_t s, int depth_mode) {
     hipLaunchKernelGGL(k_build_views, dim3((V + 63) / 64), dim3(64), 0, s, V, extrinsics, intrinsics, near, far,
-                       bg, bg_stride, scale_invariant, out);
+                       bg, bg_stride, scale_invariant, depth_mode, out);
     return hipGetLastError();
 }
 
@@ -125,11 +127,11 @@ hipError_t launch_pack_view(const float *viewmatrix, const float *projmatrix, co
 // pixels) are combined in a fixed order and stored as one second-level record.
 constexpr int kCamThreads = 256;
 __global__ void __launch_bounds__(kCamThreads)
-k_view_grad_partial(const float *__restrict__ part, int chunks, int sh, const float *__restrict__ final_T,
-                    const float *__restrict__ g_color, int HW, float *__restrict__ l2) {
+k_view_grad_partial(const float *__restrict__ part, const float *__restrict__ dpart, int chunks, int sh,
+                    const float *__restrict__ final_T, const float *__restrict__ g_color, int HW, float *__restrict__ l2) {
     const int s = blockIdx.x, v = blockIdx.y, tid = threadIdx.x;
     __shared__ float s_row[kCamThreads / kCamSlots][kCamSlots];
-    __shared__ float s_bg[kCamThreads / LSR_WAVE][3];
+    __shared__ float s_bg[kCamThreads / LSR_WAVE][5];
     const int j = tid & (kCamSlots - 1), q = tid / kCamSlots;
     // slots a kernel of this call wrote: the geometry's always, the SH direction's when the SH backward ran
     const bool used = j <= kCamScaleGeo || (sh && j < kCamScaleSh + 1);
@@ -140,7 +142,13 @@ k_view_grad_partial(const float *__restrict__ part, int chunks, int sh, const fl
         for (int c = c0 + q; c < c1; c += kCamThreads / kCamSlots) a += part[((size_t)v * chunks + c) * kCamSlots + j];
     }
     s_row[q][j] = a;
-    float b[3] = {0.0f, 0.0f, 0.0f};
+    float b[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};   // background (3), then near / far of the depth modes
+    if (dpart) {   // (nullptr: no Gaussians, nothing wrote the pairs)
+        for (int c = c0 + tid; c < c1; c += kCamThreads) {
+            const float2 t = *(const float2 *)(dpart + ((size_t)v * chunks + c) * 2);
+            b[3] += t.x; b[4] += t.y;
+        }
+    }
     if (g_color) {
         const int pper = (HW + kCamSplit - 1) / kCamSplit, p0 = s * pper, p1 = min(HW, p0 + pper);
 #pragma unroll 4
@@ -153,16 +161,16 @@ k_view_grad_partial(const float *__restrict__ part, int chunks, int sh, const fl
 #pragma unroll
     for (int m = LSR_WAVE / 2; m >= 1; m >>= 1)
 #pragma unroll
-        for (int c = 0; c < 3; ++c) b[c] += __shfl_xor(b[c], m);
+        for (int c = 0; c < 5; ++c) b[c] += __shfl_xor(b[c], m);
     if ((tid & (LSR_WAVE - 1)) == 0)
-        for (int c = 0; c < 3; ++c) s_bg[tid / LSR_WAVE][c] = b[c];
+        for (int c = 0; c < 5; ++c) s_bg[tid / LSR_WAVE][c] = b[c];
     __syncthreads();
     float *o = l2 + ((size_t)v * kCamSplit + s) * kCamL2;
     if (tid < kCamSlots) {
         float t = 0.0f;
         for (int r = 0; r < kCamThreads / kCamSlots; ++r) t += s_row[r][tid];
         o[tid] = t;
-    } else if (tid < kCamSlots + 3) {
+    } else if (tid < kCamSlots + 5) {
         float t = 0.0f;
         for (int w = 0; w < kCamThreads / LSR_WAVE; ++w) t += s_bg[w][tid - kCamSlots];
         o[tid] = t;
@@ -182,6 +190,7 @@ k_view_grad_final(const float *__restrict__ l2, float *__restrict__ grad_views) 
     else if (t == 36) a = kCamTanY;
     else if (t < 40) a = kCamSlots + (t - 37);
     else if (t == 40) { a = kCamScaleGeo; b = kCamScaleSh; }
+    else if (t >= 42) a = kCamSlots + 3 + (t - 42);     // near / far of the depth modes
     float x = 0.0f, y = 0.0f;
     for (int s = 0; s < kCamSplit; ++s) {
         const float *r = l2 + ((size_t)v * kCamSplit + s) * kCamL2;
@@ -197,7 +206,8 @@ hipError_t launch_view_grad_reduce(const lsr_dims &d, char *ws, bool sh, const f
     float *l2 = (float *)(ws + L.l2);
     prof_begin(kStViewGrad, s);
     hipLaunchKernelGGL(k_view_grad_partial, dim3(kCamSplit, d.num_views), dim3(kCamThreads), 0, s, (const float *)(ws + L.part),
-                       cam_chunks(d), sh ? 1 : 0, final_T, g_color, d.height * d.width, l2);
+                       d.num_gaussians > 0 ? (const float *)(ws + L.dpart) : nullptr, cam_chunks(d), sh ? 1 : 0, final_T, g_color,
+                       d.height * d.width, l2);
     hipLaunchKernelGGL(k_view_grad_final, dim3(d.num_views), dim3(LSR_WAVE), 0, s, (const float *)l2, grad_views);
     prof_end(kStViewGrad, s);
     return hipGetLastError();

@@ -2,7 +2,8 @@
 from .cuda_splatting import (DepthRenderingMode, RenderOutput, get_projection_matrix, render_cuda,
                              render_cuda_orthographic, render_depth_cuda, render_scenes)
 from .decoder import Decoder, DecoderOutput
-from .decoder_splatting_cuda import DecoderSplattingCUDA, DecoderSplattingCUDACfg
+from .decoder_splatting_cuda import (DecoderSplattingCUDA, DecoderSplattingCUDACfg, get_fused_depth_modes,
+                                     set_fused_depth_modes)
 from .types import DiagonalGaussianDistribution, Gaussians, VariationalGaussians
 
 DECODERS = {"splatting_cuda": DecoderSplattingCUDA}

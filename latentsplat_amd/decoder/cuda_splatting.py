@@ -26,7 +26,8 @@ from typing import Literal, Optional
 import torch
 from torch import Tensor
 
-from ..rasterizer import build_view_table, fused_feature_sh_supported, make_view_table, rasterize_views
+from ..rasterizer import (build_view_table, depth_mode_payload, fused_feature_sh_supported, make_view_table,  # noqa: F401
+                          rasterize_views)
 from .geometry import depth_to_relative_disparity, eval_sh, get_fov, homogenize_points
 
 
@@ -107,14 +108,20 @@ def _squeeze_shared(t: Optional[Tensor]) -> Optional[Tensor]:
 
 
 def _view_table(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor, background: Tensor,
-                scale_invariant: bool) -> Tensor:
-    """(B,44) camera table + scene scale.  On the MI355X: one kernel; for host tensors (the
-    not-gpu tests, which substitute the rasterizer) the same math in PyTorch."""
+                scale_invariant: bool, depth_mode=None) -> Tensor:
+    """(B,44) camera table + scene scale (+ depth mode and the caller's near / far).  On the MI355X: one kernel; for
+    host tensors (the not-gpu tests, which substitute the rasterizer) the same math in PyTorch."""
+    if depth_mode is None:      # today's call exactly
+        if extrinsics.is_cuda:
+            return build_view_table(extrinsics, intrinsics, near, far, background, scale_invariant)
+        cams, scale = _scaled_cameras(extrinsics, intrinsics, near, far, scale_invariant)
+        return make_view_table(cams.view_matrix, cams.full_projection, cams.campos, cams.tan_fov_x,
+                               cams.tan_fov_y, background, scale)
     if extrinsics.is_cuda:
-        return build_view_table(extrinsics, intrinsics, near, far, background, scale_invariant)
+        return build_view_table(extrinsics, intrinsics, near, far, background, scale_invariant, depth_mode=depth_mode)
     cams, scale = _scaled_cameras(extrinsics, intrinsics, near, far, scale_invariant)
     return make_view_table(cams.view_matrix, cams.full_projection, cams.campos, cams.tan_fov_x,
-                           cams.tan_fov_y, background, scale)
+                           cams.tan_fov_y, background, scale, depth_mode=depth_mode, near=near, far=far)
 
 
 def _render_views(views: Tensor, image_shape, means: Tensor, covariances: Tensor, opacities: Tensor,
@@ -182,10 +189,14 @@ def render_cuda(
     gaussian_feature_sh_coefficients: Optional[Tensor] = None,  # (batch,gaussian,channels,d_feature_sh)
     scale_invariant: bool = True,
     use_sh: bool = True,
+    depth_mode: Optional[str] = None,
 ) -> RenderOutput:
+    """``depth_mode`` (None: today's call exactly): "depth", "disparity", "relative_disparity" or "log" make
+    ``RenderOutput.depth`` what ``render_depth_cuda(..., mode=depth_mode)`` renders with a second pass — here from the
+    same pass (the view table carries the mode; :func:`latentsplat_amd.rasterizer.depth_mode_payload`)."""
     assert gaussian_color_sh_coefficients is not None or gaussian_feature_sh_coefficients is not None
     assert use_sh or gaussian_color_sh_coefficients.shape[-1] == 1
-    views = _view_table(extrinsics, intrinsics, near, far, background_color, scale_invariant)
+    views = _view_table(extrinsics, intrinsics, near, far, background_color, scale_invariant, depth_mode)
     return _render_views(views, image_shape, gaussian_means, gaussian_covariances, gaussian_opacities,
                          gaussian_color_sh_coefficients, gaussian_feature_sh_coefficients, use_sh)
 
@@ -204,16 +215,17 @@ def render_scenes(
     gaussian_feature_sh_coefficients: Optional[Tensor] = None,  # (b,g,c,d)
     scale_invariant: bool = True,
     use_sh: bool = True,
+    depth_mode: Optional[str] = None,
 ) -> RenderOutput:
     """Scene-major entry point: identical results to ``render_cuda`` on the v-fold replicated
     inputs, but colour SH / opacities of a scene are read once for all of its views.
-    Returns tensors flattened over (b v) like ``render_cuda``."""
+    Returns tensors flattened over (b v) like ``render_cuda``.  ``depth_mode``: as in ``render_cuda``."""
     assert gaussian_color_sh_coefficients is not None or gaussian_feature_sh_coefficients is not None
     b, v = extrinsics.shape[:2]
     outs = []
     # one camera-table launch for all b*v views
     views = _view_table(extrinsics.flatten(0, 1), intrinsics.flatten(0, 1), near.flatten(0, 1), far.flatten(0, 1),
-                        background_color, scale_invariant)
+                        background_color, scale_invariant, depth_mode)
     fsh_all = gaussian_feature_sh_coefficients
     if b == 1 or not use_sh or fsh_all is None or fused_feature_sh_supported(fsh_all):
         # ONE call for all b*v views: the b scenes are view groups of v views each (inputs keep their

@@ -8,6 +8,7 @@ tensors to ``render_scenes`` and the kernels read each scene once for all of its
 """
 from __future__ import annotations
 
+import os
 from dataclasses import dataclass
 from typing import Literal, Optional
 
@@ -17,6 +18,24 @@ from torch import Tensor
 from .cuda_splatting import DepthRenderingMode, RenderOutput, render_depth_scenes, render_scenes
 from .decoder import Decoder, DecoderOutput
 from .types import DiagonalGaussianDistribution, Gaussians
+
+
+# LSR_FUSED_DEPTH=1 / set_fused_depth_modes(True): ``forward(depth_mode=...)`` takes its depth image from the ONE render
+# it makes anyway (the view table carries the mode, the projection kernels write the mode's value into the record)
+# instead of a second, complete rasterization per scene (``render_depth``).  Off by default: the reference makes that
+# second call, and tests/test_golden_cpu.py pins the number and content of the rasterizer calls to the reference's.
+_FUSED_DEPTH = os.environ.get("LSR_FUSED_DEPTH", "0") == "1"
+
+
+def set_fused_depth_modes(on: bool) -> None:
+    """Whether subsequent ``DecoderSplattingCUDA.forward`` calls render a depth mode in the pass that renders colour and
+    features (True) or through ``render_depth`` like the reference (False, the default)."""
+    global _FUSED_DEPTH
+    _FUSED_DEPTH = bool(on)
+
+
+def get_fused_depth_modes() -> bool:
+    return _FUSED_DEPTH
 
 
 @dataclass
@@ -58,13 +77,16 @@ class DecoderSplattingCUDA(Decoder[DecoderSplattingCUDACfg]):
                 depth_mode: Optional[DepthRenderingMode] = None, return_colors: bool = True,
                 return_features: bool = True) -> DecoderOutput:
         b, v = extrinsics.shape[:2]
+        # None and "depth" keep the rasterizer's own depth output, as the reference does (:89)
+        moded = depth_mode is not None and depth_mode != "depth"
+        fused = {"depth_mode": depth_mode} if (moded and _FUSED_DEPTH) else {}
         rendered = render_scenes(
             extrinsics, intrinsics, near, far, image_shape, self.background_color,
             gaussians.means, gaussians.covariances, gaussians.opacities,
             gaussians.color_harmonics if return_colors else None,
-            gaussians.feature_harmonics if return_features else None)
+            gaussians.feature_harmonics if return_features else None, **fused)
         out = self.render_to_decoder_output(rendered, b, v)
-        if depth_mode is not None and depth_mode != "depth":
+        if moded and not fused:
             out.depth = self.render_depth(gaussians, extrinsics, intrinsics, near, far, image_shape, depth_mode)
         return out
 

@@ -38,15 +38,70 @@ class GaussianRasterizationSettings(NamedTuple):
     debug: bool
 
 
+# Depth modes of the view table (slot 41; include/lsr_rasterizer.h LSR_DEPTH_*).  The names are the reference's
+# ``DepthRenderingMode`` (cuda_splatting.py:295) plus "native": the depth output as it is without a mode.
+DEPTH_MODES = {"native": _lib.DEPTH_NATIVE, "depth": _lib.DEPTH_DEPTH, "disparity": _lib.DEPTH_DISPARITY,
+               "relative_disparity": _lib.DEPTH_RELATIVE_DISPARITY, "log": _lib.DEPTH_LOG}
+SH_C0 = 0.28209479177387814
+
+
+def depth_mode_id(mode) -> int:
+    """``None`` / a name of :data:`DEPTH_MODES` / an ``LSR_DEPTH_*`` number -> the number."""
+    if mode is None:
+        return _lib.DEPTH_NATIVE
+    if isinstance(mode, str):
+        if mode not in DEPTH_MODES:
+            raise LsrError(f"unknown depth mode {mode!r}; expected one of {sorted(DEPTH_MODES)}")
+        return DEPTH_MODES[mode]
+    if int(mode) not in DEPTH_MODES.values():
+        raise LsrError(f"unknown depth mode {mode!r}")
+    return int(mode)
+
+
+def depth_mode_value(z: Tensor, near, far, mode) -> Tensor:
+    """The per-Gaussian value ``u`` a depth mode computes from the camera-space depth ``z`` — the reference's fake colour
+    (cuda_splatting.py:314-323).  See :func:`depth_mode_payload`."""
+    m = depth_mode_id(mode)
+    if m in (_lib.DEPTH_NATIVE, _lib.DEPTH_DEPTH):
+        return z
+    if m == _lib.DEPTH_DISPARITY:
+        return 1 / z
+    if m == _lib.DEPTH_RELATIVE_DISPARITY:
+        eps = 1e-10
+        d_near, d_far = 1 / (near + eps), 1 / (far + eps)
+        return 1 - (1 / (z + eps) - d_far) / (d_near - d_far + eps)
+    t = lambda x: torch.as_tensor(x, dtype=z.dtype, device=z.device)
+    return torch.maximum(torch.minimum(z, t(near)), t(far)).log()
+
+
+def depth_mode_payload(z: Tensor, near, far, mode) -> Tensor:
+    """What a (view, Gaussian) at camera-space depth ``z`` (UNSCALED scene) contributes to the depth image under a depth
+    mode: ``d = max(0, C0 u + 0.5)`` — the degree-0 SH colour the reference's ``render_depth_cuda`` renders its value ``u``
+    through (cuda_splatting.py:298-340) — with ``u = z`` ("depth"), ``1 / z`` ("disparity"),
+    ``depth_to_relative_disparity(z, near, far)`` ("relative_disparity") or ``log(max(min(z, near), far))`` ("log":
+    the reference's expression as it stands, i.e. ``log(far)`` whenever near < far).  "native" / ``None`` returns ``z``.
+    Plain PyTorch in the dtype of ``z``, differentiable in z / near / far: the statement the kernels are tested against.
+    ``near`` / ``far`` broadcast against ``z`` (e.g. ``near[:, None]`` for ``z`` of shape (V, G))."""
+    if depth_mode_id(mode) == _lib.DEPTH_NATIVE:
+        return z
+    return torch.clamp_min(SH_C0 * depth_mode_value(z, near, far, mode) + 0.5, 0.0)
+
+
 def make_view_table(viewmatrix: Tensor, projmatrix: Tensor, campos: Tensor, tanfovx, tanfovy,
-                    bg: Tensor, scene_scale=None, dtype=torch.float32) -> Tensor:
+                    bg: Tensor, scene_scale=None, dtype=torch.float32, depth_mode=None, near=None, far=None) -> Tensor:
     """(V,44) device table: viewmatrix(16) projmatrix(16) campos(3) tanfovx tanfovy bg(3)
-    scene_scale(1) reserved(3).  All arguments batched over V; tanfov / scene_scale may be python
+    scene_scale(1) depth_mode(1) near(1) far(1).  All arguments batched over V; tanfov / scene_scale may be python
     floats or tensors (no host sync).  ``scene_scale`` (default 1) is applied to the Gaussians'
     means (and squared to their covariances) inside the kernel.  (``dtype``: float32, what the kernels
-    read; float64 for checking the table's gradient.)"""
+    read; float64 for checking the table's gradient.)
+    ``depth_mode`` (a name of :data:`DEPTH_MODES`, an ``LSR_DEPTH_*`` number or None) selects what the depth output
+    blends (:func:`depth_mode_payload`); a mode other than native needs the caller's UNSCALED ``near`` / ``far`` (V,),
+    which go to slots 42 / 43 (differentiable).  Without a mode the three slots are 0.0."""
     V = viewmatrix.shape[0]
     dev, dt = viewmatrix.device, dtype
+    mode = depth_mode_id(depth_mode)
+    if mode != _lib.DEPTH_NATIVE and (near is None or far is None):
+        raise LsrError("a depth mode needs the caller's near and far")
 
     def col(t):
         if not torch.is_tensor(t):
@@ -56,24 +111,27 @@ def make_view_table(viewmatrix: Tensor, projmatrix: Tensor, campos: Tensor, tanf
     return torch.cat([viewmatrix.reshape(V, 16).to(dt), projmatrix.reshape(V, 16).to(dt),
                       campos.reshape(V, 3).to(dt), col(tanfovx), col(tanfovy),
                       bg.reshape(-1, 3).to(dt).expand(V, 3), col(1.0 if scene_scale is None else scene_scale),
-                      torch.zeros((V, 3), dtype=dt, device=dev)], dim=1).contiguous()
+                      col(float(mode)), col(near if mode else 0.0), col(far if mode else 0.0)], dim=1).contiguous()
 
 
 def build_view_table(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor, background: Tensor,
-                     scale_invariant: bool = True) -> Tensor:
+                     scale_invariant: bool = True, depth_mode=None) -> Tensor:
     """(V,44) camera table computed on the device by one kernel (``lsr_build_views``): what the
     reference derives per call with get_fov / get_projection_matrix / inverse / matmul
     (cuda_splatting.py:75-82,111-118).  ``background`` is ``(3,)`` or ``(V,3)``.
     Differentiable: when an input requires grad (and grad mode is on) the values are still this kernel's, and the
     gradient of the table flows back through the same math in PyTorch (``_scaled_cameras`` + :func:`make_view_table`)
-    into extrinsics, intrinsics, near, far and background."""
-    table = _build_view_table(extrinsics, intrinsics, near, far, background, scale_invariant)
+    into extrinsics, intrinsics, near, far and background.
+    ``depth_mode``: as in :func:`make_view_table` (``lsr_build_views_depth``: still one launch); near / far then also
+    reach the table through slots 42 / 43."""
+    table = _build_view_table(extrinsics, intrinsics, near, far, background, scale_invariant, depth_mode_id(depth_mode))
     if torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad
                                        for t in (extrinsics, intrinsics, near, far, background)):
         from .decoder.cuda_splatting import _scaled_cameras
         cams, scale = _scaled_cameras(extrinsics, intrinsics, near, far, scale_invariant)
         torch_table = make_view_table(cams.view_matrix, cams.full_projection, cams.campos, cams.tan_fov_x,
-                                      cams.tan_fov_y, background.to(table.device), scale)
+                                      cams.tan_fov_y, background.to(table.device), scale, depth_mode=depth_mode,
+                                      near=near, far=far)
         return _straight_through(table, torch_table)
     return table
 
@@ -95,7 +153,7 @@ def _straight_through(values: Tensor, carrier: Tensor) -> Tensor:
 
 
 def _build_view_table(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor, background: Tensor,
-                      scale_invariant: bool) -> Tensor:
+                      scale_invariant: bool, depth_mode: int = _lib.DEPTH_NATIVE) -> Tensor:
     lib = _lib.load()
     dev = extrinsics.device
     if dev.type != "cuda":
@@ -106,9 +164,14 @@ def _build_view_table(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far:
     out = torch.empty((V, _lib.VIEW_FLOATS), dtype=torch.float32, device=dev)
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     with torch.cuda.device(dev):
-        _lib.check(lib.lsr_build_views(V, _ptr(ext), _ptr(intr), _ptr(nr), _ptr(fr), _ptr(bg),
-                                       0 if bg.dim() == 1 else 3, 1 if scale_invariant else 0, _ptr(out), stream),
-                   "lsr_build_views")
+        if depth_mode == _lib.DEPTH_NATIVE:
+            _lib.check(lib.lsr_build_views(V, _ptr(ext), _ptr(intr), _ptr(nr), _ptr(fr), _ptr(bg),
+                                           0 if bg.dim() == 1 else 3, 1 if scale_invariant else 0, _ptr(out), stream),
+                       "lsr_build_views")
+        else:
+            _lib.check(lib.lsr_build_views_depth(V, _ptr(ext), _ptr(intr), _ptr(nr), _ptr(fr), _ptr(bg),
+                                                 0 if bg.dim() == 1 else 3, 1 if scale_invariant else 0, depth_mode,
+                                                 _ptr(out), stream), "lsr_build_views_depth")
     return out
 
 
@@ -501,7 +564,9 @@ def rasterize_views(views: Tensor, image_height: int, image_width: int, sh_degre
     Returns ``(color (V,3,H,W)|None, feature (V,C,H,W)|None, mask (V,H,W), depth (V,H,W), radii (V,G))``.
     ``means2D`` (optional, ``(V,G,3)``) only exists to receive the NDC-space mean gradient.
     A ``views`` table that requires grad receives dL/d(view record) (``lsr_backward_views``; slot by slot in
-    include/lsr_rasterizer.h): viewmatrix, projmatrix, campos, tan(fov), background and scene scale.
+    include/lsr_rasterizer.h): viewmatrix, projmatrix, campos, tan(fov), background, scene scale and the depth modes'
+    near / far.  The table also carries the depth mode (:func:`make_view_table`): ``depth`` is then that mode's image,
+    from the same single pass.
 
     Scene-level (fused) inputs, all optional: ``cov3D_precomp`` may be full ``(...,3,3)`` matrices;
     ``feature_sh (..., C, Kf)`` (instead of ``features``) makes the kernel evaluate the latent
