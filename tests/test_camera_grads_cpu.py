@@ -6,6 +6,8 @@ import ctypes as C
 import os
 import re
 
+import numpy as np
+import pytest
 import torch
 
 from latentsplat_amd import _lib
@@ -13,6 +15,7 @@ from latentsplat_amd._lib import Dims
 from latentsplat_amd.decoder import cuda_splatting as cs
 from latentsplat_amd.rasterizer import _straight_through, make_view_table
 from latentsplat_amd.synthetic import make_scene
+from tests import camera_grad_cases as cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -103,3 +106,34 @@ def test_host_view_table_gradient_reaches_every_camera_input():
     (views * g).sum().backward()
     for t in (ext, intr, near, far, bg):
         assert t.grad is not None and torch.isfinite(t.grad).all() and t.grad.abs().sum() > 0
+
+
+# what each A case of tests/camera_grad_cases.py is about: (parts of launch_preprocess_backward, nv of k_sh_bwd's view chunks)
+VIEW_PARALLEL = {"A1": (4, [4]), "A2": (4, [4, 1]), "A2-contraction": (4, [4, 1]), "A2-depth": (4, [4, 1]), "A3": (4, [4, 3]),
+                 "A4": (4, [4, 1]), "A4-depth": (4, [4, 1]), "A5": (4, [1] * 5), "A6": (4, [4] * 4)}
+
+
+@pytest.mark.parametrize("name", list(cases.CASES))
+def test_gpu_cases_are_fragile_free_and_reach_their_structure(name):
+    """The cases test_camera_grads_gpu.py compares with the float64 oracle: no fragile evaluation in any view (the seeds),
+    and the kernel instance / reduction loop each is about, restated from the constants in the sources."""
+    c = cases.case(name)
+    fw = c.forwards()
+    assert cases.fragile_counts(None, c.H, c.W, None, None, None, None, forwards=fw) == [0] * c.V
+    if name in VIEW_PARALLEL:
+        assert cases.view_parallel_shape(c) == VIEW_PARALLEL[name]
+        return
+    radii64, masks = cases.oracle64_forward(c)
+    radii32 = torch.from_numpy(np.stack([f["radii"] for f in fw]))
+    for radii in (radii64, radii32):
+        cases.assert_reduction_structure(name, c, radii)
+    if name == "B4":
+        cases.assert_background_mask(masks[0])
+
+
+def test_a6_needs_the_big_lds_instance():
+    """sh.hip sh_backward: (64 * 75 + 64 * 117 + 4 * 64 * 17) * 4 bytes with 13 latent channels; 12 stay within 64 KB"""
+    assert cases.sh_backward_lds_bytes(4, cases.A6_CHANNELS, 2) == 66560 > 65536
+    assert cases.sh_backward_lds_bytes(4, cases.A6_CHANNELS - 1, 2) <= 65536
+    c = cases.case("A6")
+    assert c.kw["feature_sh"].shape[1:] == (cases.A6_CHANNELS, 9) and c.kw["sh_degree"] == 4 and c.V == 16

@@ -3,20 +3,26 @@ PyTorch oracle (oracle/torch_oracle.py), the chain into extrinsics / intrinsics 
 public surfaces, bitwise non-interference with the existing outputs and gradients, reproducibility, and pose recovery."""
 from __future__ import annotations
 
+import ctypes
 import math
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
+from latentsplat_amd import _lib
 from latentsplat_amd import rasterizer as R
 from latentsplat_amd.decoder import cuda_splatting as cs
-from latentsplat_amd.decoder.geometry import eval_sh, get_fov
+from latentsplat_amd.decoder.geometry import eval_sh
 from latentsplat_amd.synthetic import make_scene
 from oracle import oracle as orc
 from oracle import torch_oracle as TO
+from tests import camera_grad_cases as cases
+from tests.camera_grad_cases import (cams32 as _cams32, chain64 as _chain64, fragile_counts, oracle_forwards,  # noqa: F401
+                                     sh_payload as _sh_payload, view_inputs as _view_inputs, with_depth_channel)
 
 pytestmark = pytest.mark.gpu
 F64 = torch.float64
@@ -26,23 +32,6 @@ BLOCKS = dict(vm=slice(0, 16), pm=slice(16, 32), campos=slice(32, 35), tanfov=sl
 
 # scene seeds, chosen so that the C oracle's forward of every view reports no fragile evaluation (fragile_counts)
 SEEDS = dict(colour=11, precomp=6, latent=21, groups=40, edge=0, depth=3, ortho=7, decoder=50)
-
-
-def _chain64(ext, intr, near, far, scale_invariant=True):
-    """Reference-style camera math in float64 PyTorch: 1/near scaling, fov, projection, inverse (cuda_splatting.py)."""
-    scale = 1 / near if scale_invariant else torch.ones_like(near)
-    e = torch.cat([torch.cat([ext[:, :3, :3], ext[:, :3, 3:] * scale[:, None, None]], -1), ext[:, 3:, :]], -2)
-    nr, fr = near * scale, far * scale
-    fov = get_fov(intr)
-    tx, ty = (0.5 * fov[:, 0]).tan(), (0.5 * fov[:, 1]).tan()
-    P = torch.zeros((ext.shape[0], 4, 4), dtype=ext.dtype)
-    P[:, 0, 0] = 1 / tx
-    P[:, 1, 1] = 1 / ty
-    P[:, 2, 2] = fr / (fr - nr)
-    P[:, 2, 3] = -(fr * nr) / (fr - nr)
-    P[:, 3, 2] = 1
-    vt = torch.linalg.inv(e).transpose(1, 2)
-    return vt, vt @ P.transpose(1, 2), e[:, :3, 3], tx, ty, scale
 
 
 def _oracle_view(v, vm, pm, cp, tx, ty, bg, s, H, W, means, cov6, opac, payload):
@@ -76,44 +65,19 @@ def _scene(G, size, V, seed, **kw):
     return sc
 
 
-def _cams32(sc, bg=(0.2, 0.5, 0.7)):
-    vt, full, cp, tx, ty, s = _chain64(sc.extrinsics.to(F64), sc.intrinsics.to(F64), sc.near.to(F64), sc.far.to(F64))
-    bgt = torch.tensor(bg, dtype=F64)
-    return R.make_view_table(vt, full, cp, tx, ty, bgt, s)      # float32 (V, 44)
+def _poison_view_grad_workspace(V, G, dev):
+    """Best effort against stale memory: the reduction workspace is torch.empty, so a partial record that no kernel wrote
+    is noticed only if the block is not zero.  A block of that size filled with 0xFF (NaN as float) and freed again is what the
+    caching allocator most likely hands to the op's backward."""
+    d = _lib.Dims(num_views=V, num_gaussians=G, height=32, width=32, feat_channels=0, color_mode=1, sh_degree=0, sh_coeffs=1,
+                  cov_elems=6)
+    n = R._lib.load().lsr_view_grad_workspace_bytes(ctypes.byref(d))
+    assert n > 0
+    torch.full((n,), 0xFF, dtype=torch.uint8, device=dev)
 
 
-def _view_inputs(views32, v, means, cov, opac, scenes):
-    V = views32.shape[0]
-    sidx = v if scenes is None else v // (V // scenes)
-    m, c, o = (means, cov, opac) if scenes is None else (means[sidx], cov[sidx], opac[sidx])
-    c6 = c if c.shape[-1] == 6 else torch.stack([c[:, 0, 0], c[:, 0, 1], c[:, 0, 2], c[:, 1, 1], c[:, 1, 2], c[:, 2, 2]], -1)
-    return sidx, m.double(), c6.double(), o.double()
-
-
-def fragile_counts(views32, H, W, means, cov, opac, payload, scenes=None):
-    """Per view: evaluations the C oracle's forward flags as fragile (a decision within rounding of a threshold)."""
-    out = []
-    for v in range(views32.shape[0]):
-        sidx, m, c6, o = _view_inputs(views32, v, means, cov, opac, scenes)
-        rec = views32[v].double()
-        s = rec[40]
-        with torch.no_grad():
-            pl = payload(m * s, rec[32:35], sidx)
-        deg = pl.pop("sh_degree", 0)
-        n = lambda k: None if pl.get(k) is None else pl[k].float().contiguous().numpy()
-        view = orc.View(H, W, float(views32[v, 35]), float(views32[v, 36]), views32[v, 37:40].numpy(),
-                        views32[v, 0:16].reshape(4, 4).numpy(), views32[v, 16:32].reshape(4, 4).numpy(),
-                        views32[v, 32:35].numpy(), deg)
-        f = orc.forward(view, (m * s).float().numpy(), (c6 * s * s).float().numpy(), o.float().numpy(),
-                        n("shs"), n("colors_precomp"), n("features"))
-        out.append(len(f["fragile"]) + (1 << 20 if f["fragile_overflow"] else 0))
-    return out
-
-
-def _kernel_vs_oracle(views32, H, W, means, cov, opac, kw, payload, C, scenes=None, contraction=False, tol=1e-3):
-    """dL/dviews of the HIP op vs autograd through the float64 oracle, per view and per block, on a scene whose C-oracle
-    forward has no fragile evaluations (a gradient there may flip between two equally right answers)."""
-    assert fragile_counts(views32, H, W, means, cov, opac, payload, scenes) == [0] * views32.shape[0]
+def _op_grad(views32, H, W, means, cov, opac, kw, C, contraction=False, poison=False):
+    """(views.grad, radii) of the HIP op under the loss of ``_weights(V, H, W, C)``, on the host"""
     dev = torch.device("cuda:0")
     V = views32.shape[0]
     w = _weights(V, H, W, C)
@@ -123,26 +87,59 @@ def _kernel_vs_oracle(views32, H, W, means, cov, opac, kw, payload, C, scenes=No
         views = views32.to(dev).requires_grad_(True)
         dk = {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in kw.items()}
         deg = dk.pop("sh_degree", 0)
-        col, feat, mask, depth, _ = R.rasterize_views(views, H, W, deg, means.to(dev), cov.to(dev), opac.to(dev), **dk)
+        col, feat, mask, depth, radii = R.rasterize_views(views, H, W, deg, means.to(dev), cov.to(dev), opac.to(dev), **dk)
         loss = 0.0
         for v in range(V):
             loss = loss + _loss(None if col is None else col[v].double(), None if feat is None else feat[v].double(),
                                 mask[v][None].double(), depth[v][None].double(), {k: t.to(dev) for k, t in w[v].items()})
+        if poison:
+            _poison_view_grad_workspace(V, means.shape[-2], dev)
         loss.backward()
     finally:
         lib.lsr_set_projection_contraction(0)
-    got = views.grad.cpu().double()
-    worst = 0.0
+    return views.grad.cpu(), radii.cpu()
+
+
+def _kernel_vs_oracle(views32, H, W, means, cov, opac, kw, payload, C, scenes=None, contraction=False, tol=1e-3, placed=None,
+                      info=None):
+    """dL/dviews of the HIP op vs autograd through the float64 oracle, per view and per block, on a scene whose C-oracle
+    forward has no fragile evaluations (a gradient there may flip between two equally right answers).  A table with a
+    depth mode (slot 41): the oracle blends the mode's payload d as one more feature channel, and near / far (slots 42, 43)
+    are two more blocks.  ``placed`` (a B case of camera_grad_cases: positions of the scene's Gaussians among padding): also
+    the radii — 0 on the padding in every view, the C oracle's everywhere — and the reduction workspace is poisoned before
+    the backward.  ``info`` receives what the caller asserts on."""
+    V = views32.shape[0]
+    fwds = oracle_forwards(views32, H, W, means, cov, opac, payload, scenes)
+    assert fragile_counts(None, H, W, None, None, None, None, forwards=fwds) == [0] * V
+    moded = bool((views32[:, 41] != 0).all())
+    w = _weights(V, H, W, C)
+    got32, radii = _op_grad(views32, H, W, means, cov, opac, kw, C, contraction, poison=placed is not None)
+    if placed is not None:
+        want_radii = torch.from_numpy(np.stack([f["radii"] for f in fwds])).to(radii.dtype)
+        pad = torch.ones(means.shape[-2], dtype=torch.bool)
+        pad[placed] = False
+        assert not bool(pad.any()) or int(radii[:, pad].abs().max()) == 0
+        assert torch.equal(radii, want_radii)
+    got = got32.double()
+    blocks = dict(BLOCKS, near=slice(42, 43), far=slice(43, 44)) if moded else BLOCKS
+    worst, wants, masks = 0.0, [], []
     for v in range(V):
         rec = views32[v].double().clone().requires_grad_(True)
         vm, pm, cp = rec[0:16], rec[16:32], rec[32:35]
         tx, ty, bg, s = rec[35], rec[36], rec[37:40], rec[40]
         sidx, m, c6, o = _view_inputs(views32, v, means, cov, opac, scenes)
-        out = _oracle_view(v, vm, pm, cp, tx, ty, bg, s, H, W, m, c6, o, lambda ms, cpos: payload(ms, cpos, sidx))
-        _loss(*out, w[v]).backward()
+        col, feat, mask, depth = _oracle_view(v, vm, pm, cp, tx, ty, bg, s, H, W, m, c6, o,
+                                              lambda ms, cpos: with_depth_channel(payload(ms, cpos, sidx), rec, m))
+        if moded:
+            depth, feat = feat[-1:], (feat[:-1] if feat.shape[0] > 1 else None)
+        _loss(col, feat, mask, depth, w[v]).backward()
         want = rec.grad
-        assert float(want[41:].abs().max()) == 0.0 and float(got[v, 41:].abs().max()) == 0.0
-        for name, sl in BLOCKS.items():
+        wants.append(want)
+        masks.append(mask.detach())
+        assert float(want[41].abs()) == 0.0 and float(got[v, 41].abs()) == 0.0
+        if not moded:
+            assert float(want[42:].abs().max()) == 0.0 and float(got[v, 42:].abs().max()) == 0.0
+        for name, sl in blocks.items():
             err = float((got[v, sl] - want[sl]).abs().max())
             norm = float(want[sl].norm())
             ratio = err / max(norm, 1e-12)
@@ -150,21 +147,9 @@ def _kernel_vs_oracle(views32, H, W, means, cov, opac, kw, payload, C, scenes=No
                 worst = max(worst, ratio)
             assert err <= tol * max(norm, 1e-6), (v, name, got[v, sl], want[sl])
     print(f"worst per-block error / norm: {worst:.2e}")
+    if info is not None:
+        info.update(got=got, want=torch.stack(wants), radii=radii, masks=masks, forwards=fwds)
     return worst
-
-
-def _sh_payload(deg, shs_g, axes="3dgs"):
-    """colour SH in float64: the oracle's own basis (3DGS axes) or the reference axes B(z, x, y) as colours_precomp"""
-    def f(ms, cp, sidx):
-        sh = shs_g if shs_g.dim() == 3 else shs_g[sidx]
-        sh = sh.double()
-        if axes == "3dgs":
-            return dict(shs=sh, sh_degree=deg)
-        d = ms - cp[None]
-        d = d / d.norm(dim=-1, keepdim=True)
-        b = TO.sh_basis(deg, d[:, [2, 0, 1]])
-        return dict(colors_precomp=torch.clamp_min(torch.einsum("gk,gkc->gc", b, sh[:, : b.shape[1]]) + 0.5, 0.0))
-    return f
 
 
 @pytest.mark.parametrize("axes", ["3dgs", "reference"])
@@ -225,6 +210,69 @@ def test_view_groups(hip_device):
     opac = torch.stack([s.opacities[:, None] for s in scenes])
     shs = torch.stack([s.color_sh.transpose(1, 2) for s in scenes]).contiguous()
     _kernel_vs_oracle(views, H, W, means, cov6, opac, dict(shs=shs, sh_degree=2), _sh_payload(2, shs), 0, scenes=2)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 4+ views per group and more than 64 chunks (tests/camera_grad_cases.py: what each case reaches and why)
+# ---------------------------------------------------------------------------------------------------------------------
+def _run_case(name):
+    c, info = cases.case(name), {}
+    _kernel_vs_oracle(c.views, c.H, c.W, c.means, c.cov, c.opac, c.kw, c.payload, c.C, scenes=c.scenes,
+                      contraction=c.contraction, placed=c.placed, info=info)
+    return c, info
+
+
+@pytest.mark.parametrize("name", ["A1", "A2", "A2-contraction", "A2-depth", "A3", "A4", "A4-depth", "A5", "A6"])
+def test_view_parallel_instances_match_oracle(hip_device, name):
+    """k_preprocess_bwd<4, *, true> (V >= 4 views per group) and every view chunk of k_sh_bwd<..., true>"""
+    c, info = _run_case(name)
+    assert cases.view_parallel_shape(c)[0] == 4
+    if name == "A3":     # nothing depends on the camera position: exactly zero in the oracle, the zero-norm floor on the device
+        assert float(info["want"][:, 32:35].abs().max()) == 0.0
+    if c.mode is not None:
+        assert bool((info["want"][:, 42:44].abs() > 0).all())
+    if name == "A6":
+        assert cases.sh_backward_lds_bytes(4, cases.A6_CHANNELS, 2) > 65536
+
+
+@pytest.mark.parametrize("name", ["B1", "B2", "B3"])
+def test_reduction_with_several_chunks_per_slice(hip_device, name):
+    """k_view_grad_partial with per > 1 chunks per slice (B1), per > 8: the row loop wraps (B2), per > 256: the near / far
+    loop wraps (B3), on scenes padded with Gaussians that every view culls"""
+    c, info = _run_case(name)
+    cases.assert_reduction_structure(name, c, info["radii"])
+    if name == "B3":
+        assert float(info["want"][0, 42].abs()) > 0 and float(info["want"][0, 43].abs()) > 0
+
+
+def test_background_sum_over_more_than_256_pixels_per_slice(hip_device):
+    """128 x 160: 320 pixels per slice; the background block at the bar with final T from ~0 to 1 over the image"""
+    c, info = _run_case("B4")
+    cases.assert_reduction_structure("B4", c, info["radii"])
+    cases.assert_background_mask(info["masks"][0])
+
+
+def test_reduction_is_bitwise_reproducible(hip_device):
+    """views.grad of two identical runs of every B case, bit for bit: the reduction adds its records in a fixed order (no
+    atomics) — the first time with more than 4 chunks.  The partial records are sums of the compositing backward's
+    per-Gaussian records, whose cross-tile float atomics are order independent only under LSR_DETERMINISTIC=1 (the
+    condition include/lsr_rasterizer.h states for this promise); the knob is read once per process, hence the subprocess."""
+    code = r'''
+import sys, torch
+sys.path.insert(0, %r)
+from tests import camera_grad_cases as cases
+from tests.test_camera_grads_gpu import _op_grad
+flags = []
+for name in ("B1", "B2", "B3", "B4"):
+    c = cases.case(name)
+    a, b = (_op_grad(c.views, c.H, c.W, c.means, c.cov, c.opac, c.kw, c.C, poison=True)[0] for _ in range(2))
+    flags.append(bool(torch.equal(a, b)) and bool(torch.isfinite(a).all()) and float(a.abs().max()) > 0)
+print("RESULT", *flags)
+''' % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, LSR_DETERMINISTIC="1")
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert r.stdout.strip().splitlines()[-1] == "RESULT True True True True", r.stdout
 
 
 def edge_case():
