@@ -1,5 +1,5 @@
 """ctypes binding of ``liblsr_hip.so`` (C ABI: include/lsr_rasterizer.h, include/lsr_adapter.h, include/lsr_latent.h, include/lsr_ply.h,
-include/lsr_sh_rotate.h).
+include/lsr_sh_rotate.h, include/lsr_depth_head.h).
 
 The library is built in-tree by ``latentsplat_amd/csrc/Makefile`` (``__graft_entry__.build()``).
 There is no CPU fallback: if the shared object is missing or not loadable this module raises, and
@@ -130,6 +130,17 @@ class ShRotateDims(C.Structure):     # lsr_sh_rotate_dims (include/lsr_sh_rotate
 SH_ROTATE_MAX_DEGREE = 4
 
 
+class DepthHeadDims(C.Structure):    # lsr_depth_head_dims (include/lsr_depth_head.h)
+    _fields_ = [("num_cameras", C.c_int32), ("rays", C.c_int32), ("buckets", C.c_int32),
+                ("surfaces", C.c_int32), ("samples", C.c_int32), ("flags", C.c_int32),
+                ("opacity_exponent", C.c_float), ("opacity_scale", C.c_float),
+                ("row_stride", C.c_int64), ("grad_row_stride", C.c_int64)]
+
+
+DEPTH_HEAD_DETERMINISTIC, DEPTH_HEAD_TRANSMITTANCE = 1, 2   # lsr_depth_head_dims.flags
+DEPTH_HEAD_MAX_BUCKETS, DEPTH_HEAD_MAX_SAMPLES, DEPTH_HEAD_MAX_ROW_FLOATS = 64, 8, 4096
+
+
 def sh_rotate_table_floats(degree: int) -> int:
     """LSR_SH_ROTATE_TABLE_FLOATS: sum of (2l+1)^2 over l <= degree."""
     return (degree + 1) * (2 * degree + 1) * (2 * degree + 3) // 3
@@ -145,6 +156,7 @@ EXPORTS = (
     "lsr_adapter_forward", "lsr_adapter_backward", "lsr_latent_forward", "lsr_latent_backward",
     "lsr_ply_pack", "lsr_ply_write_host",
     "lsr_sh_rotation_matrices", "lsr_sh_rotate_forward", "lsr_sh_rotate_backward",
+    "lsr_depth_head_forward", "lsr_depth_head_backward",
 )
 
 _lib = None
@@ -259,6 +271,10 @@ def load():
     lib.lsr_sh_rotate_forward.argtypes = [C.POINTER(ShRotateDims), P, P, P, P, P, P, P]
     lib.lsr_sh_rotate_backward.restype = C.c_int
     lib.lsr_sh_rotate_backward.argtypes = [C.POINTER(ShRotateDims), P, P, P, P, P, P, P]
+    lib.lsr_depth_head_forward.restype = C.c_int
+    lib.lsr_depth_head_forward.argtypes = [C.POINTER(DepthHeadDims), P, P, P, P, P, P, P, P]
+    lib.lsr_depth_head_backward.restype = C.c_int
+    lib.lsr_depth_head_backward.argtypes = [C.POINTER(DepthHeadDims), P, P, P, P, P, P, P, P]
     _lib = lib
     return lib
 
