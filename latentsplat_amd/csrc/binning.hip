@@ -210,11 +210,22 @@ __device__ __forceinline__ uint32_t key_index(const HalfOut &ho, uint32_t low_wo
 // 16-bit sub-block mask of a sorted key's low word; list entry of a half
 __device__ __forceinline__ uint32_t key_mask(const HalfOut &ho, uint32_t low_word) { return ho.ip.key_shift ? code_mask(low_word & 0xFFu) : 0xFFFFu; }
 __device__ __forceinline__ uint32_t list_entry(const HalfOut &ho, uint32_t idx, uint32_t bits) { return idx | ((bits << kListBitsShift) & ~ho.ip.index_mask); }
-constexpr int kEmitTab = 130;   // uint64 words of LDS scratch emit_half_lists needs
+constexpr int kEmitScan = 130;            // uint64 words of LDS scratch emit_half_lists' counting passes need
+constexpr int kEmitTab = kEmitScan + 64;  // ... and behind them the 256-entry table code -> 16-bit sub-block mask (uint16)
+
+// The emitter looks the sub-block mask of every entry up twice (count, then write): code_mask is ~25 VALU
+// instructions of a function of eight bits, so the workgroup evaluates it once per CODE into LDS.  Block-wide; the
+// caller puts a barrier between this and emit_half_lists.  (Keys without codes, key_shift == 0: constant mask, no table.)
+template <int THREADS>
+__device__ __forceinline__ void build_mask_table(const HalfOut &ho, uint64_t *s_tab) {
+    uint16_t *s_mask = (uint16_t *)(s_tab + kEmitScan);
+    if (ho.ip.key_shift)
+        for (int c = threadIdx.x; c < 256; c += THREADS) s_mask[c] = (uint16_t)code_mask((uint32_t)c);
+}
 
 // Block-wide (THREADS threads): walks the tile's depth-sorted list in order and appends every entry to
 // the list of each half of the tile (pixel rows 0-7 / 8-15) its footprint can reach (order preserved), as
-// `index | 8 sub-block bits << 24`; the sub-block mask comes from the code in the low key byte.
+// `index | 8 sub-block bits << 24`; the sub-block mask comes from the code in the low key byte (build_mask_table).
 // low_word(p) = low key word of sorted position p.  A pass covers 64 wave-chunks of 64 positions: per chunk
 // and half a ballot count (two 32-bit fields of one u64), one wave scans the 64 chunk totals, then every
 // entry's place is chunk offset + lanes below it in the ballot.
@@ -223,6 +234,9 @@ template <int THREADS, class LowWord>
 __device__ __forceinline__ void emit_half_lists(const HalfOut &ho, uint32_t n, uint32_t *hdst, uint32_t *hcnt, uint64_t *s_tab, LowWord low_word) {
     const int tid = threadIdx.x, lane = tid & (LSR_WAVE - 1), wid = tid / LSR_WAVE;
     constexpr int kWaves = THREADS / LSR_WAVE;
+    const uint16_t *s_mask = (const uint16_t *)(s_tab + kEmitScan);
+    const bool coded = ho.ip.key_shift != 0;
+    auto mask_of = [&](uint32_t w) -> uint32_t { return coded ? (uint32_t)s_mask[w & 0xFFu] : 0xFFFFu; };
     uint32_t run0 = 0u, run1 = 0u;
     for (uint32_t base = 0; base < n; base += LSR_WAVE * LSR_WAVE) {
         // (nothing but the running lengths lives across the barriers: the second phase reads the words again — the
@@ -232,7 +246,7 @@ __device__ __forceinline__ void emit_half_lists(const HalfOut &ho, uint32_t n, u
             uint64_t packed = 0;
             if (p - lane < n) {                                        // wave-uniform: chunks beyond the list only write their zero
                 const uint32_t w = low_word(min(p, n - 1));            // unconditional at a clamped position
-                const uint32_t m16 = p < n ? key_mask(ho, w) : 0u;
+                const uint32_t m16 = p < n ? mask_of(w) : 0u;
                 packed = (uint64_t)__builtin_popcountll(__ballot((m16 & 0x00FFu) != 0u)) |
                          ((uint64_t)__builtin_popcountll(__ballot((m16 & 0xFF00u) != 0u)) << 32);
             }
@@ -253,7 +267,7 @@ __device__ __forceinline__ void emit_half_lists(const HalfOut &ho, uint32_t n, u
             const uint32_t p = base + (uint32_t)(c * LSR_WAVE + lane);
             if (p - lane >= n) break;                                  // wave-uniform
             const uint32_t w = low_word(min(p, n - 1));
-            const uint32_t idx = key_index(ho, w), m16 = p < n ? key_mask(ho, w) : 0u;
+            const uint32_t idx = key_index(ho, w), m16 = p < n ? mask_of(w) : 0u;
             const uint64_t off = s_tab[LSR_WAVE + c];
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
@@ -269,6 +283,27 @@ __device__ __forceinline__ void emit_half_lists(const HalfOut &ho, uint32_t n, u
         __syncthreads();   // s_tab is reused by the next pass
     }
     if (tid < 2) hcnt[tid] = tid == 0 ? run0 : run1;
+}
+
+// Reductions over the 16 lanes of every DPP row (result in each lane of the row); all lanes of the wave active.
+template <int CTRL> __device__ __forceinline__ uint32_t dpp_u32(uint32_t x) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, 0xf, false); }
+#define LSR_ROW_REDUCE(name, op)                                                                        \
+    __device__ __forceinline__ uint32_t name(uint32_t x) {                                              \
+        x = op(x, dpp_u32<0xB1>(x));  /* quad_perm [1,0,3,2] */                                         \
+        x = op(x, dpp_u32<0x4E>(x));  /* quad_perm [2,3,0,1] */                                         \
+        x = op(x, dpp_u32<0x141>(x)); /* row_half_mirror */                                             \
+        return op(x, dpp_u32<0x140>(x)); /* row_mirror */                                               \
+    }
+__device__ __forceinline__ uint32_t add_u32(uint32_t a, uint32_t b) { return a + b; }
+__device__ __forceinline__ uint32_t min_u32(uint32_t a, uint32_t b) { return a < b ? a : b; }
+__device__ __forceinline__ uint32_t max_u32(uint32_t a, uint32_t b) { return a > b ? a : b; }
+LSR_ROW_REDUCE(row_min_u32, min_u32)
+LSR_ROW_REDUCE(row_max_u32, max_u32)
+LSR_ROW_REDUCE(row_sum_u32, add_u32)
+#undef LSR_ROW_REDUCE
+__device__ __forceinline__ uint32_t rdlane(uint32_t x, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)x, l); }
+__device__ __forceinline__ uint64_t uniform_u64(uint64_t x) {   // a value every lane holds, moved to scalar registers
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(x >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)x);
 }
 
 // One workgroup of THREADS (= 512) threads per (tile, view); list length n <= CAP, keys in registers (CAP / THREADS per
@@ -295,6 +330,14 @@ __device__ __forceinline__ void emit_half_lists(const HalfOut &ho, uint32_t n, u
 // request the next tile's keys while the current tile's lists are written and count the half-list entries while the
 // sorted words are placed (no counting pass, two barriers fewer): 0.074 ms at 80 VGPRs with spills, 0.086 at 96, against
 // 0.065 for this kernel — on gfx9 the wait for the prefetched keys also waits for the list stores issued behind them.
+//
+// Instruction diet (profiles/sort_lengths_ab.md; headline launch 59.1 -> 48.4 us, 822 -> 613 VALU instructions per wave):
+// the key range comes from the depth words alone (u32 over DPP rows, one cross-wave partial per thread; the exact 64-bit
+// range only when the depth words span fewer values than there are buckets): 6.4 us; the emitter reads its sub-block
+// masks from a 256-entry LDS table instead of evaluating code_mask twice per key: 2.6 us; the scan reads the wave totals
+// in one row sum: 1.1 us; the per-key loops of the first-tier instances leave at the end of the list through a scalar
+// branch: 0.5 us (the compiler already skipped the masked-off bodies).  The persistent tiers (16 / 32 keys per thread) keep
+// whole loops: with the early exit their key arrays went to scratch.
 constexpr uint32_t kBucketOverflow = 48;   // longest bucket the in-bucket pass may get
 
 // tier: 0 = first launch of a call (also owns the empty lists), 1 = a later tier (its tiles come from a long list)
@@ -312,8 +355,10 @@ __device__ __forceinline__ void sort_tile(uint64_t *s_keys, size_t vt, int tier,
     constexpr int NB = CAP < 2048 ? CAP : 2048;          // buckets
     constexpr int kWaves = THREADS / LSR_WAVE;
     uint32_t *s_cnt = (uint32_t *)(s_keys + CAP);         // [NB] histogram -> bucket offsets
-    uint64_t *s_red = s_keys;                             // [2 * kWaves] range reduction  } alias the key array:
-    uint32_t *s_wsum = (uint32_t *)(s_keys + 2 * kWaves); // [kWaves] scan partials        } dead before the
+    static_assert(kWaves <= 16 && (kWaves & (kWaves - 1)) == 0, "cross-wave partials are reduced inside one DPP row");
+    uint2 *s_red32 = (uint2 *)s_keys;                     // [kWaves] depth-word range     }
+    uint64_t *s_red = s_keys + kWaves;                    // [2 * kWaves] exact key range  } alias the key array:
+    uint32_t *s_wsum = (uint32_t *)(s_keys + 3 * kWaves); // [kWaves] scan partials        } dead before the
     uint32_t *s_flag = s_wsum + kWaves;                   // bucket overflow               } first key is placed
     const int tid = threadIdx.x, lane = tid & (LSR_WAVE - 1), wid = tid / LSR_WAVE;
     const uint32_t start = tile_start[vt], n = tile_start[vt + 1] - start;
@@ -354,34 +399,62 @@ __device__ __forceinline__ void sort_tile(uint64_t *s_keys, size_t vt, int tier,
     }
 
     constexpr int PERK = CAP / THREADS;   // keys per thread, register-resident (the 16 384-key variant: 32 keys, 256 VGPRs)
+    // Slots of a thread that hold a key: block-uniform, so every unrolled per-key loop below leaves through a SCALAR
+    // branch at the end of the list instead of issuing masked-off bodies up to the tier's capacity.
+    const int nq = __builtin_amdgcn_readfirstlane((int)((n + THREADS - 1) / THREADS));
+    constexpr bool kEarly = PERK <= 8;
+#define LSR_LIVE(q) if (kEarly && (q) >= nq) break
     uint64_t kreg[PERK];
 #pragma unroll
     for (int q = 0; q < PERK; ++q) {
-        const uint32_t i = tid + q * THREADS;
-        const uint64_t k = src[min(i, n - 1)];   // unconditional (clamped) so that all loads are in flight together
-        kreg[q] = i < n ? k : ~0ull;
+        LSR_LIVE(q);
+        kreg[q] = src[min((uint32_t)(tid + q * THREADS), n - 1)];   // unconditional (clamped: the last slot's spare threads hold copies of the last key) so that all loads are in flight together
     }
-    // ---- key range ----
-    uint64_t kmin = ~0ull, kmax = 0ull;
-#pragma unroll
-    for (int q = 0; q < PERK; ++q) {
-        const uint64_t k = kreg[q];
-        kmin = k < kmin ? k : kmin;
-        if (tid + q * THREADS < n) kmax = k > kmax ? k : kmax;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint64_t a = __shfl_xor(kmin, off), b = __shfl_xor(kmax, off);
-        kmin = a < kmin ? a : kmin; kmax = b > kmax ? b : kmax;
-    }
-    if (lane == 0) { s_red[2 * wid] = kmin; s_red[2 * wid + 1] = kmax; }
     for (int b = tid; b < NB; b += THREADS) s_cnt[b] = 0;
     if (tid == 0) *s_flag = 0;
-    __syncthreads();
+    // ---- key range: any kmin <= every key and kmax >= every key will do (bucket = (key - kmin) >> shift stays monotone and
+    // below NB), so the depth words alone are reduced, as u32 over DPP, and a thread reads ONE cross-wave partial ----
+    uint64_t kmin, kmax;
+    uint32_t dmin = ~0u, dmax = 0u;
 #pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-        kmin = s_red[2 * w] < kmin ? s_red[2 * w] : kmin;
-        kmax = s_red[2 * w + 1] > kmax ? s_red[2 * w + 1] : kmax;
+    for (int q = 0; q < PERK; ++q) {
+        LSR_LIVE(q);
+        const uint32_t dw = (uint32_t)(kreg[q] >> 32);
+        dmin = min(dmin, dw); dmax = max(dmax, dw);
+    }
+    dmin = row_min_u32(dmin); dmax = row_max_u32(dmax);
+    const uint32_t wmin = min(min(rdlane(dmin, 0), rdlane(dmin, 16)), min(rdlane(dmin, 32), rdlane(dmin, 48)));
+    const uint32_t wmax = max(max(rdlane(dmax, 0), rdlane(dmax, 16)), max(rdlane(dmax, 32), rdlane(dmax, 48)));
+    if (lane == 0) s_red32[wid] = make_uint2(wmin, wmax);
+    __syncthreads();
+    const uint2 part = s_red32[lane & (kWaves - 1)];      // (every row of the wave sees all partials)
+    dmin = (uint32_t)__builtin_amdgcn_readfirstlane((int)row_min_u32(part.x));
+    dmax = (uint32_t)__builtin_amdgcn_readfirstlane((int)row_max_u32(part.y));
+    kmin = (uint64_t)dmin << 32; kmax = ((uint64_t)dmax << 32) | 0xFFFFFFFFull;
+    // depth words spanning fewer than NB values (coplanar Gaussians): the index words have to spread the keys, or every
+    // such tile would overfill its buckets and take the bitonic network — the exact 64-bit range, as a cold path
+    const bool exact = dmax - dmin < (uint32_t)NB;
+    if (exact) {
+        uint64_t lo = ~0ull, hi = 0ull;
+#pragma unroll
+        for (int q = 0; q < PERK; ++q) {
+            LSR_LIVE(q);
+            const uint64_t k = kreg[q];
+            lo = k < lo ? k : lo; hi = k > hi ? k : hi;
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const uint64_t a = __shfl_xor(lo, off), b = __shfl_xor(hi, off);
+            lo = a < lo ? a : lo; hi = b > hi ? b : hi;
+        }
+        if (lane == 0) { s_red[2 * wid] = lo; s_red[2 * wid + 1] = hi; }
+        __syncthreads();
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) {
+            lo = s_red[2 * w] < lo ? s_red[2 * w] : lo;
+            hi = s_red[2 * w + 1] > hi ? s_red[2 * w + 1] : hi;
+        }
+        kmin = uniform_u64(lo); kmax = uniform_u64(hi);
     }
     LSR_STAMP(1);
     const uint64_t range = kmax - kmin;
@@ -392,8 +465,10 @@ __device__ __forceinline__ void sort_tile(uint64_t *s_keys, size_t vt, int tier,
     // ---- histogram (the returning atomic is the key's rank inside its bucket), scan ----
     uint32_t rnk[PERK];
 #pragma unroll
-    for (int q = 0; q < PERK; ++q)   // (under the validity test: padding lanes on one dummy word serialise — measured 0.048 -> 0.077 ms)
+    for (int q = 0; q < PERK; ++q) {   // (under the validity test: padding lanes on one dummy word serialise — measured 0.048 -> 0.077 ms)
+        LSR_LIVE(q);
         if (tid + q * THREADS < n) rnk[q] = atomicAdd(&s_cnt[(uint32_t)((kreg[q] - kmin) >> shift)], 1u);
+    }
     __syncthreads();
     LSR_STAMP(2);
     constexpr int PER = (NB + THREADS - 1) / THREADS;   // buckets per thread of the scan (the last threads may own fewer)
@@ -410,8 +485,10 @@ __device__ __forceinline__ void sort_tile(uint64_t *s_keys, size_t vt, int tier,
     if (mx > kBucketOverflow) *s_flag = 1;
     __syncthreads();
     uint32_t run = incl - sum;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) run += w < wid ? s_wsum[w] : 0u;
+    {   // the waves before this one: lane w reads wave w's total, one row sum instead of kWaves reads per thread
+        const uint32_t mine = s_wsum[lane & (kWaves - 1)];
+        run += (uint32_t)__builtin_amdgcn_readfirstlane((int)row_sum_u32(lane < wid ? mine : 0u));
+    }
     const bool overflow = *s_flag != 0;
     if (!overflow) {
 #pragma unroll
@@ -420,8 +497,10 @@ __device__ __forceinline__ void sort_tile(uint64_t *s_keys, size_t vt, int tier,
         LSR_STAMP(3);
         // ---- place: start of the bucket + arrival rank ----
 #pragma unroll
-        for (int q = 0; q < PERK; ++q)
+        for (int q = 0; q < PERK; ++q) {
+            LSR_LIVE(q);
             if (tid + q * THREADS < n) s_keys[s_cnt[(uint32_t)((kreg[q] - kmin) >> shift)] + rnk[q]] = kreg[q];
+        }
         __syncthreads();
         LSR_STAMP(4);
         // ---- final position of every key: bucket start + number of smaller members ----
@@ -429,7 +508,7 @@ __device__ __forceinline__ void sort_tile(uint64_t *s_keys, size_t vt, int tier,
 #pragma unroll
         for (int q = 0; q < PERK; ++q) {
             dst[q] = 0;
-            if (tid + q * THREADS < n) {
+            if ((!kEarly || q < nq) && tid + q * THREADS < n) {   // (no break here: the unroller gives up on an early exit around the inner loop)
                 const uint64_t key = kreg[q];
                 const uint32_t b = (uint32_t)((key - kmin) >> shift);
                 const uint32_t lo = s_cnt[b], hi = b + 1 < (uint32_t)NB ? s_cnt[b + 1] : n;
@@ -445,12 +524,14 @@ __device__ __forceinline__ void sort_tile(uint64_t *s_keys, size_t vt, int tier,
         __syncthreads();   // all reads of the key array done: its storage becomes the sorted list of low key words
         uint32_t *s_out = (uint32_t *)s_keys;
 #pragma unroll
-        for (int q = 0; q < PERK; ++q)
+        for (int q = 0; q < PERK; ++q) {
+            LSR_LIVE(q);
             if (tid + q * THREADS < n) s_out[dst[q]] = (uint32_t)kreg[q];
+        }
+        build_mask_table<THREADS>(ho, (uint64_t *)s_cnt);   // (the bucket offsets in s_cnt are dead: scratch of the emitter)
         __syncthreads();
         LSR_STAMP(5);
         for (uint32_t i = tid; i < n; i += THREADS) point_list[start + i] = key_index(ho, s_out[i]);
-        // half-tile render lists (the bucket offsets in s_cnt are dead: scratch of the emitter)
         emit_half_lists<THREADS>(ho, n, hdst, hcnt, (uint64_t *)s_cnt, [&](uint32_t p) { return s_out[p]; });
         LSR_STAMP(6);
     } else {
@@ -458,18 +539,15 @@ __device__ __forceinline__ void sort_tile(uint64_t *s_keys, size_t vt, int tier,
         uint32_t npad = 2;
         while (npad < n) npad <<= 1;
         __syncthreads();
-        if (npad <= (uint32_t)CAP) {
+        // (CAP = 3072: a list of 2049 .. 3072 keys pads to 4096 > CAP; the key array and the bucket counters behind it
+        // hold 3072 + 1024 keys' worth of bytes — exactly the padded list)
+        static_assert(CAP * 8 + NB * 4 >= (CAP <= 2048 ? CAP : (CAP <= 4096 ? 4096 : CAP)) * 8, "bitonic padding fits the allocation");
 #pragma unroll
-            for (int q = 0; q < PERK; ++q)
-                if (tid + q * THREADS < npad) s_keys[tid + q * THREADS] = kreg[q];   // padding = ~0
-        } else {
-            // (CAP = 3072: a list of 2049 .. 3072 keys pads to 4096 > CAP; the key array and the bucket counters behind it
-            // hold 3072 + 1024 keys' worth of bytes — exactly the padded list)
-            static_assert(CAP * 8 + NB * 4 >= (CAP <= 2048 ? CAP : (CAP <= 4096 ? 4096 : CAP)) * 8, "bitonic padding fits the allocation");
-#pragma unroll
-            for (int q = 0; q < PERK; ++q) s_keys[tid + q * THREADS] = kreg[q];
-            for (uint32_t i = CAP + tid; i < npad; i += THREADS) s_keys[i] = ~0ull;
+        for (int q = 0; q < PERK; ++q) {
+            LSR_LIVE(q);
+            if (tid + q * THREADS < n) s_keys[tid + q * THREADS] = kreg[q];
         }
+        for (uint32_t i = n + tid; i < npad; i += THREADS) s_keys[i] = ~0ull;   // padding
         __syncthreads();
         for (uint32_t k = 2; k <= npad; k <<= 1) {
             for (uint32_t j = k >> 1; j > 0; j >>= 1) {
@@ -485,6 +563,8 @@ __device__ __forceinline__ void sort_tile(uint64_t *s_keys, size_t vt, int tier,
             }
         }
         // (the emitter's scratch, the counter array, only overlaps padding keys: it reads positions < n <= CAP)
+        build_mask_table<THREADS>(ho, (uint64_t *)s_cnt);
+        __syncthreads();
         for (uint32_t i = tid; i < n; i += THREADS) point_list[start + i] = key_index(ho, (uint32_t)s_keys[i]);
         emit_half_lists<THREADS>(ho, n, hdst, hcnt, (uint64_t *)s_cnt, [&](uint32_t p) { return (uint32_t)s_keys[p]; });
     }
@@ -496,6 +576,7 @@ __device__ __forceinline__ void sort_tile(uint64_t *s_keys, size_t vt, int tier,
         trace[8 * (size_t)blockIdx.x + 7] = ((unsigned long long)n << 40) | ((unsigned long long)(xcc & 0xff) << 32) | hwid;
     }
 #endif
+#undef LSR_LIVE
 #undef LSR_STAMP
 }
 
@@ -552,6 +633,8 @@ __device__ __forceinline__ void sort_tile_global(size_t vt, const uint32_t *__re
     for (uint32_t i = threadIdx.x; i < n; i += kSortThreads)
         point_list[start + i] = key_index(ho, (uint32_t)src[i]);
     const uint64_t *sorted = src;
+    build_mask_table<kSortThreads>(ho, s_tab);
+    __syncthreads();
     emit_half_lists<kSortThreads>(ho, n, ho.half_list + 2 * (size_t)start, ho.half_count + 2 * vt, s_tab, [&](uint32_t p) { return (uint32_t)sorted[p]; });
 }
 __global__ void __launch_bounds__(kSortThreads)

@@ -18,6 +18,9 @@ SORT = ["load + range", "histogram", "bucket scan", "place", "rank + sorted word
 
 
 def analyze(path, phases, tick_ns):
+    if not os.path.exists(path):   # (single-pass binning launches no scatter unless a list outgrows its segment)
+        print(path, ": not written (the kernel was not launched)")
+        return
     raw = np.fromfile(path, dtype=np.uint64).reshape(-1, 8)
     raw = raw[raw[:, 0] > 0]
     if not len(raw):
