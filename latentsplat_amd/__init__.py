@@ -4,12 +4,14 @@ Only what the hot path needs: ``csrc/`` (HIP kernels + C ABI), ``rasterizer`` (d
 ``GaussianRasterizer`` API + batched multi-view op), ``decoder`` (mirror of the reference's
 ``src/model/decoder`` surface), ``gaussian_adapter`` / ``sh_rotate`` (the encoder's adapter tail:
 geometry and SH coefficient rotation), ``depth_head`` (the encoder's depth logits to the adapter's
-depths and opacities; the op itself is ``latentsplat_amd.depth_head.depth_head``) and ``synthetic`` (seeded scenes for tests / bench).
+depths and opacities; the op itself is ``latentsplat_amd.depth_head.depth_head``), ``ply_export`` / ``ply_import`` (3DGS
+``.ply`` files out and in) and ``synthetic`` (seeded scenes for tests / bench).
 """
 __version__ = "0.1.0"
 
 _LAZY = {"rotate_sh": "sh_rotate", "GaussianAdapter": "gaussian_adapter", "GaussianAdapterCfg": "gaussian_adapter",
-         "Gaussians": "gaussian_adapter", "DepthPredictorMonocular": "depth_head", "opacity_exponent": "depth_head"}
+         "Gaussians": "gaussian_adapter", "DepthPredictorMonocular": "depth_head", "opacity_exponent": "depth_head",
+         "Scene3DGS": "ply_import", "load_ply": "ply_import", "unpack_vertices": "ply_import"}
 
 
 def __getattr__(name):     # torch is imported only when one of these is first used

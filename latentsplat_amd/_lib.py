@@ -119,6 +119,18 @@ class PlyInputs(C.Structure):        # lsr_ply_inputs (include/lsr_ply.h)
 
 
 PLY_VERTEX_FLOATS = 17
+PLY_MAX_SH_COEFFS, PLY_MAX_REST, PLY_MAX_STRIDE = 25, 72, 8192   # LSR_PLY_MAX_*
+PLY_OPACITY_RAW = 1                                               # lsr_ply_unpack flags
+
+
+class PlyLayout(C.Structure):        # lsr_ply_layout (include/lsr_ply.h): where each named property sits inside a row
+    _fields_ = [("n", C.c_int64), ("data_offset", C.c_int64), ("stride", C.c_int32), ("sh_coeffs", C.c_int32),
+                ("xyz", C.c_int32 * 3), ("f_dc", C.c_int32 * 3), ("opacity", C.c_int32), ("scale", C.c_int32 * 3),
+                ("rot", C.c_int32 * 4), ("f_rest", C.c_int32 * PLY_MAX_REST)]
+
+
+class PlyOutputs(C.Structure):       # lsr_ply_outputs
+    _fields_ = [(n, C.c_void_p) for n in ("means", "shs", "opacities", "scales", "rotations", "cov3D")]
 
 
 class ShRotateDims(C.Structure):     # lsr_sh_rotate_dims (include/lsr_sh_rotate.h)
@@ -154,7 +166,7 @@ EXPORTS = (
     "lsr_profile_enable", "lsr_profile_num_stages", "lsr_profile_stage_name", "lsr_profile_read",
     "lsr_debug_set_knob", "lsr_set_projection_contraction", "lsr_get_projection_contraction",
     "lsr_adapter_forward", "lsr_adapter_backward", "lsr_latent_forward", "lsr_latent_backward",
-    "lsr_ply_pack", "lsr_ply_write_host",
+    "lsr_ply_pack", "lsr_ply_write_host", "lsr_ply_read_header", "lsr_ply_read_rows", "lsr_ply_unpack",
     "lsr_sh_rotation_matrices", "lsr_sh_rotate_forward", "lsr_sh_rotate_backward",
     "lsr_depth_head_forward", "lsr_depth_head_backward",
 )
@@ -265,6 +277,12 @@ def load():
     lib.lsr_ply_pack.argtypes = [I64, I32, C.POINTER(PlyInputs), P, P]
     lib.lsr_ply_write_host.restype = C.c_int
     lib.lsr_ply_write_host.argtypes = [C.c_char_p, P, I64]
+    lib.lsr_ply_read_header.restype = C.c_int
+    lib.lsr_ply_read_header.argtypes = [C.c_char_p, C.POINTER(PlyLayout)]
+    lib.lsr_ply_read_rows.restype = C.c_int
+    lib.lsr_ply_read_rows.argtypes = [C.c_char_p, P, I64]
+    lib.lsr_ply_unpack.restype = C.c_int
+    lib.lsr_ply_unpack.argtypes = [C.POINTER(PlyLayout), P, I32, C.POINTER(PlyOutputs), P]
     lib.lsr_sh_rotation_matrices.restype = C.c_int
     lib.lsr_sh_rotation_matrices.argtypes = [I32, P, I64, I64, I32, P, P]
     lib.lsr_sh_rotate_forward.restype = C.c_int

@@ -5,6 +5,8 @@
 // that the exported quaternion has the same sign as the reference's.
 #include <stdio.h>
 
+#include <algorithm>
+
 #include "lsr_internal.h"
 #include "lsr_ply.h"
 
@@ -76,6 +78,123 @@ __global__ __launch_bounds__(256) void k_ply_pack(int64_t n, int d_sh, lsr_ply_i
     v[16] = (float)(q[2] * qn);
 }
 
+// ---- import: rows of a standard 3DGS scene file -> the rasterizer's tensors (lsr_ply_unpack) ----
+// A workgroup owns `rpb` consecutive rows.  Rows are 17 ... 89 floats (more with extra properties), so a lane that
+// walked its own row in global memory would touch one dword of every cache line per load; instead the workgroup's
+// block of rows — one contiguous span of rpb * stride floats — is copied into LDS with lane-dense loads (dwordx4
+// from the first 16-byte boundary of the span on, single dwords before it and behind the last full quad: neither a
+// row nor a block starts aligned in general), and every output is produced by a loop over OUTPUT elements, lane j
+// element j, reading its source from LDS.  means / shs / opacities / scales are elementwise, so those loops are all
+// there is; rotations are one dwordx4 store per lane; the covariance (one quaternion -> 6 values per Gaussian) is
+// computed per Gaussian, staged in LDS and stored by such a loop as well.
+// LDS layout (floats): [pad: (address of the span / 4) % 4][rpb * stride rows][cov staging 6 * rpb].  The pad gives the
+// LDS copy the global span's 16-byte phase, so that the quad loads are stored as aligned quads.
+// (the loops below step by the workgroup size; without this the loop vectoriser adds a second copy of each for a
+// workgroup of one lane)
+#define PLY_NO_VECTORIZE _Pragma("clang loop vectorize(disable) interleave(disable)")
+constexpr int kPlyMaxThreads = 256;
+constexpr int kPlyLdsBytes = 64 * 1024 - 512;      // dynamic LDS a launch may ask for next to the offset table
+
+template <int K>
+__global__ __launch_bounds__(kPlyMaxThreads) void k_ply_unpack(lsr_ply_layout L, int rpb, int flags,
+                                                              const float *__restrict__ rows, lsr_ply_outputs out) {
+    extern __shared__ float4 ply_lds4[];
+    __shared__ int sh_off[3 * K];                        // row offset of shs[g][k][c] at [3 k + c]
+    float *const lds = reinterpret_cast<float *>(ply_lds4);
+    const int tid = threadIdx.x, nt = blockDim.x, stride = L.stride;
+    const int64_t g0 = (int64_t)blockIdx.x * rpb;
+    const int nr = (int)(L.n - g0 < (int64_t)rpb ? L.n - g0 : (int64_t)rpb);
+    const float *const src = rows + g0 * stride;
+    const int total = nr * stride;
+    const int phase = (int)((reinterpret_cast<uintptr_t>(src) >> 2) & 3);
+    float *const tile = lds + phase;
+    float *const stage = lds + 4 + rpb * stride;
+
+    for (int e = tid; e < 3 * K; e += nt) {
+        const int k = e / 3, c = e - 3 * k;
+        sh_off[e] = k == 0 ? (c == 0 ? L.f_dc[0] : (c == 1 ? L.f_dc[1] : L.f_dc[2])) : L.f_rest[c * (K - 1) + k - 1];
+    }
+    // the span into LDS
+    const int head = min((4 - phase) & 3, total);
+    const int nquad = (total - head) >> 2;
+    if (tid < head) tile[tid] = src[tid];
+    {
+        const float4 *const s4 = reinterpret_cast<const float4 *>(src + head);
+        float4 *const t4 = reinterpret_cast<float4 *>(tile + head);
+        for (int i = tid; i < nquad; i += nt) t4[i] = s4[i];
+    }
+    for (int i = head + 4 * nquad + tid; i < total; i += nt) tile[i] = src[i];
+    __syncthreads();
+
+    // one Gaussian per lane: quaternion, covariance
+    if (out.rotations || out.cov3D) {
+        for (int r = tid; r < nr; r += nt) {
+            const float *row = tile + r * stride;
+            float w = row[L.rot[0]], x = row[L.rot[1]], y = row[L.rot[2]], z = row[L.rot[3]];
+            const float inv = 1.0f / sqrtf(w * w + x * x + y * y + z * z);
+            w *= inv; x *= inv; y *= inv; z *= inv;
+            if (out.rotations) reinterpret_cast<float4 *>(out.rotations)[g0 + r] = make_float4(w, x, y, z);
+            if (out.cov3D) {
+                const float s0 = expf(row[L.scale[0]]), s1 = expf(row[L.scale[1]]), s2 = expf(row[L.scale[2]]);
+                // M = R diag(s); Sigma = M M^T
+                const float m00 = (1.0f - 2.0f * (y * y + z * z)) * s0, m01 = 2.0f * (x * y - w * z) * s1, m02 = 2.0f * (x * z + w * y) * s2;
+                const float m10 = 2.0f * (x * y + w * z) * s0, m11 = (1.0f - 2.0f * (x * x + z * z)) * s1, m12 = 2.0f * (y * z - w * x) * s2;
+                const float m20 = 2.0f * (x * z - w * y) * s0, m21 = 2.0f * (y * z + w * x) * s1, m22 = (1.0f - 2.0f * (x * x + y * y)) * s2;
+                float *st = stage + 6 * r;
+                st[0] = m00 * m00 + m01 * m01 + m02 * m02;
+                st[1] = m00 * m10 + m01 * m11 + m02 * m12;
+                st[2] = m00 * m20 + m01 * m21 + m02 * m22;
+                st[3] = m10 * m10 + m11 * m11 + m12 * m12;
+                st[4] = m10 * m20 + m11 * m21 + m12 * m22;
+                st[5] = m20 * m20 + m21 * m21 + m22 * m22;
+            }
+        }
+    }
+    if (out.means) {
+        float *dst = out.means + g0 * 3;
+        PLY_NO_VECTORIZE
+        for (int j = tid; j < 3 * nr; j += nt) {
+            const int r = j / 3, c = j - 3 * r;
+            dst[j] = tile[r * stride + (c == 0 ? L.xyz[0] : (c == 1 ? L.xyz[1] : L.xyz[2]))];
+        }
+    }
+    if (out.scales) {
+        float *dst = out.scales + g0 * 3;
+        PLY_NO_VECTORIZE
+        for (int j = tid; j < 3 * nr; j += nt) {
+            const int r = j / 3, c = j - 3 * r;
+            dst[j] = expf(tile[r * stride + (c == 0 ? L.scale[0] : (c == 1 ? L.scale[1] : L.scale[2]))]);
+        }
+    }
+    if (out.opacities) {
+        for (int r = tid; r < nr; r += nt) {
+            const float v = tile[r * stride + L.opacity];
+            out.opacities[g0 + r] = (flags & LSR_PLY_OPACITY_RAW) ? v : 1.0f / (1.0f + expf(-v));
+        }
+    }
+    if (out.shs) {
+        float *dst = out.shs + g0 * (3 * K);
+        PLY_NO_VECTORIZE
+        for (int j = tid; j < 3 * K * nr; j += nt) {
+            const int r = j / (3 * K), e = j - 3 * K * r;
+            dst[j] = tile[r * stride + sh_off[e]];
+        }
+    }
+    if (out.cov3D) {
+        __syncthreads();
+        float *dst = out.cov3D + g0 * 6;
+        PLY_NO_VECTORIZE
+        for (int j = tid; j < 6 * nr; j += nt) dst[j] = stage[j];
+    }
+}
+
+template <int K>
+static void launch_ply_unpack(const lsr_ply_layout &L, int rpb, int threads, size_t lds, int flags, const float *rows,
+                              const lsr_ply_outputs &out, hipStream_t s) {
+    const int64_t blocks = (L.n + rpb - 1) / rpb;
+    hipLaunchKernelGGL(k_ply_unpack<K>, dim3((unsigned)blocks), dim3(threads), lds, s, L, rpb, flags, rows, out);
+}
+
 }  // namespace lsr
 
 using namespace lsr;
@@ -92,6 +211,48 @@ int lsr_ply_pack(int64_t n, int32_t d_sh, const lsr_ply_inputs *in, float *verti
         return LSR_ENULL;
     if ((n + 255) / 256 > 0x7fffffffLL) return LSR_EUNSUPPORTED;
     hipLaunchKernelGGL(k_ply_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, d_sh, *in, vertices);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
+    return LSR_OK;
+}
+
+int lsr_ply_unpack(const lsr_ply_layout *layout, const float *rows, int32_t flags, const lsr_ply_outputs *out,
+                   lsr_stream_t stream) {
+    note_hip_error(0);
+    if (!layout || !out) return LSR_ENULL;
+    const lsr_ply_layout &L = *layout;
+    const int K = L.sh_coeffs;
+    if (L.n < 0 || L.stride < 1 || L.stride > LSR_PLY_MAX_STRIDE || (flags & ~LSR_PLY_OPACITY_RAW)) return LSR_EINVAL;
+    if (K != 1 && K != 4 && K != 9 && K != 16 && K != 25) return LSR_EINVAL;
+    // every offset the kernel may read lies inside the row (and with it inside the workgroup's LDS block)
+    const auto inside = [&](const int32_t *o, int count) {
+        for (int k = 0; k < count; ++k)
+            if (o[k] < 0 || o[k] >= L.stride) return false;
+        return true;
+    };
+    if (!inside(L.xyz, 3) || !inside(L.f_dc, 3) || !inside(&L.opacity, 1) || !inside(L.scale, 3) || !inside(L.rot, 4) ||
+        !inside(L.f_rest, 3 * (K - 1)))
+        return LSR_EINVAL;
+    if (L.n == 0) return LSR_OK;
+    if (!rows) return LSR_ENULL;
+    if ((reinterpret_cast<uintptr_t>(rows) & 3) || (reinterpret_cast<uintptr_t>(out->rotations) & 15)) return LSR_EINVAL;
+    // rows per workgroup: 128 (LSR_PLY_UNPACK_ROWS, a development knob, takes any 1 ... 256; multiples of 64 are what
+    // tools/bench_ply_import.py --rows compares: DESIGN.md section 2.8), or as many as the LDS budget holds
+    const int per_row = (L.stride + 6) * (int)sizeof(float);
+    int rpb = std::min(std::max(env_int("LSR_PLY_UNPACK_ROWS", 128), 1), kPlyMaxThreads);
+    rpb = std::min(rpb, (kPlyLdsBytes - 16) / per_row);
+    if (rpb >= 64) rpb &= ~63;
+    const int threads = std::min(kPlyMaxThreads, (rpb + 63) & ~63);
+    const size_t lds = 16 + (size_t)rpb * per_row;
+    if ((L.n + rpb - 1) / rpb > 0x7fffffffLL) return LSR_EUNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    switch (K) {
+        case 1: launch_ply_unpack<1>(L, rpb, threads, lds, flags, rows, *out, s); break;
+        case 4: launch_ply_unpack<4>(L, rpb, threads, lds, flags, rows, *out, s); break;
+        case 9: launch_ply_unpack<9>(L, rpb, threads, lds, flags, rows, *out, s); break;
+        case 16: launch_ply_unpack<16>(L, rpb, threads, lds, flags, rows, *out, s); break;
+        default: launch_ply_unpack<25>(L, rpb, threads, lds, flags, rows, *out, s); break;
+    }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
     return LSR_OK;
