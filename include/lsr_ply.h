@@ -112,6 +112,68 @@ typedef struct lsr_ply_outputs {  /* device; every pointer is optional (NULL = n
 int lsr_ply_unpack(const lsr_ply_layout *layout, const float *rows, int32_t flags, const lsr_ply_outputs *out,
                    lsr_stream_t stream);
 
+/*
+ * ---- scene export: the rasterizer's tensors back to a standard 3DGS scene file ----
+ *
+ * The inverse of the import: lsr_ply_pack_scene builds the row table of the published layout on the device — every SH
+ * band, the opacity as a logit, log-scales and a quaternion taken from the covariance — and lsr_ply_write_scene_host
+ * writes it.  Unlike lsr_ply_pack (a viewer's copy: recentred, rescaled, rotated, DC band only) nothing about the
+ * scene is changed: lsr_ply_read_* / lsr_ply_unpack give it back.
+ */
+#define LSR_PLY_SCENE_ROW_FLOATS(K) (14 + 3 * (K))   /* x y z nx ny nz f_dc_0..2 f_rest_0..3(K-1)-1 opacity scale_0..2 rot_0..3 */
+
+typedef struct lsr_ply_scene_inputs {   /* device */
+    const float *means;       /* [n][3] */
+    const float *opacities;   /* [n] probabilities */
+    const float *shs;         /* colour SH: [n][sh_coeffs][3], or [n][3][sh_coeffs] with sh_channel_major */
+    const float *cov;         /* [n][cov_elems]: 6 = xx,xy,xz,yy,yz,zz; 9 = row-major 3x3 whose upper triangle is read (that
+                                 IS the symmetrised input).  NULL: scales and rotations are given instead */
+    const float *scales;      /* [n][3]; used (with rotations) only when cov is NULL */
+    const float *rotations;   /* [n][4] w,x,y,z, any non-zero norm */
+    int32_t sh_coeffs;        /* K_in in {1,4,9,16,25} */
+    int32_t sh_channel_major; /* 0 or 1 */
+    int32_t cov_elems;        /* 6 or 9 (ignored when cov is NULL) */
+    int32_t reserved0;        /* 0 */
+} lsr_ply_scene_inputs;
+
+typedef struct lsr_ply_scene_opts {
+    int32_t sh_convention;    /* basis the caller's shs are in: LSR_SH_AXES_3DGS or LSR_SH_AXES_REFERENCE */
+    int32_t sh_coeffs_out;    /* K_out in {1,4,9,16,25}, <= K_in: the lower bands are kept */
+    int32_t reserved0, reserved1;   /* 0 */
+} lsr_ply_scene_opts;
+
+/* rows[n][14 + 3 K_out] on the device, in the published property order (above).  Device to device, asynchronous;
+ * n == 0 launches nothing.  Every row has one owner and nothing is accumulated: two calls give the same bits.
+ *   x y z      means, bit for bit.  nx ny nz: 0.0f.
+ *   opacity    log(p / (1 - p)) clamped to [-20, 20]: always finite for p in [0, 1] (p = 1 loads back as 1.0f, p = 0
+ *              as 2e-9); NaN in gives NaN out, and so does p outside [0, 1].
+ *   f_dc, f_rest   LSR_SH_AXES_3DGS: a pure re-layout, bit for bit: f_dc_c = shs[g][0][c],
+ *              f_rest_{c (K_out - 1) + k} = shs[g][1 + k][c].  LSR_SH_AXES_REFERENCE: per band c' = M_l c first (the
+ *              matrix of lsr_ply_sh_axes_matrix, rounded to float), so that the file renders under the 3dgs basis what
+ *              the input renders under the reference's.
+ *   scale, rot from cov: eigenvalues lambda_k and orthonormal eigenvectors (float32 cyclic Jacobi, fixed sweeps);
+ *              lambda_k <- max(lambda_k, 1e-12 lambda_max, 1e-37), scale_k = 0.5 log lambda_k in DESCENDING order; the
+ *              eigenvector matrix has its last column flipped where needed so that det = +1, and rot is its unit
+ *              quaternion w,x,y,z with w >= 0.  R S^2 R^T rebuilt from the row is within 1e-5 of the largest |cov| entry.
+ *              From scales / rotations: log(scale_k) in the caller's order and the caller's quaternion normalised,
+ *              negated where w < 0.
+ * `rows` and the inputs need float alignment only.
+ * LSR_EINVAL: n < 0, K_in or K_out not one of the five, K_out > K_in, an unknown convention, sh_channel_major not 0 / 1,
+ * cov_elems not 6 / 9 with cov given, a non-zero reserved field.  LSR_ENULL: a NULL struct, means, opacities, shs or
+ * rows, or neither cov nor both of scales and rotations (n > 0). */
+int lsr_ply_pack_scene(int64_t n, const lsr_ply_scene_inputs *in, const lsr_ply_scene_opts *opts, float *rows,
+                       lsr_stream_t stream);
+
+/* The change of basis as one 25 x 25 row-major matrix M, out[25 * i + j]: c' = M c.  Block diagonal (band l in rows and
+ * columns l^2 .. (l+1)^2 - 1, exact zeros elsewhere) and orthogonal; with Y the basis of the kernels,
+ * Y(d) . M = Y(d_z, d_x, d_y) for every unit d.  Host only. */
+int lsr_ply_sh_axes_matrix(double *out);
+
+/* Write rows_host[n][14 + 3 sh_coeffs] (HOST memory) as a binary little-endian scene file: the header plyfile emits for
+ * those float properties, then the rows.  sh_coeffs not in {1,4,9,16,25} or n < 0: LSR_EINVAL; LSR_EINVAL as well if the
+ * file cannot be created or fully written. */
+int lsr_ply_write_scene_host(const char *path, const float *rows_host, int64_t n, int32_t sh_coeffs);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,8 @@ __version__ = "0.1.0"
 
 _LAZY = {"rotate_sh": "sh_rotate", "GaussianAdapter": "gaussian_adapter", "GaussianAdapterCfg": "gaussian_adapter",
          "Gaussians": "gaussian_adapter", "DepthPredictorMonocular": "depth_head", "opacity_exponent": "depth_head",
-         "Scene3DGS": "ply_import", "load_ply": "ply_import", "unpack_vertices": "ply_import"}
+         "Scene3DGS": "ply_import", "load_ply": "ply_import", "unpack_vertices": "ply_import",
+         "pack_scene": "ply_export", "save_ply": "ply_export", "save_gaussians": "ply_export"}
 
 
 def __getattr__(name):     # torch is imported only when one of these is first used

@@ -133,6 +133,20 @@ class PlyOutputs(C.Structure):       # lsr_ply_outputs
     _fields_ = [(n, C.c_void_p) for n in ("means", "shs", "opacities", "scales", "rotations", "cov3D")]
 
 
+class PlySceneInputs(C.Structure):   # lsr_ply_scene_inputs
+    _fields_ = [(n, C.c_void_p) for n in ("means", "opacities", "shs", "cov", "scales", "rotations")] + \
+               [(n, C.c_int32) for n in ("sh_coeffs", "sh_channel_major", "cov_elems", "reserved0")]
+
+
+class PlySceneOpts(C.Structure):     # lsr_ply_scene_opts
+    _fields_ = [(n, C.c_int32) for n in ("sh_convention", "sh_coeffs_out", "reserved0", "reserved1")]
+
+
+def ply_scene_row_floats(sh_coeffs: int) -> int:
+    """LSR_PLY_SCENE_ROW_FLOATS."""
+    return 14 + 3 * sh_coeffs
+
+
 class ShRotateDims(C.Structure):     # lsr_sh_rotate_dims (include/lsr_sh_rotate.h)
     _fields_ = [("num_cameras", C.c_int32), ("rays", C.c_int32), ("samples", C.c_int32),
                 ("color_coeffs", C.c_int32), ("feat_channels", C.c_int32), ("feat_coeffs", C.c_int32),
@@ -167,6 +181,7 @@ EXPORTS = (
     "lsr_debug_set_knob", "lsr_set_projection_contraction", "lsr_get_projection_contraction",
     "lsr_adapter_forward", "lsr_adapter_backward", "lsr_latent_forward", "lsr_latent_backward",
     "lsr_ply_pack", "lsr_ply_write_host", "lsr_ply_read_header", "lsr_ply_read_rows", "lsr_ply_unpack",
+    "lsr_ply_pack_scene", "lsr_ply_sh_axes_matrix", "lsr_ply_write_scene_host",
     "lsr_sh_rotation_matrices", "lsr_sh_rotate_forward", "lsr_sh_rotate_backward",
     "lsr_depth_head_forward", "lsr_depth_head_backward",
 )
@@ -283,6 +298,12 @@ def load():
     lib.lsr_ply_read_rows.argtypes = [C.c_char_p, P, I64]
     lib.lsr_ply_unpack.restype = C.c_int
     lib.lsr_ply_unpack.argtypes = [C.POINTER(PlyLayout), P, I32, C.POINTER(PlyOutputs), P]
+    lib.lsr_ply_pack_scene.restype = C.c_int
+    lib.lsr_ply_pack_scene.argtypes = [I64, C.POINTER(PlySceneInputs), C.POINTER(PlySceneOpts), P, P]
+    lib.lsr_ply_sh_axes_matrix.restype = C.c_int
+    lib.lsr_ply_sh_axes_matrix.argtypes = [P]
+    lib.lsr_ply_write_scene_host.restype = C.c_int
+    lib.lsr_ply_write_scene_host.argtypes = [C.c_char_p, P, I64, I32]
     lib.lsr_sh_rotation_matrices.restype = C.c_int
     lib.lsr_sh_rotation_matrices.argtypes = [I32, P, I64, I64, I32, P, P]
     lib.lsr_sh_rotate_forward.restype = C.c_int

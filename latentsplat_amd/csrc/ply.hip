@@ -7,8 +7,11 @@
 
 #include <algorithm>
 
+#include "lsr_eig3.h"
 #include "lsr_internal.h"
 #include "lsr_ply.h"
+#define LSR_SH_AXES_TABLE_QUALIFIER __device__
+#include "lsr_sh_axes_table.h"
 
 namespace lsr {
 
@@ -195,6 +198,165 @@ static void launch_ply_unpack(const lsr_ply_layout &L, int rpb, int threads, siz
     hipLaunchKernelGGL(k_ply_unpack<K>, dim3((unsigned)blocks), dim3(threads), lds, s, L, rpb, flags, rows, out);
 }
 
+
+// ---- scene export: the rasterizer's tensors -> rows of a standard 3DGS scene file (lsr_ply_pack_scene) ----
+// The unpack run backwards.  A workgroup owns `rpb` consecutive Gaussians; their rows are one contiguous span of
+// rpb * STRIDE floats of the output table, which is assembled in LDS and leaves with lane-dense dwordx4 stores (single
+// dwords up to the span's first 16-byte boundary and behind its last full quad; the LDS image has the span's 16-byte
+// phase).  Every input is read by a loop over INPUT elements, lane j element j, and scattered into the image; the
+// covariances (or scales and rotations) are staged in LDS the same way and then decomposed one Gaussian per lane
+// (lsr_eig3.h: 6 + 9 floats in registers).  Colour SH is first re-laid out as it is — for LSR_SH_AXES_3DGS that is all,
+// bit for bit — and for LSR_SH_AXES_REFERENCE each (Gaussian, channel) lane then multiplies its bands by M_l in place,
+// M as floats in LDS (every lane reads the same entry: a broadcast).  Band 0 is left alone: M_0 rounds to 1.0f.
+// LDS layout (floats): [pad: (address of the span / 4) % 4][rpb * STRIDE image][geometry staging 9 * rpb] + the table.
+// No atomics; one owner per row.
+constexpr int kPlyPackRows = 128;                    // 128 * (89 + 9) floats = 49 KiB at degree 4
+
+constexpr int sh_degree_of(int K) { return K == 1 ? 0 : K == 4 ? 1 : K == 9 ? 2 : K == 16 ? 3 : 4; }
+constexpr int sh_axes_table_floats(int deg) { return (deg + 1) * (2 * deg + 1) * (2 * deg + 3) / 3; }
+
+// f[0 .. 2L] <- M_L f, M row-major in LDS
+template <int L>
+__device__ __forceinline__ void sh_axes_band(float *f, const float *M) {
+    constexpr int N = 2 * L + 1;
+    float v[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) v[j] = f[j];
+#pragma unroll 1                                         // (unrolled, band 4 holds its 81 entries in registers: 225 VGPRs)
+    for (int i = 0; i < N; ++i) {
+        float acc = 0.0f;
+#pragma unroll
+        for (int j = 0; j < N; ++j) acc = fmaf(M[N * i + j], v[j], acc);
+        f[i] = acc;
+    }
+}
+
+template <int K>
+__global__ __launch_bounds__(kPlyMaxThreads) void k_ply_pack_scene(int64_t n, int rpb, int reference, lsr_ply_scene_inputs in,
+                                                                  float *__restrict__ rows) {
+    constexpr int STRIDE = LSR_PLY_SCENE_ROW_FLOATS(K), OPA = 6 + 3 * K, DEG = sh_degree_of(K);
+    constexpr int TABLE = sh_axes_table_floats(DEG);
+    extern __shared__ float4 ply_lds4[];
+    __shared__ float shM[TABLE];
+    float *const lds = reinterpret_cast<float *>(ply_lds4);
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int64_t g0 = (int64_t)blockIdx.x * rpb;
+    const int nr = (int)(n - g0 < (int64_t)rpb ? n - g0 : (int64_t)rpb);
+    float *const dst = rows + g0 * STRIDE;
+    const int total = nr * STRIDE;
+    const int phase = (int)((reinterpret_cast<uintptr_t>(dst) >> 2) & 3);
+    float *const tile = lds + phase;
+    float *const geo = lds + 4 + rpb * STRIDE;
+    const int Kin = in.sh_coeffs, ce = in.cov_elems;
+    const bool basis_change = reference && K > 1;
+
+    // geometry inputs into the staging area, lane-dense
+    if (in.cov) {
+        const float *src = in.cov + g0 * ce;
+        PLY_NO_VECTORIZE
+        for (int j = tid; j < ce * nr; j += nt) geo[j] = src[j];
+    } else {
+        const float *ss = in.scales + g0 * 3, *sq = in.rotations + g0 * 4;
+        PLY_NO_VECTORIZE
+        for (int j = tid; j < 3 * nr; j += nt) geo[j] = ss[j];
+        PLY_NO_VECTORIZE
+        for (int j = tid; j < 4 * nr; j += nt) geo[3 * rpb + j] = sq[j];
+    }
+    if (basis_change)
+        for (int i = tid; i < TABLE; i += nt) shM[i] = (float)kShAxesM[i];
+    {   // means, normals
+        const float *src = in.means + g0 * 3;
+        PLY_NO_VECTORIZE
+        for (int j = tid; j < 3 * nr; j += nt) {
+            const int r = j / 3, c = j - 3 * r;
+            tile[r * STRIDE + c] = src[j];
+            tile[r * STRIDE + 3 + c] = 0.0f;
+        }
+    }
+    for (int r = tid; r < nr; r += nt) {                     // opacity -> logit in [-20, 20]; a NaN passes through
+        const float p = in.opacities[g0 + r];
+        const float v = logf(p / (1.0f - p));
+        tile[r * STRIDE + OPA] = v < -20.0f ? -20.0f : (v > 20.0f ? 20.0f : v);
+    }
+    {   // colour SH: shs[g][k][c] (or [g][c][k]) -> f_dc_c, f_rest_{c (K - 1) + k - 1}; coefficients k >= K are dropped
+        const float *src = in.shs + g0 * 3 * Kin;
+        if (in.sh_channel_major) {
+            PLY_NO_VECTORIZE
+            for (int j = tid; j < 3 * K * nr; j += nt) {
+                const int r = j / (3 * K), e = j - 3 * K * r, c = e / K, k = e - K * c;
+                tile[r * STRIDE + (k == 0 ? 6 + c : 8 + c * (K - 1) + k)] = src[r * 3 * Kin + c * Kin + k];
+            }
+        } else {
+            PLY_NO_VECTORIZE
+            for (int j = tid; j < 3 * K * nr; j += nt) {
+                const int r = j / (3 * K), e = j - 3 * K * r, k = e / 3, c = e - 3 * k;
+                tile[r * STRIDE + (k == 0 ? 6 + c : 8 + c * (K - 1) + k)] = src[r * 3 * Kin + e];
+            }
+        }
+    }
+    __syncthreads();
+
+    // one Gaussian per lane: log-scales and the quaternion
+    for (int r = tid; r < nr; r += nt) {
+        float ls[3], q[4];
+        if (in.cov) {
+            const float *c = geo + r * ce;
+            float c6[6];
+            if (ce == 6) {
+#pragma unroll
+                for (int k = 0; k < 6; ++k) c6[k] = c[k];
+            } else {
+                c6[0] = c[0]; c6[1] = c[1]; c6[2] = c[2]; c6[3] = c[4]; c6[4] = c[5]; c6[5] = c[8];
+            }
+            eig3_scale_rotation(c6, ls, q);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) ls[k] = logf(geo[3 * r + k]);
+            const float *qs = geo + 3 * rpb + 4 * r;
+            const float w = qs[0], x = qs[1], y = qs[2], z = qs[3];
+            float inv = 1.0f / sqrtf(w * w + x * x + y * y + z * z);
+            if (w < 0.0f) inv = -inv;
+            q[0] = w * inv; q[1] = x * inv; q[2] = y * inv; q[3] = z * inv;
+        }
+        float *o = tile + r * STRIDE + OPA + 1;
+        o[0] = ls[0]; o[1] = ls[1]; o[2] = ls[2];
+        o[3] = q[0]; o[4] = q[1]; o[5] = q[2]; o[6] = q[3];
+    }
+    // reference -> 3dgs basis, in place: one (Gaussian, channel) per lane
+    if (basis_change) {
+        for (int j = tid; j < 3 * nr; j += nt) {
+            const int r = j / 3, c = j - 3 * r;
+            float *f = tile + r * STRIDE + 9 + c * (K - 1);     // f[k - 1]: coefficient k of this channel
+            if constexpr (DEG >= 1) sh_axes_band<1>(f, shM + sh_axes_table_floats(0));
+            if constexpr (DEG >= 2) sh_axes_band<2>(f + 3, shM + sh_axes_table_floats(1));
+            if constexpr (DEG >= 3) sh_axes_band<3>(f + 8, shM + sh_axes_table_floats(2));
+            if constexpr (DEG >= 4) sh_axes_band<4>(f + 15, shM + sh_axes_table_floats(3));
+        }
+    }
+    __syncthreads();
+
+    // the image out
+    const int head = min((4 - phase) & 3, total);
+    const int nquad = (total - head) >> 2;
+    if (tid < head) dst[tid] = tile[tid];
+    {
+        float4 *const d4 = reinterpret_cast<float4 *>(dst + head);
+        const float4 *const t4 = reinterpret_cast<const float4 *>(tile + head);
+        for (int i = tid; i < nquad; i += nt) d4[i] = t4[i];
+    }
+    for (int i = head + 4 * nquad + tid; i < total; i += nt) dst[i] = tile[i];
+}
+
+template <int K>
+static void launch_ply_pack_scene(int64_t n, int reference, const lsr_ply_scene_inputs &in, float *rows, hipStream_t s) {
+    const int rpb = kPlyPackRows;
+    const size_t lds = sizeof(float) * (4 + (size_t)rpb * (LSR_PLY_SCENE_ROW_FLOATS(K) + 9));
+    static_assert(sizeof(float) * (4 + (size_t)kPlyPackRows * (LSR_PLY_SCENE_ROW_FLOATS(K) + 9)) + 165 * sizeof(float) <= 64 * 1024,
+                  "a block of rows, its geometry staging and the table fit the per-workgroup LDS");
+    hipLaunchKernelGGL(k_ply_pack_scene<K>, dim3((unsigned)((n + rpb - 1) / rpb)), dim3(kPlyMaxThreads), lds, s, n, rpb,
+                       reference, in, rows);
+}
+
 }  // namespace lsr
 
 using namespace lsr;
@@ -252,6 +414,39 @@ int lsr_ply_unpack(const lsr_ply_layout *layout, const float *rows, int32_t flag
         case 9: launch_ply_unpack<9>(L, rpb, threads, lds, flags, rows, *out, s); break;
         case 16: launch_ply_unpack<16>(L, rpb, threads, lds, flags, rows, *out, s); break;
         default: launch_ply_unpack<25>(L, rpb, threads, lds, flags, rows, *out, s); break;
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
+    return LSR_OK;
+}
+
+int lsr_ply_pack_scene(int64_t n, const lsr_ply_scene_inputs *in, const lsr_ply_scene_opts *opts, float *rows,
+                       lsr_stream_t stream) {
+    note_hip_error(0);
+    if (!in || !opts) return LSR_ENULL;
+    const auto is_K = [](int K) { return K == 1 || K == 4 || K == 9 || K == 16 || K == 25; };
+    const int K = opts->sh_coeffs_out;
+    if (n < 0 || !is_K(in->sh_coeffs) || !is_K(K) || K > in->sh_coeffs) return LSR_EINVAL;
+    if (opts->sh_convention != LSR_SH_AXES_3DGS && opts->sh_convention != LSR_SH_AXES_REFERENCE) return LSR_EINVAL;
+    if ((in->sh_channel_major & ~1) || in->reserved0 || opts->reserved0 || opts->reserved1) return LSR_EINVAL;
+    if (in->cov && in->cov_elems != 6 && in->cov_elems != 9) return LSR_EINVAL;
+    if (n == 0) return LSR_OK;
+    if (!in->means || !in->opacities || !in->shs || !rows) return LSR_ENULL;
+    if (!in->cov && (!in->scales || !in->rotations)) return LSR_ENULL;
+    const uintptr_t align = reinterpret_cast<uintptr_t>(in->means) | reinterpret_cast<uintptr_t>(in->opacities) |
+                            reinterpret_cast<uintptr_t>(in->shs) | reinterpret_cast<uintptr_t>(in->cov) |
+                            reinterpret_cast<uintptr_t>(in->scales) | reinterpret_cast<uintptr_t>(in->rotations) |
+                            reinterpret_cast<uintptr_t>(rows);
+    if (align & 3) return LSR_EINVAL;
+    if ((n + kPlyPackRows - 1) / kPlyPackRows > 0x7fffffffLL) return LSR_EUNSUPPORTED;
+    const int reference = opts->sh_convention == LSR_SH_AXES_REFERENCE;
+    hipStream_t s = (hipStream_t)stream;
+    switch (K) {
+        case 1: launch_ply_pack_scene<1>(n, reference, *in, rows, s); break;
+        case 4: launch_ply_pack_scene<4>(n, reference, *in, rows, s); break;
+        case 9: launch_ply_pack_scene<9>(n, reference, *in, rows, s); break;
+        case 16: launch_ply_pack_scene<16>(n, reference, *in, rows, s); break;
+        default: launch_ply_pack_scene<25>(n, reference, *in, rows, s); break;
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }

@@ -1,4 +1,8 @@
-"""3DGS ``.ply`` export — mirror of /root/reference/src/model/ply_export.py (``export_ply`` :26-92,
+"""3DGS ``.ply`` export.  Two writers: ``export_ply``, the mirror of the reference's (a viewer's copy: recentred, rescaled,
+rotated, DC band only), and ``save_ply`` / ``save_gaussians`` / ``pack_scene`` further down, which keep the scene (every SH
+band, logit opacities, scales and rotations taken from the covariances) in the published layout that ``load_ply`` reads.
+
+``export_ply`` — mirror of /root/reference/src/model/ply_export.py (``export_ply`` :26-92,
 ``construct_list_of_attributes`` :13-23) on the MI355X: the per-Gaussian transform and the 17-float
 vertex packing run as one HIP kernel (csrc/ply.hip, C ABI include/lsr_ply.h), the file is written
 by the library's host writer.  ROCm float32 tensors only; no CPU fallback."""
@@ -7,6 +11,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 from pathlib import Path
+from typing import Optional
 
 import torch
 from torch import Tensor
@@ -53,3 +58,96 @@ def export_ply(extrinsics: Tensor, means: Tensor, scales: Tensor, rotations: Ten
     path.parent.mkdir(exist_ok=True, parents=True)
     _lib.check(_lib.load().lsr_ply_write_host(os.fsencode(str(path)), C.c_void_p(vertices.data_ptr()),
                                               vertices.shape[0]), "lsr_ply_write_host")
+
+
+# ---- scene export: a standard 3DGS scene file that keeps the scene (every SH band, logit opacities, geometry taken from
+# the covariances), the inverse of latentsplat_amd.ply_import.  C ABI: include/lsr_ply.h, "scene export". ----
+
+_CONVENTIONS = {"3dgs": _lib.SH_AXES_3DGS, "reference": _lib.SH_AXES_REFERENCE}
+
+
+def pack_scene(means: Tensor, opacities: Tensor, shs: Tensor, *, covariances: Optional[Tensor] = None,
+               scales: Optional[Tensor] = None, rotations: Optional[Tensor] = None, convention: Optional[str] = None,
+               channel_major: Optional[bool] = None, max_sh_degree: Optional[int] = None) -> Tensor:
+    """``(n, 14 + 3 K_out)`` float32 rows on the device in the order of ``construct_list_of_attributes(3 (K_out - 1))``
+    (``lsr_ply_pack_scene``: one HIP kernel).
+
+    Geometry is exactly one of ``covariances`` (``(n, 6)`` xx,xy,xz,yy,yz,zz or ``(n, 3, 3)``: decomposed on the device
+    into log-scales and a quaternion) or ``scales (n, 3)`` with ``rotations (n, 4)`` w,x,y,z.  ``shs`` is ``(n, K, 3)`` or,
+    channel-major, ``(n, 3, K)``; ``channel_major=None`` reads the layout off the shape.  ``convention`` is the basis the
+    coefficients are in (``None``: the one this process renders with, ``get_color_sh_convention()``); ``"reference"``
+    coefficients are changed to the ``"3dgs"`` basis the file format means.  ``max_sh_degree`` keeps the lower bands."""
+    if (covariances is None) == (scales is None and rotations is None) or (scales is None) != (rotations is None):
+        raise _lib.LsrError("pack_scene takes exactly one of covariances=, or scales= with rotations=")
+    if shs.dim() != 3:
+        raise _lib.LsrError(f"shs must be (n, K, 3) or (n, 3, K), got {tuple(shs.shape)}")
+    if channel_major is None:
+        if shs.shape[1] == 3 and shs.shape[2] == 3:
+            raise _lib.LsrError("shs of shape (n, 3, 3) is ambiguous: say channel_major=True for (n, 3, K) or False for (n, K, 3)")
+        if shs.shape[1] != 3 and shs.shape[2] != 3:
+            raise _lib.LsrError(f"shs must be (n, K, 3) or (n, 3, K), got {tuple(shs.shape)}")
+        channel_major = shs.shape[2] != 3
+    if shs.shape[1 if channel_major else 2] != 3:
+        raise _lib.LsrError(f"shs must be {'(n, 3, K)' if channel_major else '(n, K, 3)'}, got {tuple(shs.shape)}")
+    K_in = shs.shape[2 if channel_major else 1]
+    if K_in not in (1, 4, 9, 16, 25):
+        raise _lib.LsrError(f"{K_in} SH coefficients per channel: expected 1, 4, 9, 16 or 25")
+    K_out = K_in if max_sh_degree is None else min(K_in, (int(max_sh_degree) + 1) ** 2)
+    if max_sh_degree is not None and max_sh_degree < 0:
+        raise _lib.LsrError("max_sh_degree must be >= 0")
+    if convention is None:
+        from .rasterizer import get_color_sh_convention
+        convention = get_color_sh_convention()
+    if convention not in _CONVENTIONS:
+        raise _lib.LsrError(f"convention must be '3dgs' or 'reference', got {convention!r}")
+    given = [t for t in (means, opacities, shs, covariances, scales, rotations) if t is not None]
+    for t in given:
+        if not t.is_cuda or t.dtype != torch.float32:
+            raise _lib.LsrError("pack_scene needs float32 ROCm tensors (no CPU fallback)")
+    n, dev = means.shape[0], means.device
+    c = lambda t: None if t is None else t.detach().contiguous()
+    means, opacities, shs, scales, rotations = c(means), c(opacities).reshape(-1), c(shs), c(scales), c(rotations)
+    cov_elems = 0
+    if covariances is not None:
+        if tuple(covariances.shape) not in ((n, 6), (n, 3, 3)):
+            raise _lib.LsrError(f"covariances must be (n, 6) or (n, 3, 3), got {tuple(covariances.shape)}")
+        covariances = c(covariances)
+        cov_elems = 6 if covariances.dim() == 2 else 9
+    elif tuple(scales.shape) != (n, 3) or tuple(rotations.shape) != (n, 4):
+        raise _lib.LsrError("scales must be (n, 3) and rotations (n, 4)")
+    if tuple(means.shape) != (n, 3) or opacities.shape[0] != n or shs.shape[0] != n:
+        raise _lib.LsrError("means must be (n, 3), opacities (n,) or (n, 1), shs n Gaussians")
+    lib = _lib.load()
+    rows = torch.empty((n, _lib.ply_scene_row_floats(K_out)), dtype=torch.float32, device=dev)
+    p = lambda t: C.c_void_p(None if t is None else t.data_ptr())
+    inp = _lib.PlySceneInputs(p(means), p(opacities), p(shs), p(covariances), p(scales), p(rotations), K_in,
+                              int(bool(channel_major)), cov_elems, 0)
+    opts = _lib.PlySceneOpts(_CONVENTIONS[convention], K_out, 0, 0)
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.lsr_ply_pack_scene(n, C.byref(inp), C.byref(opts), p(rows), stream), "lsr_ply_pack_scene")
+    return rows
+
+
+def save_ply(path, means: Tensor, opacities: Tensor, shs: Tensor, **opts) -> None:
+    """Write a standard 3DGS scene file (binary little-endian, the published ``point_cloud.ply`` layout) that
+    :func:`latentsplat_amd.ply_import.load_ply` and standard viewers read.  Arguments as :func:`pack_scene`."""
+    rows = pack_scene(means, opacities, shs, **opts)
+    host = torch.empty(rows.shape, dtype=torch.float32, pin_memory=True)
+    host.copy_(rows)                                    # (device to pinned host: synchronises with the packing stream)
+    path = Path(path)
+    path.parent.mkdir(exist_ok=True, parents=True)
+    K = (rows.shape[1] - 14) // 3
+    _lib.check(_lib.load().lsr_ply_write_scene_host(os.fsencode(str(path)), C.c_void_p(host.data_ptr()), rows.shape[0], K),
+               "lsr_ply_write_scene_host")
+
+
+def save_gaussians(path, gaussians, scene: int = 0, **opts) -> None:
+    """One scene of the decoder's ``Gaussians`` / ``VariationalGaussians`` (``means (b, g, 3)``, ``covariances
+    (b, g, 3, 3)``, ``opacities (b, g)``, ``color_harmonics (b, g, 3, K)``) as a scene file."""
+    if gaussians.color_harmonics is None:
+        raise _lib.LsrError("save_gaussians needs color_harmonics: a scene file stores colour SH (feature harmonics have no "
+                            "standard representation)")
+    opts.setdefault("channel_major", True)
+    save_ply(path, gaussians.means[scene], gaussians.opacities[scene], gaussians.color_harmonics[scene],
+             covariances=gaussians.covariances[scene], **opts)
