@@ -126,7 +126,6 @@ struct SegOut {            // kernel argument of the projection kernels
     uint64_t *keys;        // [V*T][cap] (nullptr: two-phase binning)
     uint32_t cap;
     uint32_t key_shift;    // IndexPacking::key_shift
-    uint32_t ablate;       // LSR_SEG_ABLATE (timing experiments only, wrong results): 1 no key stores, 2 no emission pass
 };
 
 inline GeomLayout geom_layout(const lsr_dims &d) {

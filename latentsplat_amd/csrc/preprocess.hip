@@ -10,8 +10,8 @@
 
 #include "lsr_blend.h"
 #include "lsr_depth.h"
+#include "lsr_key_emit.h"
 #include "lsr_project.h"
-#include "lsr_tile_scan.h"
 
 namespace lsr {
 
@@ -128,8 +128,6 @@ k_preprocess(lsr_dims d, lsr_inputs in, float *__restrict__ rec, int RF, char *_
             const float focal_x = s_focal[vb].x, focal_y = s_focal[vb].y;   // = width / (2 tan), height / (2 tan)
             const float limx = 1.3f * tanfovx, limy = 1.3f * tanfovy;
             const float scale = vw[40], scale2 = scale * scale;   // scene scale (1/near), applied like the reference does
-            uint32_t *tc = tile_count + (size_t)v * T;
-            uint32_t *hist = s_hist + vb * T;
             const size_t o = (size_t)v * G + ii;
             const float p0 = q0 * scale, p1 = q1 * scale, p2 = q2 * scale;
             const float s0 = r0 * scale2, s1 = r1 * scale2, s2 = r2 * scale2;
@@ -139,7 +137,7 @@ k_preprocess(lsr_dims d, lsr_inputs in, float *__restrict__ rec, int RF, char *_
             const bool ok = pj.ok;
             const float px = pj.px, py = pj.py, conic_a = pj.conic_a, conic_b = pj.conic_b, conic_c = pj.conic_c, tz = pj.tz;
             const float my_radius = pj.radius;
-            const int rminx = pj.rminx, rminy = pj.rminy, rmaxx = pj.rmaxx, rmaxy = pj.rmaxy;
+            const TileRect rect{pj.rminx, pj.rminy, pj.rmaxx, pj.rmaxy};
 
             // slot 6, what the compositing kernels blend into the depth image: the view z, or the view's depth mode applied
             // to it (lsr_depth.h; the mode is uniform: a scalar branch, not taken by tables without a mode).  The bin
@@ -149,39 +147,18 @@ k_preprocess(lsr_dims d, lsr_inputs in, float *__restrict__ rec, int RF, char *_
             const float4 rr0 = make_float4(px, py, conic_a, conic_b);
             const float4 rr1 = make_float4(conic_c, opacity, ok ? zpay : -1.0f, 0.0f);   // a negative slot 6 marks a culled record (staging only)
             // footprint span for the half-tile render lists (k_scatter / k_sort_tiles); not part of the bit-exact contract
-            const uint32_t span = ok ? footprint_cells(px, py, conic_a, conic_b, conic_c, opacity, rminx, rminy) : kSpanNone;
+            const uint32_t span = ok ? footprint_cells(px, py, conic_a, conic_b, conic_c, opacity, rect.x0, rect.y0) : kSpanNone;
             if (ok) {
                 if (!staged) {
                     float4 *R = (float4 *)(rec + o * (size_t)RF);
                     R[0] = rr0; R[1] = rr1;
                     for (int c4 = 0; c4 < (RF - 8) / 4; ++c4) R[2 + c4] = payload(c4);
                 }
-                // per-tile pair counts (also the compositing kernels' scheduling key: a finer work
-                // estimate — quadrants reached per entry — was measured to schedule no better)
-                // (LSR_FWD_REACHED_ONLY: only the tiles of the rectangle the footprint box reaches are pairs)
-                int hx0 = rminx, hy0 = rminy, hx1 = rmaxx, hy1 = rmaxy;
-                if (skip_none) reached_rect(span, hx0, hy0, hx1, hy1);
-                for (int y = hy0; y < hy1; ++y)
-                    for (int x = hx0; x < hx1; ++x) {
-                        if (LDS_HIST) atomicAdd(&hist[y * gx + x], 1u);
-                        else atomicAdd(&tc[y * gx + x], 1u);
-                    }
+                count_pairs(LDS_HIST ? s_hist + vb * T : tile_count + (size_t)v * T, gx, rect, span, skip_none);
             }
             if (in_range) {
                 radii[o] = ok ? (int32_t)my_radius : 0;
-                const float out_depth = ok ? tz : 0.0f;
-                if (narrow) {
-                    BinRec br;
-                    br.rect = ok ? ((uint32_t)rminx | ((uint32_t)rminy << 8) | ((uint32_t)rmaxx << 16) | ((uint32_t)rmaxy << 24)) : 0u;
-                    br.depth = out_depth; br.span = span;
-                    ((BinRec *)binrec)[o] = br;
-                } else {
-                    BinRecWide br;
-                    br.rect = ok ? make_ushort4((unsigned short)rminx, (unsigned short)rminy, (unsigned short)rmaxx, (unsigned short)rmaxy)
-                                 : make_ushort4(0, 0, 0, 0);
-                    br.depth = out_depth; br.span = span;
-                    ((BinRecWide *)binrec)[o] = br;
-                }
+                store_bin_record(binrec, narrow, o, ok, rect, tz, span);
             }
             if (staged) {
                 s_rec[0 * kRecRow + threadIdx.x] = rr0;
@@ -202,151 +179,36 @@ k_preprocess(lsr_dims d, lsr_inputs in, float *__restrict__ rec, int RF, char *_
             }
         }
     }
-    if (LDS_HIST && !SEG) {
-        __syncthreads();
-        for (int t = threadIdx.x; t < VB * T; t += kPreThreads) {
-            const int v = v0 + t / T;
-            const uint32_t c = s_hist[t];
-            if (c && v < d.num_views) atomicAdd(&tile_count[(size_t)v * T + (t % T)], c);
-        }
-    }
+    // ---- behind the projection: histogram flush or key emission, and the folded tile scan (lsr_key_emit.h, shared with
+    // k_preprocess_sh) ----
+    const int n_valid = min(VB, d.num_views - v0) * T;   // counters of the workgroup's views that exist
+    if (LDS_HIST && !SEG) flush_counts<kPreThreads>(s_hist, tile_count + (size_t)v0 * T, n_valid);
     if (SEG) {
-        // ---- reserve: count -> first slot of this workgroup in the tile's segment ----
-        __syncthreads();
         uint32_t *s_first = s_hist + VB * T;      // (the dynamic allocation holds two arrays of VB * T words in this instance)
-        // (four counters per thread and round, their returning atomics in flight together: one round trip to the
-        // memory-side atomic unit per round instead of one per counter.  Only non-empty counters issue an atomic — adds of
-        // zero to a clamped address put thousands of same-address atomics of EVERY workgroup on one word: measured 5.5 ms
-        // instead of 0.15 for a one-view-per-workgroup launch)
-        for (int t0 = threadIdx.x; t0 < VB * T; t0 += 4 * kPreThreads) {
-            uint32_t c[4], first[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int t = t0 + k * kPreThreads;
-                c[k] = t < VB * T ? s_hist[t] : 0u;
-                if (c[k] && v0 + t / T >= d.num_views) c[k] = 0u;
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int t = t0 + k * kPreThreads;
-                if (c[k]) first[k] = __hip_atomic_fetch_add(&tile_count[(size_t)(v0 + t / T) * T + (t % T)], c[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int t = t0 + k * kPreThreads;
-                if (t < VB * T) s_first[t] = first[k];
-            }
-        }
-        __syncthreads();
-        const uint32_t cap = seg.cap;
-        // ---- emit, one view of the workgroup at a time, THROUGH LDS: the keys are first bucketed by tile in the (now idle)
-        // record staging array — a key's slot is its tile's local offset (exclusive scan of the workgroup's counts) plus its
-        // arrival rank — together with their final positions, and then leave as one linear pass over the slots: every
-        // lane stores, and the lanes of a tile's run hit consecutive addresses.  Written straight from the item loop (the
-        // first version of this pass) the same keys were 7.4 M lane-scattered 8-byte stores at 31 % lane utilisation: 0.053
-        // of the kernel's 0.155 ms (ablations in profiles/r05_ab_knobs.md); a thread still reads back only the binning
-        // records it wrote itself. ----
-        constexpr int KI = kPreItems / VB;                               // most Gaussians per thread
-        uint32_t *s_delta = (uint32_t *)s_rec;                           // [T] first slot in the segment minus local offset
-        const int kbase = (T * 4 + 7) & ~7;
-        uint64_t *s_key = (uint64_t *)((char *)s_rec + kbase);
-        const uint32_t buf = (uint32_t)((sizeof(s_rec) - kbase) / 12);
-        uint32_t *s_pos = (uint32_t *)((char *)s_rec + kbase + (size_t)buf * 8);
-        __shared__ uint32_t s_scanw[kPreThreads / LSR_WAVE];
-        const int tpt = (T + kPreThreads - 1) / kPreThreads;             // tiles per thread of the scan (<= 4: T <= 1024)
+        reserve_segments<kPreThreads>(s_hist, s_first, tile_count + (size_t)v0 * T, n_valid);
+        constexpr int KI = kPreItems / VB;        // most Gaussians per thread
+        const KeyBuckets kb(s_rec, sizeof(s_rec), T);   // (the record staging array is idle by now)
 #pragma unroll 1
         for (int vb = 0; vb < VB; ++vb) {
             const int v = v0 + vb;
-            if (v >= d.num_views || (seg.ablate & 2u)) break;             // block-uniform
-            uint32_t *cur = s_hist + vb * T;
-            // local offsets of this view's tiles: a contiguous chunk of tiles per thread
-            uint32_t cnt[4], mine = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int t = (int)threadIdx.x * tpt + k;
-                cnt[k] = (k < tpt && t < T) ? cur[t] : 0u;
-                mine += cnt[k];
-            }
-            uint32_t n_v;
-            uint32_t off = block_exclusive_scan<kPreThreads>(mine, s_scanw, n_v);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int t = (int)threadIdx.x * tpt + k;
-                if (k < tpt && t < T) { cur[t] = off; s_delta[t] = s_first[vb * T + t] - off; off += cnt[k]; }
-            }
-            __syncthreads();
-            const uint32_t seg0 = (uint32_t)v * (uint32_t)T;
+            if (v >= d.num_views) break;             // block-uniform
             // this view's records of the thread's Gaussians: unconditional loads at clamped addresses, all in flight together
             uint3 br[KI];
+            int index[KI];
+            bool valid[KI];
 #pragma unroll
             for (int it = 0; it < KI; ++it) {
                 const int i = min(base + min(it, kItems - 1) * kPreThreads + (int)threadIdx.x, G - 1);
                 br[it] = *(const uint3 *)(binrec + ((size_t)v * G + (size_t)i) * sizeof(BinRec));
+                index[it] = base + it * kPreThreads + (int)threadIdx.x;
+                valid[it] = it < kItems && index[it] < G;
             }
-#pragma unroll
-            for (int it = 0; it < KI; ++it) {
-                const int i = base + it * kPreThreads + (int)threadIdx.x;
-                const uint32_t rc = (it < kItems && i < G) ? br[it].x : 0u;     // (a culled record holds an empty rectangle)
-                const int x0 = rc & 0xff, y0 = (rc >> 8) & 0xff, x1 = (rc >> 16) & 0xff, y1 = rc >> 24;
-                const uint64_t key = ((uint64_t)br[it].y << 32) | ((uint32_t)i << seg.key_shift);
-                const uint32_t sp = br[it].z;
-                int ex0 = x0, ey0 = y0, ex1 = x1, ey1 = y1;
-                if (skip_none) reached_rect(sp, ex0, ey0, ex1, ey1);      // (the pairs pass 1 counted)
-                for (int y = ey0; y < ey1; ++y)
-                    for (int x = ex0; x < ex1; ++x) {
-                        const int t = y * gx + x;
-                        const uint32_t code = seg.key_shift ? span_code(sp, x - x0, y - y0) : 0u;
-                        const uint32_t slot = atomicAdd(&cur[t], 1u);
-                        // position in the tile's segment, CLAMPED (not tested): the surplus keys of an overfull segment land
-                        // on its last slot; such a tile is binned again by the fallback scatter
-                        const uint32_t pos = (seg0 + (uint32_t)t) * cap + min(slot + s_delta[t], cap - 1u);
-                        if (slot < buf) { s_key[slot] = key | code; s_pos[slot] = pos; }
-                        else seg.keys[pos] = key | code;              // (more pairs in one view of this workgroup than the array holds)
-                    }
-            }
-            __syncthreads();
-            const uint32_t nflush = min(n_v, buf);
-            if (!(seg.ablate & 1u))
-                for (uint32_t j = threadIdx.x; j < nflush; j += kPreThreads) seg.keys[s_pos[j]] = s_key[j];
-            __syncthreads();
+            emit_view_keys<kPreThreads, KI>(s_hist + vb * T, s_first + vb * T, kb, seg, (uint32_t)v, T, gx, skip_none, br, index, valid);
         }
     }
-    // ---- the tile scan, folded in (round 4; it used to be a kernel of its own between this one and k_scatter): the LAST
-    // workgroup to arrive scans the tile counts, writes the tile offsets, the header, the compositing work items and
-    // the two numbers the synchronous forward's host is waiting for (lsr_tile_scan.h).
-    // The counts are only ever touched by agent-scope atomics, which are performed past the (mutually incoherent)
-    // per-XCD L2s: a block waits until its own count updates have been acknowledged (vmcnt) and only then arrives at the
-    // counter, and the last block reads the counts with agent-scope atomic loads.  No release fence: that would write
-    // back every record line the block has just left dirty in L2 (measured in round 2: the forward went from 0.56 to
-    // 0.83 ms per step). ----
     if (fs.enabled) {
-        __shared__ uint32_t s_last;
         __shared__ TileScanShared<kPreThreads> s_scan;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const uint32_t arrived = __hip_atomic_fetch_add(&header[kHdrPreDone], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            s_last = arrived == gridDim.x * gridDim.y - 1u;
-        }
-        __syncthreads();
-        if (s_last) {
-            // the counts go through LDS (the record staging array is free by now): sixteen of them per thread in
-            // registers cost the whole kernel a wave per SIMD (85 instead of 77 VGPRs)
-            uint32_t *s_counts = (uint32_t *)s_rec;
-            const int N = d.num_views * T;
-            for (int i0 = threadIdx.x; i0 < N; i0 += 4 * kPreThreads) {     // four coalesced loads in flight per thread
-                uint32_t c[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    c[k] = __hip_atomic_load(&tile_count[min(i0 + k * kPreThreads, N - 1)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (i0 + k * kPreThreads < N) s_counts[i0 + k * kPreThreads] = c[k];
-            }
-            __syncthreads();
-            tile_scan_block<kPreThreads, 0, false>(s_counts, fs.tile_start, header, HostMirror{fs.host_words, fs.host_seq},
-                                                   fs.tile_order, N, fs.capacity, s_scan);
-        }
+        folded_tile_scan<kPreThreads>(fs, header, tile_count, d.num_views * T, (uint32_t *)s_rec, s_scan);
     }
 }
 
@@ -401,7 +263,7 @@ hipError_t launch_preprocess(const lsr_dims &d, const lsr_inputs &in, char *geom
     const bool fma = projection_contraction();
     // single-pass binning: the caller asks for it only when segment_capacity(d) > 0, which implies byte tile coordinates
     // and T <= 1024 (the LDS histogram of up to 4 views)
-    SegOut so{nullptr, 0u, index_packing(d).key_shift, (uint32_t)env_int("LSR_SEG_ABLATE", 0)};
+    SegOut so{nullptr, 0u, index_packing(d).key_shift};
     if (seg_mode) {
         if (!lds || !narrow || L.seg_cap == 0) return hipErrorInvalidValue;
         so.keys = (uint64_t *)(geom + L.seg_keys); so.cap = L.seg_cap;

@@ -30,9 +30,9 @@
 
 #include "lsr_blend.h"
 #include "lsr_depth.h"
+#include "lsr_key_emit.h"
 #include "lsr_project.h"
 #include "lsr_sh.h"
-#include "lsr_tile_scan.h"
 
 namespace lsr {
 
@@ -354,28 +354,11 @@ k_preprocess_sh(ShParams pk, PreShArgs a) {
             const bool ok = pj.ok;
             const size_t o = (size_t)v * G + ii;
             const uint32_t span = ok ? footprint_cells(pj.px, pj.py, pj.conic_a, pj.conic_b, pj.conic_c, opacity, pj.rminx, pj.rminy) : kSpanNone;
-            if (ok) {
-                uint32_t *hist = a.lds_hist ? s_hist + v * T : tile_count + (size_t)v * T;
-                int hx0 = pj.rminx, hy0 = pj.rminy, hx1 = pj.rmaxx, hy1 = pj.rmaxy;
-                if (skip_none) reached_rect(span, hx0, hy0, hx1, hy1);      // LSR_FWD_REACHED_ONLY
-                for (int y = hy0; y < hy1; ++y)
-                    for (int x = hx0; x < hx1; ++x) atomicAdd(&hist[y * gx + x], 1u);
-            }
+            const TileRect rect{pj.rminx, pj.rminy, pj.rmaxx, pj.rmaxy};
+            if (ok) count_pairs(a.lds_hist ? s_hist + v * T : tile_count + (size_t)v * T, gx, rect, span, skip_none);
             if (active) {
                 radii[o] = ok ? (int32_t)pj.radius : 0;
-                const float out_depth = ok ? pj.tz : 0.0f;
-                if (a.narrow) {
-                    BinRec br;
-                    br.rect = ok ? ((uint32_t)pj.rminx | ((uint32_t)pj.rminy << 8) | ((uint32_t)pj.rmaxx << 16) | ((uint32_t)pj.rmaxy << 24)) : 0u;
-                    br.depth = out_depth; br.span = span;
-                    ((BinRec *)binrec)[o] = br;
-                } else {
-                    BinRecWide br;
-                    br.rect = ok ? make_ushort4((unsigned short)pj.rminx, (unsigned short)pj.rminy, (unsigned short)pj.rmaxx, (unsigned short)pj.rmaxy)
-                                 : make_ushort4(0, 0, 0, 0);
-                    br.depth = out_depth; br.span = span;
-                    ((BinRecWide *)binrec)[o] = br;
-                }
+                store_bin_record(binrec, a.narrow, o, ok, rect, pj.tz, span);
             }
             if (!ok) continue;
             // slot 6 of the record: the view z, or the view's depth mode applied to it (as in k_preprocess; uniform branch)
@@ -426,124 +409,37 @@ k_preprocess_sh(ShParams pk, PreShArgs a) {
             }
         }
     }
-    if (a.lds_hist && !SEG) {
-        __syncthreads();
-        for (int t = tid; t < V * T; t += kShThreads) {
-            const uint32_t cnt = s_hist[t];
-            if (cnt) atomicAdd(&tile_count[t], cnt);
-        }
-    }
+    // ---- behind the projection, as in k_preprocess (lsr_key_emit.h): histogram flush, or single-pass binning (round 5) — the
+    // coefficient rows are dead by now, their area holds the emission's buckets — and the folded tile scan ----
+    if (a.lds_hist && !SEG) flush_counts<kShThreads>(s_hist, tile_count, V * T);
     if (SEG) {
-        // ---- single-pass binning (round 5), as in k_preprocess: reserve this workgroup's slots in the tiles' key segments
-        // with the returning form of the count atomics, then emit the keys of its (view, Gaussian) items view by view
-        // through an LDS bucket pass (the coefficient rows are dead by now: their area holds the buckets) ----
-        __syncthreads();
         uint32_t *s_first = s_hist + V * T;
-        for (int t0 = tid; t0 < V * T; t0 += 4 * kShThreads) {
-            uint32_t c[4], first[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { const int t = t0 + k * kShThreads; c[k] = t < V * T ? s_hist[t] : 0u; }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int t = t0 + k * kShThreads;
-                if (c[k]) first[k] = __hip_atomic_fetch_add(&tile_count[t], c[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { const int t = t0 + k * kShThreads; if (t < V * T) s_first[t] = first[k]; }
-        }
-        __syncthreads();
-        const uint32_t cap = a.seg.cap;
-        uint32_t *s_delta = (uint32_t *)s_lds;
-        const int kbase = (T * 4 + 7) & ~7;
-        uint64_t *s_key = (uint64_t *)((char *)s_lds + kbase);
-        const uint32_t buf = (uint32_t)(((size_t)a.hist_off * 4 - kbase) / 12);
-        uint32_t *s_pos = (uint32_t *)((char *)s_lds + kbase + (size_t)buf * 8);
-        __shared__ uint32_t s_scanw[kShWaves];
-        const int tpt = (T + kShThreads - 1) / kShThreads;
+        reserve_segments<kShThreads>(s_hist, s_first, tile_count, V * T);
+        const KeyBuckets kb(s_lds, (size_t)a.hist_off * 4, T);
 #pragma unroll 1
         for (int v = 0; v < V; ++v) {
-            uint32_t *cur = s_hist + v * T;
-            uint32_t cnt[4], mine = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int t = tid * tpt + k;
-                cnt[k] = (k < tpt && t < T) ? cur[t] : 0u;
-                mine += cnt[k];
-            }
-            uint32_t n_v;
-            uint32_t off = block_exclusive_scan<kShThreads>(mine, s_scanw, n_v);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int t = tid * tpt + k;
-                if (k < tpt && t < T) { cur[t] = off; s_delta[t] = s_first[v * T + t] - off; off += cnt[k]; }
-            }
-            __syncthreads();
-            const uint32_t seg0 = (uint32_t)(view0 + v) * (uint32_t)T;
             // the workgroup's Gaussians of this view: wave w takes chunks w, w + 4 (records written by whichever wave
-            // projected the view: visible since the barrier above)
+            // projected the view: visible since the barrier of the reserve pass)
             uint3 br[2];
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                const int c = min(wave + kShWaves * k, a.chunks - 1);
-                const int i = min((blockIdx.x * a.chunks + c) * LSR_WAVE + lane, G - 1);
-                br[k] = *(const uint3 *)(binrec + ((size_t)v * G + (size_t)i) * sizeof(BinRec));
-            }
+            int index[2];
+            bool valid[2];
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
                 const int c = wave + kShWaves * k;
-                const int i = (blockIdx.x * a.chunks + c) * LSR_WAVE + lane;
-                const uint32_t rc = (c < a.chunks && i < G) ? br[k].x : 0u;
-                const int x0 = rc & 0xff, y0 = (rc >> 8) & 0xff, x1 = (rc >> 16) & 0xff, y1 = rc >> 24;
-                const uint64_t key = ((uint64_t)br[k].y << 32) | ((uint32_t)i << a.seg.key_shift);
-                const uint32_t sp = br[k].z;
-                int ex0 = x0, ey0 = y0, ex1 = x1, ey1 = y1;
-                if (skip_none) reached_rect(sp, ex0, ey0, ex1, ey1);
-                for (int y = ey0; y < ey1; ++y)
-                    for (int x = ex0; x < ex1; ++x) {
-                        const int t = y * gx + x;
-                        const uint32_t code = a.seg.key_shift ? span_code(sp, x - x0, y - y0) : 0u;
-                        const uint32_t slot = atomicAdd(&cur[t], 1u);
-                        const uint32_t pos = (seg0 + (uint32_t)t) * cap + min(slot + s_delta[t], cap - 1u);
-                        if (slot < buf) { s_key[slot] = key | code; s_pos[slot] = pos; }
-                        else a.seg.keys[pos] = key | code;
-                    }
+                index[k] = (blockIdx.x * a.chunks + c) * LSR_WAVE + lane;
+                valid[k] = c < a.chunks && index[k] < G;
+                const int i = min((blockIdx.x * a.chunks + min(c, a.chunks - 1)) * LSR_WAVE + lane, G - 1);
+                br[k] = *(const uint3 *)(binrec + ((size_t)v * G + (size_t)i) * sizeof(BinRec));
             }
-            __syncthreads();
-            const uint32_t nflush = min(n_v, buf);
-            for (uint32_t j = tid; j < nflush; j += kShThreads) a.seg.keys[s_pos[j]] = s_key[j];
-            __syncthreads();
+            emit_view_keys<kShThreads, 2>(s_hist + v * T, s_first + v * T, kb, a.seg, (uint32_t)(view0 + v), T, gx, skip_none, br, index, valid);
         }
     }
-    // ---- the tile scan in the last workgroup to arrive (as in k_preprocess; the counts pass through LDS) ----
     if (a.fs.enabled) {
-        __shared__ uint32_t s_last;
         // (the scan's 4 KB of counters live in the dynamic allocation behind the staged counts, not in static LDS: static
         // bytes count against every workgroup of the launch, and 4.7 KB of them were the difference between three and four
         // workgroups per CU at the configs[3] / [4] payload)
         TileScanShared<kShThreads> &s_scan = *(TileScanShared<kShThreads> *)((char *)s_lds + (size_t)kFoldTiles * 4);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) {
-            const uint32_t arrived = __hip_atomic_fetch_add(&a.header[kHdrPreDone], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            s_last = arrived == gridDim.x * gridDim.y - 1u;
-        }
-        __syncthreads();
-        if (s_last) {
-            uint32_t *s_counts = (uint32_t *)s_lds;
-            const int N = a.views_total * T;
-            for (int i0 = tid; i0 < N; i0 += 4 * kShThreads) {
-                uint32_t cc[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    cc[k] = __hip_atomic_load(&a.tile_count[min(i0 + k * kShThreads, N - 1)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (i0 + k * kShThreads < N) s_counts[i0 + k * kShThreads] = cc[k];
-            }
-            __syncthreads();
-            tile_scan_block<kShThreads, 0, false>(s_counts, a.fs.tile_start, a.header, HostMirror{a.fs.host_words, a.fs.host_seq},
-                                                  a.fs.tile_order, N, a.fs.capacity, s_scan);
-        }
+        folded_tile_scan<kShThreads>(a.fs, a.header, a.tile_count, a.views_total * T, (uint32_t *)s_lds, s_scan);
     }
 }
 
@@ -942,7 +838,7 @@ hipError_t launch_preprocess_sh(const lsr_dims &d, const lsr_inputs &in, char *g
     // single-pass binning (the caller asks for it only when segment_capacity(d) > 0: byte tile coordinates, T <= 1024): the
     // kernel then also emits the sort keys; its bucket array lives in the coefficient area, which therefore is at least 16 KB,
     // and the histogram is followed by the array of first slots — up to 8 chunks of 64 Gaussians per workgroup (two per wave)
-    a.seg = SegOut{nullptr, 0u, index_packing(d).key_shift, 0u};
+    a.seg = SegOut{nullptr, 0u, index_packing(d).key_shift};
     if (seg_mode) {
         a.hist_off = std::max(a.hist_off, 4096);
         if (L.seg_cap == 0 || !narrow_bins(d) || ((size_t)a.hist_off + 2 * (size_t)Vg * T) * 4 > 65536) return hipErrorInvalidValue;

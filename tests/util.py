@@ -95,6 +95,15 @@ class HipRun:
             f"HipRun: features have leading dim {self.features.shape[0]}, expected {V} views"
         self.d = d = Dims(V, G, H, W, Cf, mode, bi["sh_degree"], K, 0 if shared_means else 3 * G,
                           0 if shared_means else 6 * G, 0, 0, Cf * G if Cf else 0, 6, 0, 0, 0, 0, 0, 0, forward_flags)
+        self._forward(d, dev)
+
+    def _forward(self, d, dev):
+        """lsr_forward_prepare + lsr_forward_render of dims ``d`` on the input tensors held by ``self``."""
+        from latentsplat_amd import _lib
+        from latentsplat_amd._lib import Inputs, Layout, Outputs
+        self.lib = lib = _lib.load()
+        self.d = d
+        V, G, H, W, Cf, mode = d.num_views, d.num_gaussians, d.height, d.width, d.feat_channels, d.color_mode
         p = lambda x: None if x is None else C.c_void_p(x.data_ptr())
         self.inp = Inputs(p(self.views), p(self.means), p(self.cov6), p(self.opac), p(self.color), p(self.features))
         u8 = dict(dtype=torch.uint8, device=dev)

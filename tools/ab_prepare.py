@@ -1,9 +1,8 @@
 #!/usr/bin/env python
 """Times lsr_forward_prepare ALONE (projection kernel + tile scan; nothing downstream runs) for development-knob sets in
-one process — used for phase ablations of the single-pass binning whose results are deliberately wrong
-(LSR_SEG_ABLATE) and must therefore never reach the sort / compositing kernels.
+one process.
 
-    python tools/ab_prepare.py [--views 16] [--gaussians 300000] '{"LSR_SEGMENTS":0}' '{"LSR_SEG_ABLATE":1}' ..."""
+    python tools/ab_prepare.py [--views 16] [--gaussians 300000] '{"LSR_SEGMENTS":0}' '{"LSR_PRE_VB":2}' ..."""
 import argparse
 import ctypes as C
 import json
@@ -19,7 +18,7 @@ import bench  # noqa: E402
 from latentsplat_amd import _lib  # noqa: E402
 from latentsplat_amd._lib import Dims, Inputs  # noqa: E402
 
-DEFAULTS = {"LSR_SEGMENTS": 1, "LSR_SEG_ABLATE": 0, "LSR_PRE_VB": 0, "LSR_PRE_ITEMS": 8, "LSR_FOLD_SCAN": 1}
+DEFAULTS = {"LSR_SEGMENTS": 1, "LSR_PRE_VB": 0, "LSR_PRE_ITEMS": 8, "LSR_FOLD_SCAN": 1}
 
 
 def main():
