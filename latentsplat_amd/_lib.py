@@ -1,5 +1,5 @@
 """ctypes binding of ``liblsr_hip.so`` (C ABI: include/lsr_rasterizer.h, include/lsr_adapter.h, include/lsr_latent.h, include/lsr_ply.h,
-include/lsr_sh_rotate.h, include/lsr_depth_head.h).
+include/lsr_sh_rotate.h, include/lsr_depth_head.h, include/lsr_scene.h).
 
 The library is built in-tree by ``latentsplat_amd/csrc/Makefile`` (``__graft_entry__.build()``).
 There is no CPU fallback: if the shared object is missing or not loadable this module raises, and
@@ -167,6 +167,27 @@ DEPTH_HEAD_DETERMINISTIC, DEPTH_HEAD_TRANSMITTANCE = 1, 2   # lsr_depth_head_dim
 DEPTH_HEAD_MAX_BUCKETS, DEPTH_HEAD_MAX_SAMPLES, DEPTH_HEAD_MAX_ROW_FLOATS = 64, 8, 4096
 
 
+class SceneParams(C.Structure):      # lsr_scene_params (include/lsr_scene.h)
+    _fields_ = [(n, C.c_void_p) for n in ("features_dc", "features_rest", "opacity", "scaling", "rotation")]
+
+
+class SceneDims(C.Structure):        # lsr_scene_dims
+    _fields_ = [("n", C.c_int64), ("sh_coeffs", C.c_int32), ("scale_modifier", C.c_float),
+                ("reserved0", C.c_int32), ("reserved1", C.c_int32)]
+
+
+class SceneOutputs(C.Structure):     # lsr_scene_outputs
+    _fields_ = [(n, C.c_void_p) for n in ("shs", "opacities", "cov3D", "scales", "rotations")]
+
+
+class SceneOutGrads(C.Structure):    # lsr_scene_out_grads
+    _fields_ = [(n, C.c_void_p) for n in ("shs", "opacities", "cov3D")]
+
+
+class SceneInGrads(C.Structure):     # lsr_scene_in_grads
+    _fields_ = [(n, C.c_void_p) for n in ("features_dc", "features_rest", "opacity", "scaling", "rotation")]
+
+
 def sh_rotate_table_floats(degree: int) -> int:
     """LSR_SH_ROTATE_TABLE_FLOATS: sum of (2l+1)^2 over l <= degree."""
     return (degree + 1) * (2 * degree + 1) * (2 * degree + 3) // 3
@@ -184,6 +205,7 @@ EXPORTS = (
     "lsr_ply_pack_scene", "lsr_ply_sh_axes_matrix", "lsr_ply_write_scene_host",
     "lsr_sh_rotation_matrices", "lsr_sh_rotate_forward", "lsr_sh_rotate_backward",
     "lsr_depth_head_forward", "lsr_depth_head_backward",
+    "lsr_scene_activate_forward", "lsr_scene_activate_backward",
 )
 
 _lib = None
@@ -314,6 +336,11 @@ def load():
     lib.lsr_depth_head_forward.argtypes = [C.POINTER(DepthHeadDims), P, P, P, P, P, P, P, P]
     lib.lsr_depth_head_backward.restype = C.c_int
     lib.lsr_depth_head_backward.argtypes = [C.POINTER(DepthHeadDims), P, P, P, P, P, P, P, P]
+    lib.lsr_scene_activate_forward.restype = C.c_int
+    lib.lsr_scene_activate_forward.argtypes = [C.POINTER(SceneDims), C.POINTER(SceneParams), C.POINTER(SceneOutputs), P]
+    lib.lsr_scene_activate_backward.restype = C.c_int
+    lib.lsr_scene_activate_backward.argtypes = [C.POINTER(SceneDims), C.POINTER(SceneParams), C.POINTER(SceneOutGrads),
+                                                C.POINTER(SceneInGrads), P]
     _lib = lib
     return lib
 

@@ -1,0 +1,275 @@
+"""A trainable 3DGS scene: the raw parameters a 3DGS trainer holds, activated for the rasterizer by one HIP kernel.
+
+A scene file, and every 3DGS trainer, holds log-scales, unnormalised quaternions, opacity logits and the colour SH as
+``f_dc`` / ``f_rest``; the rasterizer takes packed covariances, probabilities and one ``(n, K, 3)`` SH tensor.
+:func:`activate_scene` is that map as a ``torch.autograd.Function`` over ``lsr_scene_activate_forward`` /
+``lsr_scene_activate_backward`` (csrc/scene_params.hip, C ABI include/lsr_scene.h): one launch each way.
+:class:`GaussianScene` holds a scene under the published trainer's parameter names, reads and writes scene files without
+touching the values, and renders through :func:`latentsplat_amd.rasterizer.rasterize_views`.
+
+The kernels take float32 ROCm tensors only; there is no CPU fallback.  Scene files mean the ``"3dgs"`` colour SH basis
+(:func:`latentsplat_amd.rasterizer.set_color_sh_convention`, the default); nothing here changes that process-wide
+setting."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from math import isqrt
+from pathlib import Path
+from typing import Optional, Sequence
+
+import torch
+from torch import Tensor, nn
+
+from . import _lib
+from .ply_import import Scene3DGS, read_header
+
+_FORWARD_OUTPUTS = ("shs", "opacities", "cov3D", "scales", "rotations")
+_PARAMS = ("features_dc", "features_rest", "opacity", "scaling", "rotation")
+
+
+def _ptr(t: Optional[Tensor]) -> C.c_void_p:
+    return C.c_void_p(None if t is None or t.numel() == 0 else t.data_ptr())
+
+
+def _quad(t: Tensor) -> Tensor:
+    """(the kernels move a quaternion as one 16-byte quad)"""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _prepare(features_dc: Tensor, features_rest: Tensor, opacity: Tensor, scaling: Tensor, rotation: Tensor):
+    """Checked, detached, contiguous parameters and ``(n, K)``."""
+    given = (features_dc, features_rest, opacity, scaling, rotation)
+    for name, t in zip(_PARAMS, given):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32:
+            raise _lib.LsrError(f"activate_scene needs float32 ROCm tensors (no CPU fallback): {name} is not one")
+    n = features_dc.shape[0]
+    if tuple(features_dc.shape) != (n, 1, 3) or features_rest.dim() != 3 or features_rest.shape[0] != n or features_rest.shape[2] != 3:
+        raise _lib.LsrError(f"features_dc must be (n, 1, 3) and features_rest (n, K - 1, 3), got {tuple(features_dc.shape)} "
+                            f"and {tuple(features_rest.shape)}")
+    K = features_rest.shape[1] + 1
+    if K not in (1, 4, 9, 16, 25):
+        raise _lib.LsrError(f"{K} SH coefficients per channel: expected 1, 4, 9, 16 or 25")
+    if tuple(opacity.shape) != (n, 1) or tuple(scaling.shape) != (n, 3) or tuple(rotation.shape) != (n, 4):
+        raise _lib.LsrError("opacity must be (n, 1), scaling (n, 3) and rotation (n, 4)")
+    if len({t.device for t in given}) != 1:
+        raise _lib.LsrError("the scene's tensors must be on one device")
+    dc, rest, op, sc, rot = (t.detach().contiguous() for t in given)
+    return (dc, rest, op, sc, _quad(rot)), n, K
+
+
+def _dims(n: int, K: int, scale_modifier: float) -> _lib.SceneDims:
+    return _lib.SceneDims(n=n, sh_coeffs=K, scale_modifier=float(scale_modifier), reserved0=0, reserved1=0)
+
+
+def activate_forward(features_dc: Tensor, features_rest: Tensor, opacity: Tensor, scaling: Tensor, rotation: Tensor,
+                     scale_modifier: float = 1.0, want: Optional[Sequence[str]] = None) -> dict:
+    """``lsr_scene_activate_forward`` as it is (no autograd): the outputs named in ``want`` (default: all of ``shs,
+    opacities, cov3D, scales, rotations``) as a dict; the others are not computed."""
+    params, n, K = _prepare(features_dc, features_rest, opacity, scaling, rotation)
+    shapes = dict(shs=(n, K, 3), opacities=(n, 1), cov3D=(n, 6), scales=(n, 3), rotations=(n, 4))
+    unknown = [k for k in (want or ()) if k not in shapes]
+    if unknown:
+        raise _lib.LsrError(f"unknown outputs {unknown}; expected some of {list(shapes)}")
+    lib = _lib.load()
+    dev = params[0].device
+    out = {k: torch.empty(s, dtype=torch.float32, device=dev) for k, s in shapes.items() if want is None or k in want}
+    if n == 0:
+        return out
+    ptrs = _lib.SceneOutputs(**{k: _ptr(t) for k, t in out.items()})
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.lsr_scene_activate_forward(C.byref(_dims(n, K, scale_modifier)),
+                                                  C.byref(_lib.SceneParams(*map(_ptr, params))), C.byref(ptrs), stream),
+                   "lsr_scene_activate_forward")
+    return out
+
+
+def activate_backward(features_dc: Tensor, features_rest: Tensor, opacity: Tensor, scaling: Tensor, rotation: Tensor,
+                      grad_shs: Optional[Tensor], grad_opacities: Optional[Tensor], grad_cov3D: Optional[Tensor],
+                      scale_modifier: float = 1.0, want: Optional[Sequence[str]] = None) -> dict:
+    """``lsr_scene_activate_backward`` as it is: the gradients of the parameters named in ``want`` (default: all five)
+    for the given upstream gradients (``None`` = zero)."""
+    params, n, K = _prepare(features_dc, features_rest, opacity, scaling, rotation)
+    unknown = [k for k in (want or ()) if k not in _PARAMS]
+    if unknown:
+        raise _lib.LsrError(f"unknown gradients {unknown}; expected some of {list(_PARAMS)}")
+    dev = params[0].device
+    ups = []
+    for name, g, shape in (("shs", grad_shs, (n, K, 3)), ("opacities", grad_opacities, (n, 1)), ("cov3D", grad_cov3D, (n, 6))):
+        if g is not None:
+            if not g.is_cuda or g.dtype != torch.float32 or tuple(g.shape) != shape or g.device != dev:
+                raise _lib.LsrError(f"the gradient of {name} must be a float32 ROCm tensor of shape {shape} on the scene's device")
+            g = g.detach().contiguous()
+        ups.append(g)
+    lib = _lib.load()
+    out = {k: torch.empty_like(t) for k, t in zip(_PARAMS, params) if want is None or k in want}
+    if n == 0:
+        return out
+    grads = _lib.SceneInGrads(**{k: _ptr(t) for k, t in out.items()})
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.lsr_scene_activate_backward(C.byref(_dims(n, K, scale_modifier)),
+                                                   C.byref(_lib.SceneParams(*map(_ptr, params))),
+                                                   C.byref(_lib.SceneOutGrads(*map(_ptr, ups))), C.byref(grads), stream),
+                   "lsr_scene_activate_backward")
+    return out
+
+
+class _ActivateScene(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, features_dc, features_rest, opacity, scaling, rotation, scale_modifier, geometry):
+        ctx.set_materialize_grads(False)
+        want = _FORWARD_OUTPUTS if geometry else _FORWARD_OUTPUTS[:3]
+        out = activate_forward(features_dc, features_rest, opacity, scaling, rotation, scale_modifier, want)
+        ctx.save_for_backward(features_dc, features_rest, opacity, scaling, rotation)
+        ctx.scale_modifier = scale_modifier
+        scales, rotations = out.get("scales"), out.get("rotations")
+        if geometry:
+            ctx.mark_non_differentiable(scales, rotations)
+        return out["shs"], out["opacities"], out["cov3D"], scales, rotations
+
+    @staticmethod
+    def backward(ctx, g_shs, g_opacities, g_cov3D, _g_scales, _g_rotations):
+        # a parameter gets a gradient (and a buffer) only where it is asked for and something reaches it
+        reach = (g_shs, g_shs, g_opacities, g_cov3D, g_cov3D)
+        want = [k for k, need, g in zip(_PARAMS, ctx.needs_input_grad, reach) if need and g is not None]
+        if not want:
+            return (None,) * 7
+        got = activate_backward(*ctx.saved_tensors, g_shs, g_opacities, g_cov3D, ctx.scale_modifier, want)
+        return tuple(got.get(k) for k in _PARAMS) + (None, None)
+
+
+def activate_scene(features_dc: Tensor, features_rest: Tensor, opacity: Tensor, scaling: Tensor, rotation: Tensor,
+                   scale_modifier: float = 1.0):
+    """Raw 3DGS parameters to the rasterizer's inputs, differentiable: ``(shs (n, K, 3), opacities (n, 1), cov3D (n, 6))``.
+
+    ``features_dc (n, 1, 3)`` and ``features_rest (n, K - 1, 3)`` are concatenated; ``opacity (n, 1)`` holds logits;
+    ``cov3D = R diag((m s)^2) R^T`` packed as xx,xy,xz,yy,yz,zz with ``s = exp(scaling (n, 3))``, ``m =
+    scale_modifier`` and ``R`` the rotation of ``rotation (n, 4)`` (w,x,y,z, any non-zero norm).  One HIP launch
+    forward, one backward; float32 ROCm tensors only."""
+    return _ActivateScene.apply(features_dc, features_rest, opacity, scaling, rotation, float(scale_modifier), False)[:3]
+
+
+# ---- rows of a scene file <-> raw parameters: plain torch column gathers, once per load / save (any device) ----
+
+def rows_to_parameters(rows: Tensor, layout: _lib.PlyLayout) -> dict:
+    """The columns of a scene file's row table ``(n, stride)`` as the raw parameter tensors, bit for bit.  ``f_rest`` is
+    channel-major in the file (``f_rest_{c (K - 1) + k}``) and ``(n, K - 1, 3)`` here."""
+    n, K = rows.shape[0], layout.sh_coeffs
+    col = lambda offsets: rows[:, torch.tensor(list(offsets), dtype=torch.long, device=rows.device)].contiguous()
+    rest = col(layout.f_rest[:3 * (K - 1)]).reshape(n, 3, K - 1).transpose(1, 2).contiguous()
+    return dict(xyz=col(layout.xyz), features_dc=col(layout.f_dc).reshape(n, 1, 3), features_rest=rest,
+                opacity=col([layout.opacity]), scaling=col(layout.scale), rotation=col(layout.rot))
+
+
+def parameters_to_rows(xyz: Tensor, features_dc: Tensor, features_rest: Tensor, opacity: Tensor, scaling: Tensor,
+                       rotation: Tensor) -> Tensor:
+    """``(n, 14 + 3 K)`` rows in the published property order: xyz, three zero normals, f_dc, channel-major f_rest,
+    opacity, scale, rot; the values as they are."""
+    n = xyz.shape[0]
+    rest = features_rest.detach().transpose(1, 2).reshape(n, -1)
+    cols = [xyz.detach(), torch.zeros_like(xyz), features_dc.detach().reshape(n, 3), rest, opacity.detach(),
+            scaling.detach(), rotation.detach()]
+    return torch.cat(cols, dim=1).contiguous()
+
+
+class GaussianScene(nn.Module):
+    """A 3DGS scene as trainers hold it: raw parameters under the published trainer's names (``_xyz (n, 3)``,
+    ``_features_dc (n, 1, 3)``, ``_features_rest (n, K - 1, 3)``, ``_opacity (n, 1)`` logits, ``_scaling (n, 3)`` logs,
+    ``_rotation (n, 4)`` w,x,y,z), so that state dicts and per-tensor optimiser recipes carry over.  ``max_sh_degree`` is
+    the degree the stored bands reach, ``active_sh_degree`` the one rendered (:meth:`oneup_sh_degree`).
+
+    The colour SH coefficients are in the ``"3dgs"`` basis, as scene files hold them; :meth:`render` renders with the
+    process's colour SH convention as it finds it (``"3dgs"`` is the default) and does not change it."""
+
+    def __init__(self, xyz: Tensor, features_dc: Tensor, features_rest: Tensor, opacity: Tensor, scaling: Tensor,
+                 rotation: Tensor, active_sh_degree: Optional[int] = None):
+        super().__init__()
+        n = xyz.shape[0]
+        K = features_rest.shape[1] + 1 if features_rest.dim() == 3 else 0
+        shapes = ((xyz, (n, 3)), (features_dc, (n, 1, 3)), (features_rest, (n, K - 1, 3)), (opacity, (n, 1)),
+                  (scaling, (n, 3)), (rotation, (n, 4)))
+        if K not in (1, 4, 9, 16, 25) or any(tuple(t.shape) != s for t, s in shapes):
+            raise _lib.LsrError("GaussianScene takes xyz (n, 3), features_dc (n, 1, 3), features_rest (n, K - 1, 3) with K in "
+                                "1, 4, 9, 16, 25, opacity (n, 1), scaling (n, 3) and rotation (n, 4)")
+        if any(t.dtype != torch.float32 for t, _ in shapes):
+            raise _lib.LsrError("GaussianScene takes float32 tensors")
+        p = lambda t: nn.Parameter(t.detach().clone().contiguous())
+        self._xyz, self._features_dc, self._features_rest = p(xyz), p(features_dc), p(features_rest)
+        self._opacity, self._scaling, self._rotation = p(opacity), p(scaling), p(rotation)
+        self.max_sh_degree = isqrt(K) - 1
+        self.active_sh_degree = self.max_sh_degree if active_sh_degree is None else int(active_sh_degree)
+        if not 0 <= self.active_sh_degree <= self.max_sh_degree:
+            raise _lib.LsrError(f"active_sh_degree must be in 0..{self.max_sh_degree}")
+
+    @classmethod
+    def from_tensors(cls, xyz: Tensor, features_dc: Tensor, features_rest: Tensor, opacity: Tensor, scaling: Tensor,
+                     rotation: Tensor, active_sh_degree: Optional[int] = None) -> "GaussianScene":
+        """From raw tensors (copied): log-scales, opacity logits, unnormalised quaternions."""
+        return cls(xyz, features_dc, features_rest, opacity, scaling, rotation, active_sh_degree)
+
+    @classmethod
+    def from_ply(cls, path, device, *, check_opacity: bool = True) -> "GaussianScene":
+        """The raw parameters of a binary little-endian 3DGS scene file, bit for bit (the library's host reader, then
+        column gathers; nothing is activated and inverted again).  Logit-opacity files only: a file whose opacities all
+        lie in [0, 1] stores probabilities, as this project's viewer export ``export_ply`` writes them, and is refused
+        (``check_opacity=False`` takes the values as logits regardless)."""
+        device = torch.device(device)
+        lib = _lib.load()
+        layout = read_header(path)
+        host = torch.empty((layout.n, layout.stride), dtype=torch.float32, pin_memory=device.type == "cuda")
+        _lib.check(lib.lsr_ply_read_rows(os.fsencode(str(path)), C.c_void_p(host.data_ptr()), host.numel()),
+                   "lsr_ply_read_rows")
+        if check_opacity and layout.n > 0:
+            o = host[:, layout.opacity]
+            if float(o.min()) >= 0.0 and float(o.max()) <= 1.0:
+                raise _lib.LsrError(f"{path}: every opacity lies in [0, 1]: the file stores probabilities, not logits (a viewer "
+                                    "export of export_ply). Such a file holds no trainable scene; read it with "
+                                    "load_ply(path, device, opacity=\"raw\")")
+        return cls(**rows_to_parameters(host.to(device), layout))
+
+    @property
+    def num_gaussians(self) -> int:
+        return self._xyz.shape[0]
+
+    def oneup_sh_degree(self) -> None:
+        """Render one more SH band, up to the stored ones."""
+        if self.active_sh_degree < self.max_sh_degree:
+            self.active_sh_degree += 1
+
+    def _activate(self, scale_modifier: float, geometry: bool):
+        if not self._xyz.is_cuda:
+            raise _lib.LsrError("a GaussianScene is activated and rendered on the MI355X: move it to a ROCm ('cuda') device; "
+                                "there is no CPU fallback")
+        return _ActivateScene.apply(self._features_dc, self._features_rest, self._opacity, self._scaling, self._rotation,
+                                    float(scale_modifier), geometry)
+
+    def activated(self, scale_modifier: float = 1.0) -> Scene3DGS:
+        """The scene as the rasterizer takes it (differentiable in the parameters; ``scales`` and ``rotations`` are
+        values only).  ``means`` is ``_xyz`` itself; ``sh_degree`` the active degree, ``shs`` all stored bands."""
+        shs, opacities, cov, scales, rotations = self._activate(scale_modifier, True)
+        return Scene3DGS(means=self._xyz, covariances=cov, opacities=opacities, shs=shs, scales=scales,
+                         rotations=rotations, sh_degree=self.active_sh_degree)
+
+    def render(self, views: Tensor, height: int, width: int, scale_modifier: float = 1.0, **kw):
+        """``rasterize_views`` of the activated scene: ``(color, feature, mask, depth, radii)``.  ``views`` is a table
+        of ``build_view_table`` / ``make_view_table`` (one that requires grad receives the camera gradient); ``kw``
+        goes to ``rasterize_views``.  All stored SH coefficients are passed with ``sh_degree=active_sh_degree``."""
+        from .rasterizer import rasterize_views
+        shs, opacities, cov, _, _ = self._activate(scale_modifier, False)
+        return rasterize_views(views, height, width, self.active_sh_degree, self._xyz, cov, opacities, shs=shs, **kw)
+
+    def rows(self) -> Tensor:
+        """The scene as rows of a scene file (:func:`parameters_to_rows`), on the parameters' device."""
+        return parameters_to_rows(self._xyz, self._features_dc, self._features_rest, self._opacity, self._scaling,
+                                  self._rotation)
+
+    def save_ply(self, path) -> None:
+        """Write the raw parameters as a standard 3DGS scene file.  The values go out as they are: a scene that was
+        loaded and is saved untouched has bit-identical rows."""
+        rows = self.rows().cpu()
+        path = Path(path)
+        path.parent.mkdir(exist_ok=True, parents=True)
+        _lib.check(_lib.load().lsr_ply_write_scene_host(os.fsencode(str(path)), C.c_void_p(rows.data_ptr()), rows.shape[0],
+                                                        (self.max_sh_degree + 1) ** 2), "lsr_ply_write_scene_host")

@@ -1,0 +1,111 @@
+#!/usr/bin/env python
+"""Fit a 3DGS scene file to renders of itself: the load -> optimise -> save loop of INTEGRATION.md §10, as a tool.
+
+  1. `GaussianScene.from_ply(path, device)`: the file's raw parameters (log-scales, opacity logits, unnormalised
+     quaternions, f_dc / f_rest) under the published trainer's names;
+  2. target images: the loaded scene rendered under `no_grad` from the cameras of `tools/render_ply.py` (a circle around
+     the median of the means, `--distance` scene extents away);
+  3. the parameters are perturbed with seeded Gaussian noise scaled by `--noise`; unit noise is 0.1 on f_dc, 0.5 on the
+     opacity logits, 0.05 on the log-scales, 0.05 on the quaternions and 0.002 x extent on the positions;
+  4. `torch.optim.Adam`, one parameter group per tensor, minimising the mean L1 between render and target over all views
+     each step.  Every step is one `lsr_scene_activate_forward`, the rasterizer, its backward and one
+     `lsr_scene_activate_backward`;
+  5. `fit.json` (`loss_first`, `loss_last`, `steps`, the wall time per step after a warm-up, the scene's size) and the
+     fitted scene as `point_cloud.ply` in `--out`.
+
+The learning rates default to the published trainer's customary ones (position 1.6e-4 x extent, f_dc 2.5e-3, f_rest
+f_dc / 20, opacity 5e-2, scaling 5e-3, rotation 1e-3; Adam eps 1e-15).  They are defaults, not measurements: nothing here
+tuned them.  No SSIM term and no densification.
+
+usage: python tools/fit_ply.py scene.ply --out DIR [--views 8] [--size 256] [--steps 200] [--noise 1.0] [--seed 0] [--distance 2.5]"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+if os.path.dirname(os.path.abspath(__file__)) not in sys.path:
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from render_ply import circle_cameras, scene_extent  # noqa: E402
+
+UNIT_NOISE = dict(_features_dc=0.1, _opacity=0.5, _scaling=0.05, _rotation=0.05)
+POSITION_NOISE = 0.002      # x extent
+WARMUP_STEPS = 5            # steps left out of the time per step (fewer when there are fewer than 10 steps)
+
+
+def main(argv=None) -> dict:
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0],
+                                 epilog="The learning rates are the published trainer's customary defaults, not measurements.")
+    ap.add_argument("ply")
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--views", type=int, default=8)
+    ap.add_argument("--size", type=int, default=256)
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--noise", type=float, default=1.0, help="scale of the perturbation (0: start from the loaded scene)")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--distance", type=float, default=2.5, help="circle radius in scene extents")
+    ap.add_argument("--lr-position", type=float, default=1.6e-4, help="times the scene's extent (a default, not a measurement)")
+    ap.add_argument("--lr-dc", type=float, default=2.5e-3, help="(a default, not a measurement)")
+    ap.add_argument("--lr-rest", type=float, default=None, help="default: --lr-dc / 20")
+    ap.add_argument("--lr-opacity", type=float, default=5e-2, help="(a default, not a measurement)")
+    ap.add_argument("--lr-scaling", type=float, default=5e-3, help="(a default, not a measurement)")
+    ap.add_argument("--lr-rotation", type=float, default=1e-3, help="(a default, not a measurement)")
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.views < 1:
+        sys.exit("fit_ply needs at least one step and one view")
+    if not torch.cuda.is_available():
+        sys.exit("fit_ply needs an MI355X: no ROCm device is visible (there is no CPU fallback)")
+    from latentsplat_amd.rasterizer import build_view_table
+    from latentsplat_amd.scene_model import GaussianScene
+    dev = torch.device("cuda:0")
+    scene = GaussianScene.from_ply(a.ply, dev)
+    with torch.no_grad():
+        centre, extent = scene_extent(scene._xyz)
+        ext, intr, near, far = circle_cameras(centre, extent, a.views, a.distance)
+        views = build_view_table(ext, intr, near, far, torch.zeros(3, device=dev))
+        target = scene.render(views, a.size, a.size)[0]
+        gen = torch.Generator().manual_seed(a.seed)
+        noise = dict(UNIT_NOISE, _xyz=POSITION_NOISE * float(extent))
+        for name, p in scene.named_parameters():
+            if name in noise and a.noise:
+                p.add_((torch.randn(p.shape, generator=gen) * (a.noise * noise[name])).to(dev))
+    rates = dict(_xyz=a.lr_position * float(extent), _features_dc=a.lr_dc,
+                 _features_rest=a.lr_dc / 20 if a.lr_rest is None else a.lr_rest, _opacity=a.lr_opacity,
+                 _scaling=a.lr_scaling, _rotation=a.lr_rotation)
+    groups = [dict(params=[p], lr=rates[name], name=name) for name, p in scene.named_parameters() if p.numel()]
+    opt = torch.optim.Adam(groups, lr=0.0, eps=1e-15)
+    warm = min(WARMUP_STEPS, a.steps // 2)
+    losses = []
+    t0 = None
+    for step in range(a.steps):
+        if step == warm:
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+        opt.zero_grad(set_to_none=True)
+        loss = (scene.render(views, a.size, a.size)[0] - target).abs().mean()
+        loss.backward()
+        opt.step()
+        losses.append(loss.detach())
+    torch.cuda.synchronize(dev)
+    per_step = (time.perf_counter() - t0) / (a.steps - warm)
+    os.makedirs(a.out, exist_ok=True)
+    scene.save_ply(os.path.join(a.out, "point_cloud.ply"))
+    res = dict(loss_first=float(losses[0]), loss_last=float(losses[-1]), steps=a.steps, ms_per_step=1e3 * per_step,
+               timed_steps=a.steps - warm, gaussians=scene.num_gaussians, sh_degree=scene.max_sh_degree, views=a.views,
+               size=a.size, noise=a.noise, seed=a.seed, extent=float(extent))
+    with open(os.path.join(a.out, "fit.json"), "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+    return res
+
+
+if __name__ == "__main__":
+    main()
