@@ -351,8 +351,11 @@ int lsr_forward_speculative(const lsr_dims *d, const lsr_inputs *in, void *geom_
  * then follows on the SAME host thread and stream with the same dims + LSR_FWD_FRONT_DONE, the same geom_ws,
  * `out->radii` == radii and the same pair_capacity, and launches the rest.  Results are those of the one-call form bit for
  * bit (the same launches in the same stream order).  A call with LSR_FWD_FRONT_DONE that does not match the thread's pending
- * front half (other geom_ws / capacity, or none pending) returns LSR_EINVAL and launches nothing.  No allocation, no host
- * wait: graph-capturable like lsr_forward_nosync.  A synchronised call into an idle device: V = 1 0.128 -> 0.120 ms, V = 4
+ * front half (other geom_ws / capacity, or none pending) returns LSR_EINVAL and launches nothing.  No host wait.  On a stream
+ * that is being captured the front half keeps its counts on the device like lsr_forward_nosync — no pinned host words (whose
+ * first use on a host thread allocates), nothing a replay would write to the host — and is graph-capturable together with the
+ * lsr_forward_nosync that follows (tests/test_concurrent_calls_gpu.py); lsr_forward_speculative waits for the host words and
+ * refuses such a front half (LSR_EINVAL).  A synchronised call into an idle device: V = 1 0.128 -> 0.120 ms, V = 4
  * 0.201 -> 0.193 (profiles/r06_ab_knobs.md section 12); costs back-to-back callers one more C call (~5 us of host time). */
 int lsr_forward_front(const lsr_dims *d, const lsr_inputs *in, void *geom_ws, int32_t *radii, int64_t pair_capacity,
                       lsr_stream_t stream);

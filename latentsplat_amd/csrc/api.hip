@@ -578,10 +578,15 @@ int lsr_forward_front(const lsr_dims *d, const lsr_inputs *in, void *geom_ws, in
     if (d->num_gaussians > 0 && !radii) return LSR_ENULL;
     if (pair_capacity < 1 || pair_capacity >= ((int64_t)1 << 32)) return LSR_EINVAL;
     hipStream_t s = (hipStream_t)stream;
+    // On a capturing stream the counts stay on the device, as in lsr_forward_nosync (the only full call a capture can hold):
+    // the thread's first host_words() allocates pinned memory, which a capture refuses and is invalidated by, and every replay
+    // would write this call's stale sequence number into the thread's words.  seq 0 = launched without host words.
+    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &capture) != hipSuccess) { (void)hipGetLastError(); capture = hipStreamCaptureStatusNone; }
     HostWords hw;
-    host_words(hw);
-    const uint32_t seq = next_seq();
-    rc = launch_front(*d, *in, (char *)geom_ws, radii, &hw, seq, (uint32_t)pair_capacity, s);
+    uint32_t seq = 0u;
+    if (capture == hipStreamCaptureStatusNone) { host_words(hw); seq = next_seq(); }
+    rc = launch_front(*d, *in, (char *)geom_ws, radii, seq ? &hw : nullptr, seq, (uint32_t)pair_capacity, s);
     if (rc) return rc;
     g_front.geom = geom_ws; g_front.radii = radii; g_front.capacity = pair_capacity; g_front.seq = seq; g_front.stream = s;
     return LSR_OK;
@@ -699,7 +704,7 @@ int lsr_forward_speculative(const lsr_dims *d, const lsr_inputs *in, void *geom_
     host_words(hw);
     uint32_t seq;
     if (d->forward_flags & LSR_FWD_FRONT_DONE) {
-        if (!take_front(geom_ws, out->radii, pair_capacity, s, seq)) return LSR_EINVAL;
+        if (!take_front(geom_ws, out->radii, pair_capacity, s, seq) || seq == 0u) return LSR_EINVAL;   // (0: a front half without host words)
     } else {
         seq = next_seq();
         rc = launch_front(*d, *in, geom, out->radii, &hw, seq, (uint32_t)pair_capacity, s);

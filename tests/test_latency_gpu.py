@@ -108,9 +108,12 @@ def test_graph_capture_and_replay(hip_device):
 
 
 def test_graph_capture_of_forward_and_backward(hip_device):
-    """Round 6: a training-mode no-sync forward forks the gradient-workspace clear onto the library's side stream (beside the
-    compositing kernel) and joins it back inside the call, and orders the backward's work items with one more small kernel:
-    a hipGraph capture of forward + backward records all of it and replays to the eager gradients (float-atomic order only)."""
+    """Round 6: a training-mode no-sync forward zeroes the backward's gradient workspace itself and orders the backward's work
+    items with one more small kernel: a hipGraph capture of forward + backward records all of it and replays to the eager
+    gradients (float-atomic order only).  At this size the workspace is far below the ~110 MB above which the clear is forked
+    onto the library's side stream, so it runs in line on the caller's stream and this capture holds NO fork / join; the
+    capture with the fork and join (LSR_CLEAR_BESIDE=1, also with the side stream first created under capture) is
+    tests/test_concurrent_calls_gpu.py::test_captured_fork_and_join."""
     from latentsplat_amd.rasterizer import last_forward_status
     dev = hip_device
     bi, views, t, size = _inputs(dev, G=8000, size=64)
