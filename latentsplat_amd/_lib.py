@@ -1,5 +1,5 @@
 """ctypes binding of ``liblsr_hip.so`` (C ABI: include/lsr_rasterizer.h, include/lsr_adapter.h, include/lsr_latent.h, include/lsr_ply.h,
-include/lsr_sh_rotate.h, include/lsr_depth_head.h, include/lsr_scene.h).
+include/lsr_sh_rotate.h, include/lsr_depth_head.h, include/lsr_scene.h, include/lsr_loss.h).
 
 The library is built in-tree by ``latentsplat_amd/csrc/Makefile`` (``__graft_entry__.build()``).
 There is no CPU fallback: if the shared object is missing or not loadable this module raises, and
@@ -188,6 +188,11 @@ class SceneInGrads(C.Structure):     # lsr_scene_in_grads
     _fields_ = [(n, C.c_void_p) for n in ("features_dc", "features_rest", "opacity", "scaling", "rotation")]
 
 
+class PhotometricDims(C.Structure):  # lsr_photometric_dims (include/lsr_loss.h)
+    _fields_ = [("num_images", C.c_int32), ("channels", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("lambda_dssim", C.c_float), ("cov_norm", C.c_float), ("crop", C.c_int32), ("reserved0", C.c_int32)]
+
+
 def sh_rotate_table_floats(degree: int) -> int:
     """LSR_SH_ROTATE_TABLE_FLOATS: sum of (2l+1)^2 over l <= degree."""
     return (degree + 1) * (2 * degree + 1) * (2 * degree + 3) // 3
@@ -206,6 +211,7 @@ EXPORTS = (
     "lsr_sh_rotation_matrices", "lsr_sh_rotate_forward", "lsr_sh_rotate_backward",
     "lsr_depth_head_forward", "lsr_depth_head_backward",
     "lsr_scene_activate_forward", "lsr_scene_activate_backward",
+    "lsr_photometric_workspace_bytes", "lsr_photometric_forward", "lsr_photometric_backward",
 )
 
 _lib = None
@@ -341,6 +347,12 @@ def load():
     lib.lsr_scene_activate_backward.restype = C.c_int
     lib.lsr_scene_activate_backward.argtypes = [C.POINTER(SceneDims), C.POINTER(SceneParams), C.POINTER(SceneOutGrads),
                                                 C.POINTER(SceneInGrads), P]
+    lib.lsr_photometric_workspace_bytes.restype = SZ
+    lib.lsr_photometric_workspace_bytes.argtypes = [C.POINTER(PhotometricDims)]
+    lib.lsr_photometric_forward.restype = C.c_int
+    lib.lsr_photometric_forward.argtypes = [C.POINTER(PhotometricDims), P, P, P, P, P, P, P, P, P]
+    lib.lsr_photometric_backward.restype = C.c_int
+    lib.lsr_photometric_backward.argtypes = [C.POINTER(PhotometricDims), P, P, P, P, P, P]
     _lib = lib
     return lib
 

@@ -9,15 +9,17 @@
      opacity logits, 0.05 on the log-scales, 0.05 on the quaternions and 0.002 x extent on the positions;
   4. `torch.optim.Adam`, one parameter group per tensor, minimising the mean L1 between render and target over all views
      each step.  Every step is one `lsr_scene_activate_forward`, the rasterizer, its backward and one
-     `lsr_scene_activate_backward`;
-  5. `fit.json` (`loss_first`, `loss_last`, `steps`, the wall time per step after a warm-up, the scene's size) and the
-     fitted scene as `point_cloud.ply` in `--out`.
+     `lsr_scene_activate_backward`.  `--lambda-dssim L` with L > 0 minimises the published trainer's objective instead,
+     `(1 - L) * L1 + L * (1 - SSIM)` (its L is 0.2), through `latentsplat_amd.photometric_loss`: one HIP call each way;
+  5. `fit.json` (`loss_first`, `loss_last`, `steps`, `lambda_dssim`, the wall time per step after a warm-up, the scene's
+     size) and the fitted scene as `point_cloud.ply` in `--out`.
 
 The learning rates default to the published trainer's customary ones (position 1.6e-4 x extent, f_dc 2.5e-3, f_rest
 f_dc / 20, opacity 5e-2, scaling 5e-3, rotation 1e-3; Adam eps 1e-15).  They are defaults, not measurements: nothing here
-tuned them.  No SSIM term and no densification.
+tuned them.  No densification.
 
-usage: python tools/fit_ply.py scene.ply --out DIR [--views 8] [--size 256] [--steps 200] [--noise 1.0] [--seed 0] [--distance 2.5]"""
+usage: python tools/fit_ply.py scene.ply --out DIR [--views 8] [--size 256] [--steps 200] [--noise 1.0] [--seed 0] [--distance 2.5]
+                               [--lambda-dssim 0.0]"""
 from __future__ import annotations
 
 import argparse
@@ -52,6 +54,8 @@ def main(argv=None) -> dict:
     ap.add_argument("--noise", type=float, default=1.0, help="scale of the perturbation (0: start from the loaded scene)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--distance", type=float, default=2.5, help="circle radius in scene extents")
+    ap.add_argument("--lambda-dssim", type=float, default=0.0,
+                    help="weight of the D-SSIM term (0: plain L1, the default; the published trainer uses 0.2)")
     ap.add_argument("--lr-position", type=float, default=1.6e-4, help="times the scene's extent (a default, not a measurement)")
     ap.add_argument("--lr-dc", type=float, default=2.5e-3, help="(a default, not a measurement)")
     ap.add_argument("--lr-rest", type=float, default=None, help="default: --lr-dc / 20")
@@ -61,9 +65,12 @@ def main(argv=None) -> dict:
     a = ap.parse_args(argv)
     if a.steps < 1 or a.views < 1:
         sys.exit("fit_ply needs at least one step and one view")
+    if not 0.0 <= a.lambda_dssim <= 1.0:
+        sys.exit("--lambda-dssim must be in [0, 1]")
     if not torch.cuda.is_available():
         sys.exit("fit_ply needs an MI355X: no ROCm device is visible (there is no CPU fallback)")
     from latentsplat_amd.rasterizer import build_view_table
+    from latentsplat_amd.losses import photometric_loss
     from latentsplat_amd.scene_model import GaussianScene
     dev = torch.device("cuda:0")
     scene = GaussianScene.from_ply(a.ply, dev)
@@ -90,7 +97,8 @@ def main(argv=None) -> dict:
             torch.cuda.synchronize(dev)
             t0 = time.perf_counter()
         opt.zero_grad(set_to_none=True)
-        loss = (scene.render(views, a.size, a.size)[0] - target).abs().mean()
+        render = scene.render(views, a.size, a.size)[0]
+        loss = photometric_loss(render, target, a.lambda_dssim) if a.lambda_dssim > 0 else (render - target).abs().mean()
         loss.backward()
         opt.step()
         losses.append(loss.detach())
@@ -100,7 +108,7 @@ def main(argv=None) -> dict:
     scene.save_ply(os.path.join(a.out, "point_cloud.ply"))
     res = dict(loss_first=float(losses[0]), loss_last=float(losses[-1]), steps=a.steps, ms_per_step=1e3 * per_step,
                timed_steps=a.steps - warm, gaussians=scene.num_gaussians, sh_degree=scene.max_sh_degree, views=a.views,
-               size=a.size, noise=a.noise, seed=a.seed, extent=float(extent))
+               size=a.size, noise=a.noise, seed=a.seed, extent=float(extent), lambda_dssim=a.lambda_dssim)
     with open(os.path.join(a.out, "fit.json"), "w") as f:
         json.dump(res, f, indent=1)
     print(json.dumps(res))
