@@ -1,5 +1,5 @@
 """ctypes binding of ``liblsr_hip.so`` (C ABI: include/lsr_rasterizer.h, include/lsr_adapter.h, include/lsr_latent.h, include/lsr_ply.h,
-include/lsr_sh_rotate.h, include/lsr_depth_head.h, include/lsr_scene.h, include/lsr_loss.h).
+include/lsr_sh_rotate.h, include/lsr_depth_head.h, include/lsr_scene.h, include/lsr_loss.h, include/lsr_density.h).
 
 The library is built in-tree by ``latentsplat_amd/csrc/Makefile`` (``__graft_entry__.build()``).
 There is no CPU fallback: if the shared object is missing or not loadable this module raises, and
@@ -193,6 +193,21 @@ class PhotometricDims(C.Structure):  # lsr_photometric_dims (include/lsr_loss.h)
                 ("lambda_dssim", C.c_float), ("cov_norm", C.c_float), ("crop", C.c_int32), ("reserved0", C.c_int32)]
 
 
+class DensifyParams(C.Structure):   # lsr_densify_params (include/lsr_density.h)
+    _fields_ = [("grad_threshold", C.c_float), ("dense_extent", C.c_float), ("min_opacity", C.c_float),
+                ("max_screen_size", C.c_float), ("world_limit", C.c_float), ("n_split", C.c_int32),
+                ("reserved0", C.c_int32), ("reserved1", C.c_int32)]
+
+
+class DensifyTable(C.Structure):    # lsr_densify_table
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("width", C.c_int32), ("rule", C.c_int32)]
+
+
+DENSIFY_COPY, DENSIFY_ZERO_NEW, DENSIFY_XYZ, DENSIFY_SCALING = 0, 1, 2, 3   # lsr_densify_table.rule
+DENSIFY_KEPT, DENSIFY_CLONE, DENSIFY_CHILD0 = 0, 1, 2                      # map kinds
+DENSIFY_MAX_SPLIT, DENSIFY_MAX_TABLES, DENSIFY_MAX_WIDTH, DENSIFY_KIND_SHIFT, DENSIFY_MAX_ROWS = 8, 24, 4096, 28, 1 << 28
+
+
 def sh_rotate_table_floats(degree: int) -> int:
     """LSR_SH_ROTATE_TABLE_FLOATS: sum of (2l+1)^2 over l <= degree."""
     return (degree + 1) * (2 * degree + 1) * (2 * degree + 3) // 3
@@ -212,6 +227,7 @@ EXPORTS = (
     "lsr_depth_head_forward", "lsr_depth_head_backward",
     "lsr_scene_activate_forward", "lsr_scene_activate_backward",
     "lsr_photometric_workspace_bytes", "lsr_photometric_forward", "lsr_photometric_backward",
+    "lsr_density_accumulate", "lsr_densify_workspace_bytes", "lsr_densify_plan", "lsr_densify_apply",
 )
 
 _lib = None
@@ -353,6 +369,14 @@ def load():
     lib.lsr_photometric_forward.argtypes = [C.POINTER(PhotometricDims), P, P, P, P, P, P, P, P, P]
     lib.lsr_photometric_backward.restype = C.c_int
     lib.lsr_photometric_backward.argtypes = [C.POINTER(PhotometricDims), P, P, P, P, P, P]
+    lib.lsr_density_accumulate.restype = C.c_int
+    lib.lsr_density_accumulate.argtypes = [I32, I64, P, P, P, P, P, P]
+    lib.lsr_densify_workspace_bytes.restype = SZ
+    lib.lsr_densify_workspace_bytes.argtypes = [I64]
+    lib.lsr_densify_plan.restype = C.c_int
+    lib.lsr_densify_plan.argtypes = [I64, P, P, P, P, P, C.POINTER(DensifyParams), P, I64, P, P, P]
+    lib.lsr_densify_apply.restype = C.c_int
+    lib.lsr_densify_apply.argtypes = [I64, I64, P, P, I32, C.POINTER(DensifyTable), I32, P, P, P, I64, P]
     _lib = lib
     return lib
 

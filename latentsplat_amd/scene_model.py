@@ -233,6 +233,27 @@ class GaussianScene(nn.Module):
     def num_gaussians(self) -> int:
         return self._xyz.shape[0]
 
+    def replace_parameters_(self, **tensors: Tensor) -> None:
+        """Install fresh ``nn.Parameter``s of a new row count (what densification and pruning produce): all six of
+        ``xyz, features_dc, features_rest, opacity, scaling, rotation``, float32, on the scene's device, with the
+        scene's SH width.  The tensors are taken as they are (detached, not copied); ``active_sh_degree`` and
+        ``max_sh_degree`` stay.  An optimizer that held the old parameters has to be re-keyed by the caller
+        (:meth:`latentsplat_amd.density.DensityControl.densify_and_prune` does)."""
+        names = ("xyz", "features_dc", "features_rest", "opacity", "scaling", "rotation")
+        if set(tensors) != set(names):
+            raise _lib.LsrError(f"replace_parameters_ takes exactly {', '.join(names)}")
+        n = tensors["xyz"].shape[0]
+        rest = self._features_rest.shape[1]
+        shapes = dict(xyz=(n, 3), features_dc=(n, 1, 3), features_rest=(n, rest, 3), opacity=(n, 1), scaling=(n, 3),
+                      rotation=(n, 4))
+        for k in names:
+            t = tensors[k]
+            if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != shapes[k] or t.device != self._xyz.device:
+                raise _lib.LsrError(f"replace_parameters_: {k} must be a float32 tensor of shape {shapes[k]} on {self._xyz.device}")
+        for k in names:
+            old = getattr(self, "_" + k)
+            setattr(self, "_" + k, nn.Parameter(tensors[k].detach().contiguous(), requires_grad=old.requires_grad))
+
     def oneup_sh_degree(self) -> None:
         """Render one more SH band, up to the stored ones."""
         if self.active_sh_degree < self.max_sh_degree:

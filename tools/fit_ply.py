@@ -16,10 +16,21 @@
 
 The learning rates default to the published trainer's customary ones (position 1.6e-4 x extent, f_dc 2.5e-3, f_rest
 f_dc / 20, opacity 5e-2, scaling 5e-3, rotation 1e-3; Adam eps 1e-15).  They are defaults, not measurements: nothing here
-tuned them.  No densification.
+tuned them.
+
+Adaptive density control is off by default.  `--densify-interval I` with I > 0 turns it on: every step
+renders with a per-view `(V, n, 3)` `means2D` and feeds its gradient and the radii to `DensityControl.update`; every I-th
+step after `--densify-from` and up to `--densify-until` runs `DensityControl.densify_and_prune` (clone, split, prune; the
+optimizer's moments travel with their rows), with size pruning (20 px, 0.1 x extent) once the first opacity reset is
+behind; every `--opacity-reset-interval`-th step resets the opacities.  The loss here is a mean over the V views, so each
+view's gradient is 1 / V of the published single-view one and `--densify-grad-threshold` defaults to `2e-4 / views`:
+like the learning rates, a default and not a measurement.  `--drop F` removes a seeded fraction F of the Gaussians after
+the targets are rendered, so that there is something to grow back.  With densification on, `fit.json` also holds
+`gaussians_first`, `gaussians_last` and `densify_events` (the counts of every event).
 
 usage: python tools/fit_ply.py scene.ply --out DIR [--views 8] [--size 256] [--steps 200] [--noise 1.0] [--seed 0] [--distance 2.5]
-                               [--lambda-dssim 0.0]"""
+                               [--lambda-dssim 0.0] [--drop 0.0] [--densify-interval 0] [--densify-from 0] [--densify-until STEPS]
+                               [--densify-grad-threshold 2e-4/VIEWS] [--min-opacity 0.005] [--opacity-reset-interval 0]"""
 from __future__ import annotations
 
 import argparse
@@ -62,11 +73,22 @@ def main(argv=None) -> dict:
     ap.add_argument("--lr-opacity", type=float, default=5e-2, help="(a default, not a measurement)")
     ap.add_argument("--lr-scaling", type=float, default=5e-3, help="(a default, not a measurement)")
     ap.add_argument("--lr-rotation", type=float, default=1e-3, help="(a default, not a measurement)")
+    ap.add_argument("--drop", type=float, default=0.0,
+                    help="remove this fraction of the Gaussians (seeded) after the targets are rendered (default 0: none)")
+    ap.add_argument("--densify-interval", type=int, default=0, help="densify and prune every this many steps (0: never, the default)")
+    ap.add_argument("--densify-from", type=int, default=0, help="no densification before this step")
+    ap.add_argument("--densify-until", type=int, default=None, help="no densification (and no statistics) after this step (default: --steps)")
+    ap.add_argument("--densify-grad-threshold", type=float, default=None,
+                    help="on the mean view-space gradient (default 2e-4 / --views: a default, not a measurement)")
+    ap.add_argument("--min-opacity", type=float, default=0.005, help="Gaussians below it are pruned at a densification")
+    ap.add_argument("--opacity-reset-interval", type=int, default=0, help="reset the opacities every this many steps (0: never)")
     a = ap.parse_args(argv)
     if a.steps < 1 or a.views < 1:
         sys.exit("fit_ply needs at least one step and one view")
     if not 0.0 <= a.lambda_dssim <= 1.0:
         sys.exit("--lambda-dssim must be in [0, 1]")
+    if not 0.0 <= a.drop < 1.0 or a.densify_interval < 0 or a.opacity_reset_interval < 0:
+        sys.exit("--drop must be in [0, 1); the intervals must not be negative")
     if not torch.cuda.is_available():
         sys.exit("fit_ply needs an MI355X: no ROCm device is visible (there is no CPU fallback)")
     from latentsplat_amd.rasterizer import build_view_table
@@ -84,11 +106,23 @@ def main(argv=None) -> dict:
         for name, p in scene.named_parameters():
             if name in noise and a.noise:
                 p.add_((torch.randn(p.shape, generator=gen) * (a.noise * noise[name])).to(dev))
+        if a.drop > 0.0:
+            keep = (torch.rand(scene.num_gaussians, generator=gen) >= a.drop).to(dev)
+            scene.replace_parameters_(**{name[1:]: p.detach()[keep] for name, p in scene.named_parameters()})
     rates = dict(_xyz=a.lr_position * float(extent), _features_dc=a.lr_dc,
                  _features_rest=a.lr_dc / 20 if a.lr_rest is None else a.lr_rest, _opacity=a.lr_opacity,
                  _scaling=a.lr_scaling, _rotation=a.lr_rotation)
     groups = [dict(params=[p], lr=rates[name], name=name) for name, p in scene.named_parameters() if p.numel()]
     opt = torch.optim.Adam(groups, lr=0.0, eps=1e-15)
+    gen_dev = torch.Generator(device=dev).manual_seed(a.seed)      # the children's offsets at a split
+    densify = a.densify_interval > 0
+    control = None
+    if densify:
+        from latentsplat_amd.density import DensityControl
+        control = DensityControl(scene)
+        until = a.steps if a.densify_until is None else a.densify_until
+        threshold = 2e-4 / a.views if a.densify_grad_threshold is None else a.densify_grad_threshold
+    gaussians_first, events = scene.num_gaussians, []
     warm = min(WARMUP_STEPS, a.steps // 2)
     losses = []
     t0 = None
@@ -97,11 +131,24 @@ def main(argv=None) -> dict:
             torch.cuda.synchronize(dev)
             t0 = time.perf_counter()
         opt.zero_grad(set_to_none=True)
-        render = scene.render(views, a.size, a.size)[0]
+        if densify and step < until:
+            means2D = torch.zeros((a.views, scene.num_gaussians, 3), device=dev, requires_grad=True)
+            render, _, _, _, radii = scene.render(views, a.size, a.size, means2D=means2D)
+        else:
+            means2D, render = None, scene.render(views, a.size, a.size)[0]
         loss = photometric_loss(render, target, a.lambda_dssim) if a.lambda_dssim > 0 else (render - target).abs().mean()
         loss.backward()
         opt.step()
         losses.append(loss.detach())
+        if means2D is not None:
+            done = step + 1
+            control.update(means2D.grad, radii)
+            if done > a.densify_from and done % a.densify_interval == 0:
+                size = 20.0 if a.opacity_reset_interval and done > a.opacity_reset_interval else 0.0
+                counts = control.densify_and_prune(opt, threshold, a.min_opacity, float(extent), size, generator=gen_dev)
+                events.append(dict(step=done, **counts))
+        if control is not None and a.opacity_reset_interval and (step + 1) % a.opacity_reset_interval == 0:
+            control.reset_opacity(opt)
     torch.cuda.synchronize(dev)
     per_step = (time.perf_counter() - t0) / (a.steps - warm)
     os.makedirs(a.out, exist_ok=True)
@@ -109,6 +156,8 @@ def main(argv=None) -> dict:
     res = dict(loss_first=float(losses[0]), loss_last=float(losses[-1]), steps=a.steps, ms_per_step=1e3 * per_step,
                timed_steps=a.steps - warm, gaussians=scene.num_gaussians, sh_degree=scene.max_sh_degree, views=a.views,
                size=a.size, noise=a.noise, seed=a.seed, extent=float(extent), lambda_dssim=a.lambda_dssim)
+    if densify:
+        res.update(gaussians_first=gaussians_first, gaussians_last=scene.num_gaussians, densify_events=events)
     with open(os.path.join(a.out, "fit.json"), "w") as f:
         json.dump(res, f, indent=1)
     print(json.dumps(res))
