@@ -1,5 +1,5 @@
 """ctypes binding of ``liblsr_hip.so`` (C ABI: include/lsr_rasterizer.h, include/lsr_adapter.h, include/lsr_latent.h, include/lsr_ply.h,
-include/lsr_sh_rotate.h, include/lsr_depth_head.h, include/lsr_scene.h, include/lsr_loss.h, include/lsr_density.h).
+include/lsr_sh_rotate.h, include/lsr_depth_head.h, include/lsr_scene.h, include/lsr_loss.h, include/lsr_density.h, include/lsr_optim.h).
 
 The library is built in-tree by ``latentsplat_amd/csrc/Makefile`` (``__graft_entry__.build()``).
 There is no CPU fallback: if the shared object is missing or not loadable this module raises, and
@@ -208,6 +208,15 @@ DENSIFY_KEPT, DENSIFY_CLONE, DENSIFY_CHILD0 = 0, 1, 2                      # map
 DENSIFY_MAX_SPLIT, DENSIFY_MAX_TABLES, DENSIFY_MAX_WIDTH, DENSIFY_KIND_SHIFT, DENSIFY_MAX_ROWS = 8, 24, 4096, 28, 1 << 28
 
 
+class AdamTable(C.Structure):       # lsr_adam_table (include/lsr_optim.h)
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("rows", C.c_int64), ("width", C.c_int32), ("reserved", C.c_int32), ("beta1", C.c_float), ("beta2", C.c_float),
+                ("one_minus_beta1", C.c_float), ("one_minus_beta2", C.c_float), ("eps", C.c_float), ("step_size", C.c_float), ("inv_sqrt_bc2", C.c_float), ("reserved_f", C.c_float)]
+
+
+ADAM_MAX_TABLES, ADAM_MAX_WIDTH, ADAM_MAX_ROWS = 24, 4096, 1 << 40   # LSR_ADAM_MAX_*
+
+
 def sh_rotate_table_floats(degree: int) -> int:
     """LSR_SH_ROTATE_TABLE_FLOATS: sum of (2l+1)^2 over l <= degree."""
     return (degree + 1) * (2 * degree + 1) * (2 * degree + 3) // 3
@@ -228,6 +237,7 @@ EXPORTS = (
     "lsr_scene_activate_forward", "lsr_scene_activate_backward",
     "lsr_photometric_workspace_bytes", "lsr_photometric_forward", "lsr_photometric_backward",
     "lsr_density_accumulate", "lsr_densify_workspace_bytes", "lsr_densify_plan", "lsr_densify_apply",
+    "lsr_adam_step",
 )
 
 _lib = None
@@ -377,6 +387,8 @@ def load():
     lib.lsr_densify_plan.argtypes = [I64, P, P, P, P, P, C.POINTER(DensifyParams), P, I64, P, P, P]
     lib.lsr_densify_apply.restype = C.c_int
     lib.lsr_densify_apply.argtypes = [I64, I64, P, P, I32, C.POINTER(DensifyTable), I32, P, P, P, I64, P]
+    lib.lsr_adam_step.restype = C.c_int
+    lib.lsr_adam_step.argtypes = [C.POINTER(AdamTable), I32, P, I64, P]
     _lib = lib
     return lib
 

@@ -18,6 +18,13 @@ The learning rates default to the published trainer's customary ones (position 1
 f_dc / 20, opacity 5e-2, scaling 5e-3, rotation 1e-3; Adam eps 1e-15).  They are defaults, not measurements: nothing here
 tuned them.
 
+`--optimizer fused` takes the step with `latentsplat_amd.SceneAdam`: all six tensors in one HIP launch.
+`--optimizer sparse` is the same without bias correction and with the mask `visible_from_radii` of the step's render: only
+Gaussians that were on screen in one of the step's views are updated.  `--optimizer torch`, the default, is
+`torch.optim.Adam` as before.  `--lr-position-final F` turns on the customary exponential schedule of the position rate
+(`expon_lr`): from `--lr-position` to F, both times the extent, over `--lr-position-max-steps` steps (default `--steps`).
+`fit.json` names the optimizer.
+
 Adaptive density control is off by default.  `--densify-interval I` with I > 0 turns it on: every step
 renders with a per-view `(V, n, 3)` `means2D` and feeds its gradient and the radii to `DensityControl.update`; every I-th
 step after `--densify-from` and up to `--densify-until` runs `DensityControl.densify_and_prune` (clone, split, prune; the
@@ -30,7 +37,8 @@ the targets are rendered, so that there is something to grow back.  With densifi
 
 usage: python tools/fit_ply.py scene.ply --out DIR [--views 8] [--size 256] [--steps 200] [--noise 1.0] [--seed 0] [--distance 2.5]
                                [--lambda-dssim 0.0] [--drop 0.0] [--densify-interval 0] [--densify-from 0] [--densify-until STEPS]
-                               [--densify-grad-threshold 2e-4/VIEWS] [--min-opacity 0.005] [--opacity-reset-interval 0]"""
+                               [--densify-grad-threshold 2e-4/VIEWS] [--min-opacity 0.005] [--opacity-reset-interval 0]
+                               [--optimizer torch|fused|sparse] [--lr-position-final F] [--lr-position-max-steps S]"""
 from __future__ import annotations
 
 import argparse
@@ -73,6 +81,12 @@ def main(argv=None) -> dict:
     ap.add_argument("--lr-opacity", type=float, default=5e-2, help="(a default, not a measurement)")
     ap.add_argument("--lr-scaling", type=float, default=5e-3, help="(a default, not a measurement)")
     ap.add_argument("--lr-rotation", type=float, default=1e-3, help="(a default, not a measurement)")
+    ap.add_argument("--optimizer", choices=("torch", "fused", "sparse"), default="torch",
+                    help="torch: torch.optim.Adam (the default); fused: SceneAdam, one HIP launch; sparse: SceneAdam without bias "
+                         "correction, updating only the Gaussians visible in the step's views")
+    ap.add_argument("--lr-position-final", type=float, default=None,
+                    help="times the extent: decay the position rate exponentially to this (default: constant rate)")
+    ap.add_argument("--lr-position-max-steps", type=int, default=None, help="steps over which the position rate decays (default: --steps)")
     ap.add_argument("--drop", type=float, default=0.0,
                     help="remove this fraction of the Gaussians (seeded) after the targets are rendered (default 0: none)")
     ap.add_argument("--densify-interval", type=int, default=0, help="densify and prune every this many steps (0: never, the default)")
@@ -89,10 +103,13 @@ def main(argv=None) -> dict:
         sys.exit("--lambda-dssim must be in [0, 1]")
     if not 0.0 <= a.drop < 1.0 or a.densify_interval < 0 or a.opacity_reset_interval < 0:
         sys.exit("--drop must be in [0, 1); the intervals must not be negative")
+    if a.lr_position_final is not None and (a.lr_position_final < 0.0 or (a.lr_position_max_steps or a.steps) < 1):
+        sys.exit("--lr-position-final must not be negative and --lr-position-max-steps must be positive")
     if not torch.cuda.is_available():
         sys.exit("fit_ply needs an MI355X: no ROCm device is visible (there is no CPU fallback)")
     from latentsplat_amd.rasterizer import build_view_table
     from latentsplat_amd.losses import photometric_loss
+    from latentsplat_amd.optim import SceneAdam, expon_lr, visible_from_radii
     from latentsplat_amd.scene_model import GaussianScene
     dev = torch.device("cuda:0")
     scene = GaussianScene.from_ply(a.ply, dev)
@@ -113,7 +130,12 @@ def main(argv=None) -> dict:
                  _features_rest=a.lr_dc / 20 if a.lr_rest is None else a.lr_rest, _opacity=a.lr_opacity,
                  _scaling=a.lr_scaling, _rotation=a.lr_rotation)
     groups = [dict(params=[p], lr=rates[name], name=name) for name, p in scene.named_parameters() if p.numel()]
-    opt = torch.optim.Adam(groups, lr=0.0, eps=1e-15)
+    if a.optimizer == "torch":
+        opt = torch.optim.Adam(groups, lr=0.0, eps=1e-15)
+    else:
+        opt = SceneAdam(groups, lr=0.0, eps=1e-15, bias_correction=a.optimizer == "fused")
+    sparse = a.optimizer == "sparse"
+    xyz_group = next(g for g in opt.param_groups if g["name"] == "_xyz")
     gen_dev = torch.Generator(device=dev).manual_seed(a.seed)      # the children's offsets at a split
     densify = a.densify_interval > 0
     control = None
@@ -135,10 +157,17 @@ def main(argv=None) -> dict:
             means2D = torch.zeros((a.views, scene.num_gaussians, 3), device=dev, requires_grad=True)
             render, _, _, _, radii = scene.render(views, a.size, a.size, means2D=means2D)
         else:
-            means2D, render = None, scene.render(views, a.size, a.size)[0]
+            means2D = None
+            render, _, _, _, radii = scene.render(views, a.size, a.size)
         loss = photometric_loss(render, target, a.lambda_dssim) if a.lambda_dssim > 0 else (render - target).abs().mean()
         loss.backward()
-        opt.step()
+        if a.lr_position_final is not None:
+            xyz_group["lr"] = expon_lr(step, a.lr_position * float(extent), a.lr_position_final * float(extent),
+                                       a.lr_position_max_steps or a.steps)
+        if sparse:
+            opt.step(visibility=visible_from_radii(radii))
+        else:
+            opt.step()
         losses.append(loss.detach())
         if means2D is not None:
             done = step + 1
@@ -155,7 +184,7 @@ def main(argv=None) -> dict:
     scene.save_ply(os.path.join(a.out, "point_cloud.ply"))
     res = dict(loss_first=float(losses[0]), loss_last=float(losses[-1]), steps=a.steps, ms_per_step=1e3 * per_step,
                timed_steps=a.steps - warm, gaussians=scene.num_gaussians, sh_degree=scene.max_sh_degree, views=a.views,
-               size=a.size, noise=a.noise, seed=a.seed, extent=float(extent), lambda_dssim=a.lambda_dssim)
+               size=a.size, noise=a.noise, seed=a.seed, extent=float(extent), lambda_dssim=a.lambda_dssim, optimizer=a.optimizer)
     if densify:
         res.update(gaussians_first=gaussians_first, gaussians_last=scene.num_gaussians, densify_events=events)
     with open(os.path.join(a.out, "fit.json"), "w") as f:
