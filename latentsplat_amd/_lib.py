@@ -292,9 +292,8 @@ def load():
     lib.lsr_get_layout.argtypes = [C.POINTER(Dims), I64, C.POINTER(Layout)]
     lib.lsr_build_views.restype = C.c_int
     lib.lsr_build_views.argtypes = [I32, P, P, P, P, P, I32, I32, P, P]
-    if hasattr(lib, "lsr_build_views_depth"):  # (absent from an earlier build selected with LSR_LIB for an A/B)
-        lib.lsr_build_views_depth.restype = C.c_int
-        lib.lsr_build_views_depth.argtypes = [I32, P, P, P, P, P, I32, I32, I32, P, P]
+    lib.lsr_build_views_depth.restype = C.c_int
+    lib.lsr_build_views_depth.argtypes = [I32, P, P, P, P, P, I32, I32, I32, P, P]
     lib.lsr_pack_view.restype = C.c_int
     lib.lsr_pack_view.argtypes = [P, P, P, P, C.c_float, C.c_float, P, P, P, P]
     lib.lsr_forward_prepare.restype = C.c_int
@@ -324,12 +323,11 @@ def load():
     lib.lsr_profile_stage_name.restype = C.c_char_p
     lib.lsr_profile_stage_name.argtypes = [C.c_int]
     lib.lsr_profile_read.argtypes = [C.POINTER(C.c_double), C.POINTER(I64)]
-    if hasattr(lib, "lsr_debug_set_knob"):    # (absent from a previous round's build selected with LSR_LIB for an A/B)
-        lib.lsr_debug_set_knob.restype = C.c_int
-        lib.lsr_debug_set_knob.argtypes = [C.c_char_p, C.c_int]
-        lib.lsr_set_projection_contraction.restype = C.c_int
-        lib.lsr_set_projection_contraction.argtypes = [C.c_int]
-        lib.lsr_get_projection_contraction.restype = C.c_int
+    lib.lsr_debug_set_knob.restype = C.c_int
+    lib.lsr_debug_set_knob.argtypes = [C.c_char_p, C.c_int]
+    lib.lsr_set_projection_contraction.restype = C.c_int
+    lib.lsr_set_projection_contraction.argtypes = [C.c_int]
+    lib.lsr_get_projection_contraction.restype = C.c_int
     lib.lsr_adapter_forward.restype = C.c_int
     lib.lsr_adapter_forward.argtypes = [C.POINTER(AdapterDims), C.POINTER(AdapterInputs),
                                         C.POINTER(AdapterOutputs), P]

@@ -110,7 +110,7 @@ uint32_t lsr::segment_capacity(const lsr_dims &d) {
     return (uint32_t)cap;
 }
 
-// Development knobs (LSR_FWD_VARIANT, LSR_SH_PLACEMENT, ...): read from the environment once per process and knob,
+// Development knobs (LSR_FWD_ROWS, LSR_SH_PLACEMENT, ...): read from the environment once per process and knob,
 // then served from a table — no getenv on the launch path.  lsr_debug_set_knob overrides a table entry at run time
 // (kernel A/B experiments in one process; not part of the product surface).
 namespace {
@@ -277,7 +277,7 @@ static int forward_tail(const lsr_dims &d, const lsr_inputs &in, char *geom, cha
         LSR_HIP(hipEventRecord(side.fork, s));
         LSR_HIP(hipStreamWaitEvent(side.stream, side.fork, 0));
         forked = true;      // from here on the side stream is joined back whatever happens (the workspace is the caller's)
-        hipError_t e = launch_clear_grad(d, out.radii, (char *)out.grad_ws, side.stream);
+        hipError_t e = launch_clear_grad(d, (char *)out.grad_ws, side.stream);
         if (e == hipSuccess) e = hipEventRecord(side.join, side.stream);
         if (e != hipSuccess) { (void)hipStreamSynchronize(side.stream); return fail_hip(e); }
     }
@@ -287,7 +287,7 @@ static int forward_tail(const lsr_dims &d, const lsr_inputs &in, char *geom, cha
         if (ej != hipSuccess) { (void)hipStreamSynchronize(side.stream); return fail_hip(ej); }
     }
     LSR_STAGE("render_forward", s, er);
-    if (clears && !forked) LSR_HIP(launch_clear_grad(d, out.radii, (char *)out.grad_ws, s));
+    if (clears && !forked) LSR_HIP(launch_clear_grad(d, (char *)out.grad_ws, s));
     return LSR_OK;
 }
 
@@ -754,10 +754,10 @@ static int backward_impl(const lsr_dims *d, const lsr_inputs *in, const void *ge
     if (d->feat_channels > 0 && !gin->features) return LSR_ENULL;
     if (num_pairs > 0 && !bin_ws) return LSR_ENULL;
     // zero the packed gradient records the compositing backward accumulates into (unless the forward did: LSR_FWD_CLEARS_GRAD)
-    if (!(d->forward_flags & LSR_FWD_CLEARS_GRAD)) LSR_HIP(launch_clear_grad(*d, radii, (char *)grad_ws, s));
+    if (!(d->forward_flags & LSR_FWD_CLEARS_GRAD)) LSR_HIP(launch_clear_grad(*d, (char *)grad_ws, s));
     if (num_pairs > 0)
         LSR_STAGE("render_backward", s, launch_render_backward(*d, *in, (const char *)geom_ws, (const char *)bin_ws, num_pairs,
-                                       (const char *)img_ws, *fwd, *gout, (char *)grad_ws, *gin, s));
+                                       (const char *)img_ws, *fwd, *gout, (char *)grad_ws, s));
     // Geometry and SH backward: one launch each, all scenes (view groups) of the call at once (the scene in
     // blockIdx.y).  Both add into the scene's mean gradients, hence in stream order.
     if (!cam) {

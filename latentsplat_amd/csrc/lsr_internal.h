@@ -40,7 +40,8 @@ struct BinLayout {
 // (k_preprocess_bwd turns the moments into dL/d mean, conic, opacity: the conic and the opacity
 // are constant over a Gaussian's pixels.)  16 floats (one 64-byte line) for <= 8 payload
 // channels, 32 for <= 12, 64 beyond.
-// per-SIMD-bin queue heads of the compositing kernels (experiment knobs LSR_FWD_BINQ / LSR_BWD_BINQ): room for 4096 bins
+// per-SIMD-bin queue heads of the compositing FORWARD (LSR_FWD_BINQ; only the forward uses a bin queue now): room for 4096 bins.
+// GradLayout keeps as many bytes of cleared slack, the retired backward bin queue's, so that the gradient workspace keeps its size.
 constexpr size_t kBinQueueBytes = 4096 * 4;
 // Work items are handed to the compositing waves costliest first.  The tile scan orders them by the tile's pair count (all it
 // has).  A forward that a backward follows knows better when it is done: the RECORD compositing kernel has counted the lock-step
@@ -329,11 +330,11 @@ hipError_t launch_render_forward(const lsr_dims &d, const lsr_inputs &in, const 
                                  hipStream_t s);
 // Zeroes what the compositing backward accumulates into: the gradient records, the queue / zero-line slack and, in
 // deterministic mode, the fixed-point records.
-hipError_t launch_clear_grad(const lsr_dims &d, const int32_t *radii, char *grad, hipStream_t s);
+hipError_t launch_clear_grad(const lsr_dims &d, char *grad, hipStream_t s);
 hipError_t launch_render_backward(const lsr_dims &d, const lsr_inputs &in, const char *geom,
                                   const char *bin, int64_t num_pairs, const char *img,
                                   const lsr_outputs &fwd, const lsr_out_grads &gout, char *grad,
-                                  const lsr_in_grads &gin, hipStream_t s);
+                                  hipStream_t s);
 // ---- camera gradients (lsr_backward_views) ----
 // The geometry and SH backward kernels plain-store one partial record of dL/d(view record) per (view, 64-Gaussian chunk)
 // (the wave's sum: the view is wave-uniform in both); two small kernels (views.hip) add them up in a fixed order.  No float

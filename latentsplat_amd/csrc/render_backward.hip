@@ -62,7 +62,6 @@ struct RenderBwdParams {
     const uint32_t *items2;       // the same items ordered by their true cost (k_sort_tiles; valid when header[kHdrOrder2Valid])
     const uint32_t *header;       // geometry-workspace header (item count)
     uint32_t *queue;              // work-queue head (zeroed with the gradient workspace)
-    uint32_t *bin_queue;          // per-SIMD-bin queue heads (LSR_BWD_BINQ=1, experiment), or nullptr: one global queue
     int prio_pct;                 // issue priority by progress: percentage of the launch's mean tile list (0 = off; see the kernel)
     const uint32_t *item_flags;   // [2 V T] kItemFlagSteep per half-tile item, written by the forward compositing kernel (lsr_internal.h)
     int rev_mode;                 // which items are walked BACK TO FRONT: 0 none, 1 all, 2 the steep ones (and all when the forward left no flags)
@@ -127,12 +126,12 @@ __device__ __forceinline__ float2_b group_reduce_pairs(float2_b p0, float2_b p1,
 
 __device__ __forceinline__ void atomic_add_f32(float *addr, float v) { unsafeAtomicAdd(addr, v); }
 
-// WPB = waves per workgroup, WGS = workgroups per compute unit: as many resident waves as the per-wave LDS slice
+// WPB = waves per workgroup, one workgroup per compute unit: as many resident waves as the per-wave LDS slice
 // and the register budget allow (the kernel is bound by instruction issue and the latencies of its dependent
 // chain: DESIGN.md).
 // SPLIT: the list-splitting instance for launches that cannot fill the wave slots (see the item loop); the plain instance
 // carries none of its tests.
-template <int NCHP, bool DEPTH_GRAD, int WPB, int WGS, bool SPLIT>
+template <int NCHP, bool DEPTH_GRAD, int WPB, bool SPLIT>
 __global__ void __launch_bounds__(LSR_WAVE * WPB)
 k_render_bwd(RenderBwdParams p) {
     // float4 per staged entry: odd (conflict-free staging stores) except for the 8-channel payload, whose
@@ -183,8 +182,8 @@ k_render_bwd(RenderBwdParams p) {
     const int l16 = lane & 15, fgrp = lane >> 4;           // flush: one 64-byte record per 16 lanes
     const int fcol = kPackRow ? (l16 < 8 ? l16 : l16 - 2) : l16;
 
-    const uint32_t simd_bins = (uint32_t)p.num_cus * 4u, slots = (uint32_t)p.num_cus * (uint32_t)(WPB * WGS);
-    const uint32_t vwave = (uint32_t)wid + (uint32_t)WPB * (blockIdx.x / (uint32_t)p.num_cus);   // 0 .. WPB*WGS-1
+    const uint32_t simd_bins = (uint32_t)p.num_cus * 4u, slots = (uint32_t)p.num_cus * (uint32_t)WPB;
+    const uint32_t vwave = (uint32_t)wid + (uint32_t)WPB * (blockIdx.x / (uint32_t)p.num_cus);   // 0 .. WPB-1 (one workgroup per CU: the quotient is 0)
     const uint32_t bin = (blockIdx.x % (uint32_t)p.num_cus) * 4u + (vwave & 3u);
     const uint32_t j0 = vwave >> 2;
     // Issue priority by progress (round 5).  A wave walks its list at HIGH priority (s_setprio 3) until prio_target entries are
@@ -211,17 +210,11 @@ k_render_bwd(RenderBwdParams p) {
             if (qi >= num_items) continue;
         } else {
             if (num_items <= slots) break;
+            // one global queue: per-SIMD-bin lists as in k_render_fwd measured no gain here (0.570 -> 0.568 ms at 16 views x 300 k,
+            // +2.5 % on opaque scenes, +3 % at 10^6 Gaussians)
             uint32_t t = 0;
-            if (p.bin_queue) {
-                // per-SIMD-bin lists as in k_render_fwd (LSR_BWD_BINQ=1; measured no gain here: 0.570 -> 0.568 ms at 16 views x 300 k,
-                // +2.5 % on opaque scenes, +3 % at 10^6 Gaussians: off by default)
-                if (lane == 0) t = atomicAdd(p.bin_queue + bin, 1u);
-                const uint32_t k = (uint32_t)(WPB * WGS) / 4u + __builtin_amdgcn_readfirstlane(t);
-                qi = (k & 1u) ? (k + 1u) * simd_bins - 1u - bin : k * simd_bins + bin;
-            } else {
-                if (lane == 0) t = atomicAdd(p.queue, 1u);
-                qi = slots + __builtin_amdgcn_readfirstlane(t);
-            }
+            if (lane == 0) t = atomicAdd(p.queue, 1u);
+            qi = slots + __builtin_amdgcn_readfirstlane(t);
             if (qi >= num_items) break;
         }
         qi = __builtin_amdgcn_readfirstlane(qi);
@@ -571,16 +564,15 @@ __global__ void __launch_bounds__(256) k_fixed_to_float(const long long *__restr
 // — radii > 0, 68 % of them — with a kernel that reads the radius and stores under the test: the forward + backward step
 // got 0.01-0.03 ms SLOWER than with this plain streaming clear of everything; what stayed is that the per-Gaussian backward
 // kernels no longer READ the records of culled slots: GradLayout's zero line.)
-hipError_t launch_clear_grad(const lsr_dims &d, const int32_t *radii, char *grad, hipStream_t s) {
-    (void)radii;
+hipError_t launch_clear_grad(const lsr_dims &d, char *grad, hipStream_t s) {
     return launch_clear(grad, grad_layout(d).total, s);
 }
 
-template <int NCHP, bool DG, int WPB, int WGS>
+template <int NCHP, bool DG, int WPB>
 static void launch_variant(RenderBwdParams p, uint64_t items, hipStream_t s) {
     // list splitting: as many waves per half-tile item (a power of two, at most 8) as the launch's wave slots hold.
     // LSR_BWD_PARTS = log2 of the number of parts forces it (0: never split).
-    const uint64_t slots = (uint64_t)p.num_cus * WPB * WGS;
+    const uint64_t slots = (uint64_t)p.num_cus * WPB;
     const int forced = env_int("LSR_BWD_PARTS", -1);
     int pl = 0;
     if (forced >= 0) pl = forced > 3 ? 3 : forced;
@@ -589,14 +581,14 @@ static void launch_variant(RenderBwdParams p, uint64_t items, hipStream_t s) {
     // issue priority by progress (see the kernel): on for the instances it was measured to help, LSR_BWD_PRIO_PCT >= 0 forces a value
     const int prio_knob = env_int("LSR_BWD_PRIO_PCT", -1);
     p.prio_pct = prio_knob >= 0 ? prio_knob : ((!DG && (NCHP == 4 || (NCHP == 8 && pl > 0))) ? 18 : 0);
-    if (pl) hipLaunchKernelGGL((k_render_bwd<NCHP, DG, WPB, WGS, true>), dim3(p.num_cus * WGS), dim3(LSR_WAVE * WPB), 0, s, p);
-    else hipLaunchKernelGGL((k_render_bwd<NCHP, DG, WPB, WGS, false>), dim3(p.num_cus * WGS), dim3(LSR_WAVE * WPB), 0, s, p);
+    if (pl) hipLaunchKernelGGL((k_render_bwd<NCHP, DG, WPB, true>), dim3(p.num_cus), dim3(LSR_WAVE * WPB), 0, s, p);
+    else hipLaunchKernelGGL((k_render_bwd<NCHP, DG, WPB, false>), dim3(p.num_cus), dim3(LSR_WAVE * WPB), 0, s, p);
 }
 
 hipError_t launch_render_backward(const lsr_dims &d, const lsr_inputs &in, const char *geom,
                                   const char *bin, int64_t num_pairs, const char *img,
                                   const lsr_outputs &fwd, const lsr_out_grads &gout, char *grad,
-                                  const lsr_in_grads &gin, hipStream_t s) {
+                                  hipStream_t s) {
     const GeomLayout L = geom_layout(d);
     const ImgLayout I = img_layout(d);
     const BinLayout B = bin_layout(d, num_pairs, 0);
@@ -620,34 +612,29 @@ hipError_t launch_render_backward(const lsr_dims &d, const lsr_inputs &in, const
     const bool det = deterministic_backward();
     p.rec_fixed = det ? (long long *)(grad + R.fixed) : nullptr;
     p.queue = (uint32_t *)(grad + R.fixed - 512);   // the zeroed slack behind the float records
-    p.bin_queue = (env_int("LSR_BWD_BINQ", 0) && 4 * p.num_cus <= (int)(kBinQueueBytes / 4)) ? (uint32_t *)(grad + R.fixed - 512 - kBinQueueBytes) : nullptr;
     p.item_flags = (const uint32_t *)(geom + L.item_flags);
     {   // LSR_BWD_REV: 0 never walk back to front, 1 always, 2 (default) the items the forward flagged as steep
         const int rm = env_int("LSR_BWD_REV", 2);
         p.rev_mode = rm < 0 || rm > 2 ? 2 : rm;
     }
-    (void)gin;
     const int nch = (p.has_color ? 3 : 0) + d.feat_channels;
     const int nchp = nch <= 4 ? 4 : (nch <= 8 ? 8 : (nch <= 12 ? 12 : 36));
     const bool dg = gout.depth != nullptr;
     prof_begin(kStRenderBwd, s);
     const uint64_t items = 2ull * (uint64_t)d.num_views * (uint64_t)p.T;   // upper bound of the header's item count
-#define LSR_RB(N, WPB, WGS)                                      \
-    do {                                                         \
-        if (dg) launch_variant<N, true, WPB, WGS>(p, items, s);  \
-        else launch_variant<N, false, WPB, WGS>(p, items, s);    \
+#define LSR_RB(N, WPB)                                      \
+    do {                                                    \
+        if (dg) launch_variant<N, true, WPB>(p, items, s);  \
+        else launch_variant<N, false, WPB>(p, items, s);    \
     } while (0)
-    // LSR_BWD_VARIANT (development knob, read once) selects the alternatives measured in DESIGN.md
-    const int variant = env_int("LSR_BWD_VARIANT", 0);
-    if (nchp == 4 && !dg) { if (variant == 1) launch_variant<4, false, 10, 2>(p, items, s); else if (variant == 2) launch_variant<4, false, 12, 1>(p, items, s); else launch_variant<4, false, 16, 1>(p, items, s); }
-    else if (nchp == 4) LSR_RB(4, 16, 1);
+    if (nchp == 4) LSR_RB(4, 16);
     // packed table rows: 16 waves per CU fit with 64-byte staged entries.  (Round 4: this instance shows 34 % LDS bank-conflict
     // cycles — eight lane groups reading eight 64-byte records start in one of only four bank groups — but the odd
     // 80-byte stride costs a wave: 15 waves 0.969-0.977 ms, 14 waves 1.02 against 0.945-0.954 at configs[4].)
-    else if (nchp == 8 && !dg) launch_variant<8, false, 16, 1>(p, items, s);
-    else if (nchp == 8) launch_variant<8, true, 12, 1>(p, items, s);
-    else if (nchp == 12) LSR_RB(12, 8, 1);
-    else LSR_RB(36, 4, 1);
+    else if (nchp == 8 && !dg) launch_variant<8, false, 16>(p, items, s);
+    else if (nchp == 8) launch_variant<8, true, 12>(p, items, s);
+    else if (nchp == 12) LSR_RB(12, 8);
+    else LSR_RB(36, 4);
 #undef LSR_RB
     if (det) {   // fixed-point sums -> the float records the next stages read
         const size_t n = (size_t)d.num_views * (size_t)d.num_gaussians * (size_t)R.rec_floats;

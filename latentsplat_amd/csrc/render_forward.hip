@@ -115,11 +115,8 @@ struct RenderFwdParams {
 // -1/255 (kept in a register pair instead).  Lossless for the backward by construction: an (entry, sub-block) without a
 // contributing pixel has alpha T = 0 everywhere on the sub-block, i.e. no gradient (the stopping entry of a pixel is not
 // blended and lies beyond the pixel's n_contrib).
-// EMU (timing experiments only, LSR_FWD_VARIANT 5 / 6; WRONG images): every item is walked by EMU waves, wave k taking the
-// k-th share of its batches from T = 1 — what a split along the list through the linearity of the composite would
-// execute, without its partial writes and combine pass (profiles/r06_ab_knobs.md: the bound of that design).
-template <int NCHP, int WPB, bool RECORD = false, int EMU = 0>
-__global__ void __launch_bounds__(LSR_WAVE * WPB, WPB == 14 ? 7 : ((RECORD && WPB == 12) ? 6 : 1))   // (2 x 14 waves: 72 registers, seven waves per SIMD; the RECORD instance of 2 x 12 must stay within six)
+template <int NCHP, int WPB, bool RECORD = false>
+__global__ void __launch_bounds__(LSR_WAVE * WPB, (RECORD && WPB == 12) ? 6 : 1)   // (the RECORD instance of 2 x 12 must stay within six waves per SIMD)
 k_render_fwd(RenderFwdParams p) {
     // Staged entries, one record per list entry: (x, y, a2, c2) (b2, log2(255 o), z / 255, -1 / 255) payload / 255 ...
     // (lsr_blend.h: the loop works in units of 255 alpha).  The odd float4 stride keeps the per-lane staging
@@ -153,8 +150,7 @@ k_render_fwd(RenderFwdParams p) {
 #pragma unroll
         for (int c4 = 0; c4 < NCHP / 4; ++c4) s_ent[LSR_WAVE][2 + c4] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     }
-    constexpr uint32_t kEmu = EMU ? (uint32_t)EMU : 1u;     // (a divisor the EMU = 0 instances can compile)
-    const uint32_t num_items = p.num_items * kEmu;
+    const uint32_t num_items = p.num_items;
     const int coff = p.has_color ? 3 : 0;
     // RECORD: -1/255 lives in a register pair (the staged record's fourth word of its second quad collects the hit bits)
     float2_t kz2 = float2_t{-kInv255, -kInv255};
@@ -207,20 +203,14 @@ k_render_fwd(RenderFwdParams p) {
         uint32_t trace_iters = 0;   // lock-step iterations of this item
 #endif
         qi = __builtin_amdgcn_readfirstlane(qi);
-        const uint32_t item = p.items[qi / kEmu];
+        const uint32_t item = p.items[qi];
         const uint32_t vt = item & kItemTileMask, half = item >> kItemHalfShift;
         const int tile = (int)(vt % (uint32_t)p.T), v = (int)(vt / (uint32_t)p.T);
         const int tx0 = (tile % p.gx) * LSR_TILE, ty0 = (tile / p.gx) * LSR_TILE + 8 * (int)half;
         const size_t vG = (size_t)v * p.G;
         const uint32_t tstart = p.tile_start[vt], tn = p.tile_start[vt + 1] - tstart;
-        uint32_t hn = p.half_count[2 * (size_t)vt + half];
+        const uint32_t hn = p.half_count[2 * (size_t)vt + half];
         const uint32_t *hlist = p.half_list + 2 * (size_t)tstart + (size_t)half * tn;
-        if (EMU) {   // this wave's share of the item's batches
-            const uint32_t nbat = (hn + LSR_WAVE - 1) / LSR_WAVE, part = qi % kEmu;
-            const uint32_t b0 = part * nbat / kEmu, b1 = (part + 1u) * nbat / kEmu;
-            hlist += b0 * LSR_WAVE;
-            hn = min(hn, b1 * LSR_WAVE) - min(hn, b0 * LSR_WAVE);
-        }
 
         // per-pixel state of the lane's two pixels as register pairs (pixel 0, pixel 1): the blend runs on
         // packed f32 instructions across the two pixels
@@ -976,7 +966,7 @@ __device__ __forceinline__ void render_subblock_item(const RenderFwdParams &p, c
 }
 
 // The launch for small view batches: the p.quad_items costliest half-tile items are rendered as eight SUB-BLOCK items
-// each, the others as two ROW items each.  The launcher asks for all or none (see there); the mix is an experiment knob.
+// each, the others as two ROW items each.  The launcher asks for all or none (see there).
 template <int NCHP, int WPB, bool REC = false>
 __global__ void __launch_bounds__(LSR_WAVE * WPB, (REC && WPB == 12) ? 6 : 1)   // (the REC instances must stay within six waves per SIMD: 2 x 12 per CU)
 k_render_fwd_small(RenderFwdParams p) {
@@ -1072,7 +1062,7 @@ hipError_t launch_render_forward(const lsr_dims &d, const lsr_inputs &in, const 
     p.quad_items = 0;
     p.all_live = env_int("LSR_FWD_LIVE", 1) == 0 ? 1u : 0u;
 #ifdef LSR_ENABLE_TRACE
-    const int64_t max_items = 2 * (int64_t)p.T * d.num_views * 4;     // (x 4: the EMU instances' units)
+    const int64_t max_items = 2 * (int64_t)p.T * d.num_views * 4;     // (x 4: slack; tools/trace_forward.py drops the records that stayed zero)
     const char *trace_path = getenv("LSR_TRACE");
     if (trace_path) {
         (void)hipMalloc((void **)&p.trace, (size_t)max_items * 48);
@@ -1081,7 +1071,6 @@ hipError_t launch_render_forward(const lsr_dims &d, const lsr_inputs &in, const 
 #endif
     prof_begin(kStRenderFwd, s);
     // WPC = resident waves per CU = (workgroups per CU) x WPB: as many as registers and LDS slices allow.
-    // LSR_FWD_VARIANT (development knob, read once) selects the alternatives measured in DESIGN.md.
 #define LSR_RF(N, WPB, WPC)                                                                                \
     do {                                                                                                   \
         p.waves_per_cu = (WPC);                                                                            \
@@ -1093,21 +1082,19 @@ hipError_t launch_render_forward(const lsr_dims &d, const lsr_inputs &in, const 
     const int rows_knob = env_int("LSR_FWD_ROWS", -1), quad_knob = env_int("LSR_FWD_QUAD", -1);
     const uint64_t slots = (uint64_t)p.num_cus * 24u;
     // Forwards that a backward follows narrow the render lists for it while they composite: row items do it per row
-    // (render_row_item REC), sub-block items cannot (eight waves share an entry's word and one view's backward gains little).
-    // LSR_FWD_ROWREC = 0: the round-6a policy (3+ views of 256 x 256 take the half-tile RECORD kernel instead of row items).
-    const bool for_bwd = (d.forward_flags & LSR_FWD_FOR_BACKWARD) != 0 && p.ip.all_bits == 0u && env_int("LSR_FWD_RECORD", 1) != 0;
-    const bool row_rec = env_int("LSR_FWD_ROWREC", 1) != 0;
-    const bool small = (nchp == 4 || nchp == 8) && (quad_knob == 1 || (rows_knob >= 0 ? rows_knob != 0 : (2ull * p.num_items <= slots && !(for_bwd && !row_rec && 4ull * p.num_items >= slots))));
+    // (render_row_item REC), sub-block items cannot (eight waves share an entry's word and one view's backward gains little);
+    // the half-tile kernel does it per half tile (k_render_fwd RECORD).  The entries must carry bits: scenes of up to 2^24
+    // Gaussians.  LSR_FWD_RECORD=0 turns it off.
+    const bool record = (d.forward_flags & LSR_FWD_FOR_BACKWARD) != 0 && p.ip.all_bits == 0u && env_int("LSR_FWD_RECORD", 1) != 0;
+    const bool small = (nchp == 4 || nchp == 8) && (quad_knob == 1 || (rows_knob >= 0 ? rows_knob != 0 : 2ull * p.num_items <= slots));
     if (small) {
         p.waves_per_cu = 24;
         // Sub-block items for ALL items or none.  (Measured: the costliest (slots - 2 items) / 6 items as sub-block items next
         // to row items for the rest fill every slot, and with six waves per SIMD the sub-block items — the longest lists —
         // take twice as long as alone: V = 2 0.085 against 0.068 ms for row items only, V = 4 0.088 / 0.078, configs[3]
-        // 0.160 / 0.136.  LSR_FWD_QUAD_ITEMS = n forces n leading items for experiments.)
-        const int forced = env_int("LSR_FWD_QUAD_ITEMS", -1);
+        // 0.160 / 0.136.)
         p.quad_items = quad_knob == 0 ? 0u : ((quad_knob == 1 || 8ull * p.num_items <= slots) ? p.num_items : 0u);
-        if (forced >= 0) p.quad_items = std::min<uint32_t>(p.num_items, (uint32_t)forced);
-        const bool rec = for_bwd && row_rec && p.quad_items == 0u;
+        const bool rec = record && p.quad_items == 0u;
         if (nchp == 4) {
             if (rec) hipLaunchKernelGGL((k_render_fwd_small<4, 12, true>), dim3(p.num_cus * 2), dim3(LSR_WAVE * 12), 0, s, p);
             else hipLaunchKernelGGL((k_render_fwd_small<4, 12>), dim3(p.num_cus * 2), dim3(LSR_WAVE * 12), 0, s, p);
@@ -1118,10 +1105,6 @@ hipError_t launch_render_forward(const lsr_dims &d, const lsr_inputs &in, const 
         prof_end(kStRenderFwd, s);
         return hipGetLastError();
     }
-    const int variant = env_int("LSR_FWD_VARIANT", 0);
-    // a forward that a backward will follow (lsr_dims::forward_flags) refines the lists' sub-block bits while it composites
-    // (k_render_fwd RECORD; the entries must carry bits: scenes of up to 2^24 Gaussians).  LSR_FWD_RECORD=0 turns it off.
-    const bool record = (d.forward_flags & LSR_FWD_FOR_BACKWARD) != 0 && p.ip.all_bits == 0u && env_int("LSR_FWD_RECORD", 1) != 0;
 #define LSR_RFR(N, WPB, WPC)                                                                               \
     do {                                                                                                   \
         p.waves_per_cu = (WPC);                                                                            \
@@ -1146,18 +1129,14 @@ hipError_t launch_render_forward(const lsr_dims &d, const lsr_inputs &in, const 
     }
     // the backward's work order from the RECORD forward's own iteration counts (k_order_items), when an item is a sizeable
     // part of a wave slot's work in the backward (more items than its 16 x CUs slots, at most kMaxReorderItems).  LSR_REORDER=0: off
-    const bool reorder = record && (nchp == 8 || (nchp == 4 && variant == 0)) && p.num_items > 16u * (uint32_t)p.num_cus &&
+    const bool reorder = record && (nchp == 4 || nchp == 8) && p.num_items > 16u * (uint32_t)p.num_cus &&
                          p.num_items <= kMaxReorderItems && env_int("LSR_REORDER", 1) != 0;
     if (reorder) p.item_cost = (uint32_t *)(const_cast<char *>(geom) + L.item_cost);
-    if (record && nchp == 4 && variant == 0) LSR_RFR(4, 12, 24);
+    if (record && nchp == 4) LSR_RFR(4, 12, 24);
     else if (record && nchp == 8) LSR_RFR(8, 16, 16);
-    else
-    if (nchp == 4 && (variant == 5 || variant == 6)) {   // timing emulation of list splitting (see the kernel's EMU parameter)
-        p.waves_per_cu = 24;
-        if (variant == 5) hipLaunchKernelGGL((k_render_fwd<4, 12, false, 2>), dim3(p.num_cus * 2), dim3(LSR_WAVE * 12), 0, s, p);
-        else hipLaunchKernelGGL((k_render_fwd<4, 12, false, 4>), dim3(p.num_cus * 2), dim3(LSR_WAVE * 12), 0, s, p);
-    } else
-    if (nchp == 4) { if (variant == 2) LSR_RF(4, 16, 16); else if (variant == 3) LSR_RF(4, 14, 28); else LSR_RF(4, 12, 24); }   // 2 x 12 waves per CU: 0.245 vs 0.281 ms per 16 views with 16
+    // 2 x 12 waves per CU, six per SIMD: 0.245 vs 0.281 ms per 16 views with one 16-wave workgroup, and 0.222 vs 0.264 ms
+    // with 2 x 14 (seven per SIMD, 72 registers)
+    else if (nchp == 4) LSR_RF(4, 12, 24);
     // 7 / 8 channels (colour + 4 latent channels: the reference's configs[3] / [4] payload; 7.3 KB of LDS and 90 VGPRs per
     // wave).  Round 4 measured 2 x 10 waves per CU (what LDS and registers allow at most) and 2 x 8: configs[3] 0.1426 /
     // 0.1367 ms against 0.1377 for one 16-wave workgroup, configs[4] 0.3019 / 0.3006 / 0.3017 — no gain, the shape stays.

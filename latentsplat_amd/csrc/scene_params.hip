@@ -9,11 +9,10 @@
 //   * the SH concat (forward) / split (backward) is a loop over the elements of the big span, lane j element j, four
 //     independent elements per lane in flight.  The three dc floats per Gaussian — 12 bytes every 12 K — would be the one
 //     sparse access; they cross through LDS instead (their span is read / written densely on its own);
-//   * the geometry runs one Gaussian per lane: the quaternion is one 16-byte access; the 3- and 6-float rows are either
-//     accessed directly by their lane (GEO_LDS = false: the three / six strided dword accesses of a wave together cover
-//     whole cache lines, and the lines stay in the vector cache between them) or staged through LDS with lane-dense
-//     accesses as ply.hip does (GEO_LDS = true).  LSR_SCENE_GEOM_LDS picks the variant (a development knob; DESIGN.md
-//     section 2.10 has the measurement behind the default).
+//   * the geometry runs one Gaussian per lane: the quaternion is one 16-byte access; the 3- and 6-float rows are
+//     accessed directly by their lane: the three / six strided dword accesses of a wave together cover whole cache
+//     lines, and the lines stay in the vector cache between them (DESIGN.md section 2.10 has the measurement against
+//     staging them through LDS as ply.hip does).
 // Indices are 64-bit from the chunk base on (3 K n passes 2^31 near 30 M Gaussians); inside a chunk they are ints
 // (at most 75 * 256).  One owner per output element, no atomics: two calls give the same bits.
 #include <math.h>
@@ -35,12 +34,10 @@ __device__ __forceinline__ void scene_copy(float *__restrict__ dst, const float 
     for (int j = tid; j < count; j += kSceneChunk) dst[j] = src ? src[j] : 0.0f;
 }
 
-template <int K, bool GEO_LDS>
+template <int K>
 __global__ __launch_bounds__(kSceneChunk) void k_scene_fwd(int64_t n, float m, lsr_scene_params p, lsr_scene_outputs o) {
     constexpr int E = 3 * K, G = kSceneChunk;
     __shared__ float s_dc[3 * G];
-    __shared__ float s_ls[GEO_LDS ? 3 * G : 1];      // log-scales in, scales out (each lane its own three)
-    __shared__ float s_cov[GEO_LDS ? 6 * G : 1];
     const int tid = threadIdx.x;
     const int64_t chunks = (n + G - 1) / G;
     const bool geo = o.cov3D || o.scales || o.rotations;
@@ -48,7 +45,6 @@ __global__ __launch_bounds__(kSceneChunk) void k_scene_fwd(int64_t n, float m, l
         const int64_t g0 = c * G;
         const int nr = (int)(n - g0 < (int64_t)G ? n - g0 : (int64_t)G);
         if (o.shs && K > 1) scene_copy(s_dc, p.features_dc + g0 * 3, 3 * nr, tid);
-        if (GEO_LDS && geo) scene_copy(s_ls, p.scaling + g0 * 3, 3 * nr, tid);
         __syncthreads();
 
         if (o.shs) {
@@ -86,10 +82,10 @@ __global__ __launch_bounds__(kSceneChunk) void k_scene_fwd(int64_t n, float m, l
             const float inv = 1.0f / sqrtf(w * w + x * x + y * y + z * z);
             w *= inv; x *= inv; y *= inv; z *= inv;
             if (o.rotations) reinterpret_cast<float4 *>(o.rotations)[gi] = make_float4(w, x, y, z);
-            const float *ls = GEO_LDS ? s_ls + 3 * tid : p.scaling + 3 * gi;
+            const float *ls = p.scaling + 3 * gi;
             const float s0 = m * expf(ls[0]), s1 = m * expf(ls[1]), s2 = m * expf(ls[2]);
             if (o.scales) {
-                float *sc = GEO_LDS ? s_ls + 3 * tid : o.scales + 3 * gi;
+                float *sc = o.scales + 3 * gi;
                 sc[0] = s0; sc[1] = s1; sc[2] = s2;
             }
             if (o.cov3D) {
@@ -97,7 +93,7 @@ __global__ __launch_bounds__(kSceneChunk) void k_scene_fwd(int64_t n, float m, l
                 const float m00 = (1.0f - 2.0f * (y * y + z * z)) * s0, m01 = 2.0f * (x * y - w * z) * s1, m02 = 2.0f * (x * z + w * y) * s2;
                 const float m10 = 2.0f * (x * y + w * z) * s0, m11 = (1.0f - 2.0f * (x * x + z * z)) * s1, m12 = 2.0f * (y * z - w * x) * s2;
                 const float m20 = 2.0f * (x * z - w * y) * s0, m21 = 2.0f * (y * z + w * x) * s1, m22 = (1.0f - 2.0f * (x * x + y * y)) * s2;
-                float *st = GEO_LDS ? s_cov + 6 * tid : o.cov3D + 6 * gi;
+                float *st = o.cov3D + 6 * gi;
                 st[0] = m00 * m00 + m01 * m01 + m02 * m02;
                 st[1] = m00 * m10 + m01 * m11 + m02 * m12;
                 st[2] = m00 * m20 + m01 * m21 + m02 * m22;
@@ -106,22 +102,15 @@ __global__ __launch_bounds__(kSceneChunk) void k_scene_fwd(int64_t n, float m, l
                 st[5] = m20 * m20 + m21 * m21 + m22 * m22;
             }
         }
-        if (GEO_LDS && (o.cov3D || o.scales)) {
-            __syncthreads();
-            if (o.cov3D) scene_copy(o.cov3D + g0 * 6, s_cov, 6 * nr, tid);
-            if (o.scales) scene_copy(o.scales + g0 * 3, s_ls, 3 * nr, tid);
-        }
-        __syncthreads();                                 // the LDS arrays are the next chunk's
+        __syncthreads();                                 // s_dc is the next chunk's
     }
 }
 
-template <int K, bool GEO_LDS>
+template <int K>
 __global__ __launch_bounds__(kSceneChunk) void k_scene_bwd(int64_t n, float m, lsr_scene_params p, lsr_scene_out_grads g,
                                                           lsr_scene_in_grads d) {
     constexpr int E = 3 * K, G = kSceneChunk;
     __shared__ float s_dc[3 * G];
-    __shared__ float s_ls[GEO_LDS ? 3 * G : 1];      // log-scales in, their gradients out (each lane its own three)
-    __shared__ float s_g[GEO_LDS ? 6 * G : 1];       // upstream covariance gradients
     const int tid = threadIdx.x;
     const int64_t chunks = (n + G - 1) / G;
     const bool geo = d.scaling || d.rotation;
@@ -131,10 +120,6 @@ __global__ __launch_bounds__(kSceneChunk) void k_scene_bwd(int64_t n, float m, l
     for (int64_t c = blockIdx.x; c < chunks; c += gridDim.x) {
         const int64_t g0 = c * G;
         const int nr = (int)(n - g0 < (int64_t)G ? n - g0 : (int64_t)G);
-        if (GEO_LDS && geo) {
-            scene_copy(s_ls, p.scaling + g0 * 3, 3 * nr, tid);
-            scene_copy(s_g, g.cov3D ? g.cov3D + g0 * 6 : nullptr, 6 * nr, tid);
-        }
         // colour SH: the forward's re-layout run backwards
         if (d_rest_all) {
             float *drest = d_rest_all + g0 * (E - 3);
@@ -190,16 +175,11 @@ __global__ __launch_bounds__(kSceneChunk) void k_scene_bwd(int64_t n, float m, l
             float w = q.x, x = q.y, y = q.z, z = q.w;
             const float inv = 1.0f / sqrtf(w * w + x * x + y * y + z * z);
             w *= inv; x *= inv; y *= inv; z *= inv;
-            const float *ls = GEO_LDS ? s_ls + 3 * tid : p.scaling + 3 * gi;
+            const float *ls = p.scaling + 3 * gi;
             const float s[3] = {m * expf(ls[0]), m * expf(ls[1]), m * expf(ls[2])};
             float gc[6];
-            if (GEO_LDS) {
 #pragma unroll
-                for (int k = 0; k < 6; ++k) gc[k] = s_g[6 * tid + k];
-            } else {
-#pragma unroll
-                for (int k = 0; k < 6; ++k) gc[k] = g.cov3D ? g.cov3D[6 * gi + k] : 0.0f;
-            }
+            for (int k = 0; k < 6; ++k) gc[k] = g.cov3D ? g.cov3D[6 * gi + k] : 0.0f;
             // G: the diagonal as given, each off-diagonal entry half of its packed value
             const float Gm[9] = {gc[0], 0.5f * gc[1], 0.5f * gc[2],
                                  0.5f * gc[1], gc[3], 0.5f * gc[4],
@@ -219,7 +199,7 @@ __global__ __launch_bounds__(kSceneChunk) void k_scene_bwd(int64_t n, float m, l
                 dR[k] = dm0 * s[k]; dR[3 + k] = dm1 * s[k]; dR[6 + k] = dm2 * s[k];
             }
             if (d.scaling) {
-                float *o3 = GEO_LDS ? s_ls + 3 * tid : d.scaling + 3 * gi;
+                float *o3 = d.scaling + 3 * gi;
                 o3[0] = dls[0]; o3[1] = dls[1]; o3[2] = dls[2];
             }
             if (d.rotation) {
@@ -236,11 +216,7 @@ __global__ __launch_bounds__(kSceneChunk) void k_scene_bwd(int64_t n, float m, l
                     make_float4((dw - dot * w) * inv, (dx - dot * x) * inv, (dy - dot * y) * inv, (dz - dot * z) * inv);
             }
         }
-        if (GEO_LDS && d.scaling) {
-            __syncthreads();
-            scene_copy(d.scaling + g0 * 3, s_ls, 3 * nr, tid);
-        }
-        __syncthreads();                                 // the LDS arrays are the next chunk's
+        __syncthreads();                                 // s_dc is the next chunk's
     }
 }
 
@@ -258,28 +234,26 @@ static unsigned scene_blocks(int64_t n) {
     return (unsigned)std::min<int64_t>((n + kSceneChunk - 1) / kSceneChunk, kSceneMaxBlocks);
 }
 
-template <bool GEO_LDS>
 static void launch_scene_fwd(const lsr_scene_dims &d, const lsr_scene_params &p, const lsr_scene_outputs &o, hipStream_t s) {
     const dim3 grid(scene_blocks(d.n)), block(kSceneChunk);
     switch (d.sh_coeffs) {
-        case 1: hipLaunchKernelGGL((k_scene_fwd<1, GEO_LDS>), grid, block, 0, s, d.n, d.scale_modifier, p, o); break;
-        case 4: hipLaunchKernelGGL((k_scene_fwd<4, GEO_LDS>), grid, block, 0, s, d.n, d.scale_modifier, p, o); break;
-        case 9: hipLaunchKernelGGL((k_scene_fwd<9, GEO_LDS>), grid, block, 0, s, d.n, d.scale_modifier, p, o); break;
-        case 16: hipLaunchKernelGGL((k_scene_fwd<16, GEO_LDS>), grid, block, 0, s, d.n, d.scale_modifier, p, o); break;
-        default: hipLaunchKernelGGL((k_scene_fwd<25, GEO_LDS>), grid, block, 0, s, d.n, d.scale_modifier, p, o); break;
+        case 1: hipLaunchKernelGGL((k_scene_fwd<1>), grid, block, 0, s, d.n, d.scale_modifier, p, o); break;
+        case 4: hipLaunchKernelGGL((k_scene_fwd<4>), grid, block, 0, s, d.n, d.scale_modifier, p, o); break;
+        case 9: hipLaunchKernelGGL((k_scene_fwd<9>), grid, block, 0, s, d.n, d.scale_modifier, p, o); break;
+        case 16: hipLaunchKernelGGL((k_scene_fwd<16>), grid, block, 0, s, d.n, d.scale_modifier, p, o); break;
+        default: hipLaunchKernelGGL((k_scene_fwd<25>), grid, block, 0, s, d.n, d.scale_modifier, p, o); break;
     }
 }
 
-template <bool GEO_LDS>
 static void launch_scene_bwd(const lsr_scene_dims &d, const lsr_scene_params &p, const lsr_scene_out_grads &g,
                              const lsr_scene_in_grads &o, hipStream_t s) {
     const dim3 grid(scene_blocks(d.n)), block(kSceneChunk);
     switch (d.sh_coeffs) {
-        case 1: hipLaunchKernelGGL((k_scene_bwd<1, GEO_LDS>), grid, block, 0, s, d.n, d.scale_modifier, p, g, o); break;
-        case 4: hipLaunchKernelGGL((k_scene_bwd<4, GEO_LDS>), grid, block, 0, s, d.n, d.scale_modifier, p, g, o); break;
-        case 9: hipLaunchKernelGGL((k_scene_bwd<9, GEO_LDS>), grid, block, 0, s, d.n, d.scale_modifier, p, g, o); break;
-        case 16: hipLaunchKernelGGL((k_scene_bwd<16, GEO_LDS>), grid, block, 0, s, d.n, d.scale_modifier, p, g, o); break;
-        default: hipLaunchKernelGGL((k_scene_bwd<25, GEO_LDS>), grid, block, 0, s, d.n, d.scale_modifier, p, g, o); break;
+        case 1: hipLaunchKernelGGL((k_scene_bwd<1>), grid, block, 0, s, d.n, d.scale_modifier, p, g, o); break;
+        case 4: hipLaunchKernelGGL((k_scene_bwd<4>), grid, block, 0, s, d.n, d.scale_modifier, p, g, o); break;
+        case 9: hipLaunchKernelGGL((k_scene_bwd<9>), grid, block, 0, s, d.n, d.scale_modifier, p, g, o); break;
+        case 16: hipLaunchKernelGGL((k_scene_bwd<16>), grid, block, 0, s, d.n, d.scale_modifier, p, g, o); break;
+        default: hipLaunchKernelGGL((k_scene_bwd<25>), grid, block, 0, s, d.n, d.scale_modifier, p, g, o); break;
     }
 }
 
@@ -299,8 +273,7 @@ int lsr_scene_activate_forward(const lsr_scene_dims *dims, const lsr_scene_param
     if (!params->features_dc || !params->opacity || !params->scaling || !params->rotation) return LSR_ENULL;
     if ((reinterpret_cast<uintptr_t>(params->rotation) | reinterpret_cast<uintptr_t>(out->rotations)) & 15) return LSR_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    if (env_int("LSR_SCENE_GEOM_LDS", 0)) launch_scene_fwd<true>(*dims, *params, *out, s);
-    else launch_scene_fwd<false>(*dims, *params, *out, s);
+    launch_scene_fwd(*dims, *params, *out, s);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
     return LSR_OK;
@@ -316,8 +289,7 @@ int lsr_scene_activate_backward(const lsr_scene_dims *dims, const lsr_scene_para
     if (!params->opacity || !params->scaling || !params->rotation) return LSR_ENULL;
     if ((reinterpret_cast<uintptr_t>(params->rotation) | reinterpret_cast<uintptr_t>(din->rotation)) & 15) return LSR_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    if (env_int("LSR_SCENE_GEOM_LDS", 0)) launch_scene_bwd<true>(*dims, *params, *dout, *din, s);
-    else launch_scene_bwd<false>(*dims, *params, *dout, *din, s);
+    launch_scene_bwd(*dims, *params, *dout, *din, s);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
     return LSR_OK;

@@ -427,20 +427,15 @@ class _RasterizeViews(torch.autograd.Function):
                 if not done:
                     SPECULATION_STATS["exact"] += 1
                     d.forward_flags &= ~_lib.FWD_FRONT_DONE      # (a speculative forward that fell short is run again from the start)
-                    try:
-                        _lib.check(lib.lsr_forward_prepare(C.byref(d), C.byref(inp), _ptr(geom), _ptr(radii),
-                                                           C.byref(npairs), C.byref(maxtile), stream),
-                                   "lsr_forward_prepare")
-                        # the largest pair-count dependent allocation (the likeliest out-of-memory site of a forward)
-                        binws = torch.empty(lib.lsr_binning_workspace_bytes(C.byref(d), npairs.value, maxtile.value), **u8)
-                        _lib.check(lib.lsr_forward_render(C.byref(d), C.byref(inp), _ptr(geom), _ptr(binws), _ptr(img),
-                                                          npairs.value, maxtile.value, C.byref(outs), stream),
-                                   "lsr_forward_render")
-                        layout_pairs = npairs.value
-                    except BaseException:
-                        # (a no-op since ABI v7 — every launch of a forward is on the caller's stream — kept for v6 libraries)
-                        lib.lsr_forward_abandon(stream)
-                        raise
+                    _lib.check(lib.lsr_forward_prepare(C.byref(d), C.byref(inp), _ptr(geom), _ptr(radii),
+                                                       C.byref(npairs), C.byref(maxtile), stream),
+                               "lsr_forward_prepare")
+                    # the largest pair-count dependent allocation (the likeliest out-of-memory site of a forward)
+                    binws = torch.empty(lib.lsr_binning_workspace_bytes(C.byref(d), npairs.value, maxtile.value), **u8)
+                    _lib.check(lib.lsr_forward_render(C.byref(d), C.byref(inp), _ptr(geom), _ptr(binws), _ptr(img),
+                                                      npairs.value, maxtile.value, C.byref(outs), stream),
+                               "lsr_forward_render")
+                    layout_pairs = npairs.value
                 if _SPECULATE:
                     _estimate_update(shape_key, npairs.value, maxtile.value)
             if debug:

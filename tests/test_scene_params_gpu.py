@@ -62,29 +62,6 @@ def test_forward_and_backward_match_the_restatement(hip_device, n, K, m):
         assert np.array_equal(o.detach().cpu().numpy(), got[k]), k
 
 
-@pytest.mark.parametrize("n,K", [(257, 16), (1031, 25), (300, 1)])
-def test_the_staged_geometry_variant_computes_the_same(hip_device, n, K):
-    """LSR_SCENE_GEOM_LDS (a development knob): the 3- and 6-float rows staged through LDS instead of accessed by their
-    lane.  Held to the same bars."""
-    from latentsplat_amd.scene_model import activate_backward, activate_forward
-    p = sref.make_params(n, K, seed=5 * n + K)
-    up = sref.make_upstream(n, K, seed=n)
-    t = _dev(p, hip_device)
-    g = [torch.from_numpy(up[k]).to(hip_device) for k in ("shs", "opacities", "cov3D")]
-    results = []
-    try:
-        for knob in (0, 1):
-            _lib.set_knob("LSR_SCENE_GEOM_LDS", knob)
-            results.append((_np(activate_forward(*t, scale_modifier=0.5)), _np(activate_backward(*t, *g, scale_modifier=0.5))))
-    finally:
-        _lib.set_knob("LSR_SCENE_GEOM_LDS", 0)
-    for a, b in zip(results[0], results[1]):                    # the copies and the per-lane scalars: the same bits
-        for k in set(a) & {"shs", "opacities", "rotations", "features_dc", "features_rest", "opacity", "rotation"}:
-            assert np.array_equal(a[k], b[k]), k
-    ref.assert_matches(results[1][0], sref.expected(p, 0.5))
-    sref.assert_backward_matches(results[1][1], p, up, 0.5, show=f"staged n={n} K={K}")
-
-
 def test_optional_pieces(hip_device):
     from latentsplat_amd.scene_model import activate_backward, activate_forward, activate_scene
     n, K, m = 300, 9, 0.5

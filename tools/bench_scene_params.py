@@ -14,10 +14,9 @@ of `--samples` (>= 20) after `--warmup` calls, the variants alternated sample by
 must move per Gaussian: the forward reads (3 K + 8) * 4 and writes (3 K + 7) * 4 bytes, the backward reads (3 K + 7 + 8) * 4
 and writes (3 K + 8) * 4; the rate is that over the time, as a fraction of the 6.3 TB/s achievable HBM rate of the
 MI355X.  `fused_*_first_half_ms` / `_second_half_ms` (the medians of the two halves of the samples) and min / max say
-how far the kernel's own figure moved inside the run.  `--geometry` also times the other geometry layout (the
-LSR_SCENE_GEOM_LDS development knob: the 3- and 6-float rows staged through LDS instead of accessed by their lane).
+how far the kernel's own figure moved inside the run.
 
-usage: python tools/bench_scene_params.py [--samples 30] [--warmup 5] [--inner 5] [--geometry] [--json [profiles/scene_params_bench.json]]"""
+usage: python tools/bench_scene_params.py [--samples 30] [--warmup 5] [--inner 5] [--json [profiles/scene_params_bench.json]]"""
 from __future__ import annotations
 
 import argparse
@@ -82,7 +81,6 @@ def main():
     ap.add_argument("--samples", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--inner", type=int, default=5)
-    ap.add_argument("--geometry", action="store_true", help="also time the other geometry layout (rows staged through LDS)")
     ap.add_argument("--json", nargs="?", const=os.path.join(ROOT, "profiles", "scene_params_bench.json"), default=None)
     a = ap.parse_args()
     if a.samples < 20:
@@ -150,15 +148,8 @@ def main():
                               torch_min_ms=min(ts), torch_max_ms=max(ts), fused_bytes_per_s=rate,
                               fused_fraction_of_achievable_hbm=rate / HBM_ACHIEVABLE,
                               faster_than_torch_in_every_sample=bool(max(tf) < min(ts)))
-            if a.geometry:
-                _lib.set_knob("LSR_SCENE_GEOM_LDS", 1)
-                entry[leg]["fused_ms_geometry_through_lds"] = _median_of(fused, dev, a)
-                _lib.set_knob("LSR_SCENE_GEOM_LDS", 0)
-                entry[leg]["fused_ms_geometry_direct_again"] = _median_of(fused, dev, a)
             print(f"n={n:8d} {leg:17s} fused {mf:7.4f} ms [{min(tf):.4f}, {max(tf):.4f}]  torch {ms:8.4f} ms [{min(ts):.4f}, {max(ts):.4f}]  "
-                  f"x{ms / mf:.1f}  model {nb[leg] / 1e6:.1f} MB -> {rate / 1e12:.2f} TB/s = {100 * rate / HBM_ACHIEVABLE:.1f} % of 6.3 TB/s"
-                  + (f"  through LDS {entry[leg]['fused_ms_geometry_through_lds']:.4f} ms, direct again "
-                     f"{entry[leg]['fused_ms_geometry_direct_again']:.4f} ms" if a.geometry else ""), flush=True)
+                  f"x{ms / mf:.1f}  model {nb[leg] / 1e6:.1f} MB -> {rate / 1e12:.2f} TB/s = {100 * rate / HBM_ACHIEVABLE:.1f} % of 6.3 TB/s", flush=True)
         entry["forward_backward"]["fused_autograd_ms"] = _median_of(public_fwd_bwd, dev, a)
         print(f"n={n:8d} public path (activate_scene + autograd.backward) {entry['forward_backward']['fused_autograd_ms']:.4f} ms", flush=True)
         print(f"n={n:8d} fused vs torch, max relative difference: " + ", ".join(f"{k} {v:.1e}" for k, v in diff.items()), flush=True)
