@@ -57,7 +57,8 @@ __host__ __device__ inline int latent_bands(const lsr_latent_dims &d, bool want_
 
 __global__ __launch_bounds__(kLatentThreads) void k_latent_fwd(lsr_latent_dims d, lsr_latent_inputs in,
                                                                 lsr_latent_outputs out) {
-    extern __shared__ float col[];                       // [width] column sums of this band
+    extern __shared__ float col[];                       // [kLatentThreads * 4]: the row lanes' partial sums, then
+                                                         // [width] column sums of this band
     const int H = d.height, W = d.width, C = d.channels, cc = d.color_channels;
     const bool want_z = out.z != nullptr;
     const int bands = latent_bands(d, want_z);
@@ -132,12 +133,18 @@ __global__ __launch_bounds__(kLatentThreads) void k_latent_fwd(lsr_latent_dims d
             a4.x += wy * s4.x; a4.y += wy * s4.y; a4.z += wy * s4.z; a4.w += wy * s4.w;
         }
         if (!want_z) return;
-        // column sums: add the row lanes through LDS (rl = 0 stores, the others add in turn)
-        for (int r = 0; r < nrl; ++r) {
-            if (rl == r) {
-                float4 *c4 = (float4 *)col + cg;
-                if (r == 0) *c4 = a4;
-                else { float4 t = *c4; t.x += a4.x; t.y += a4.y; t.z += a4.z; t.w += a4.w; *c4 = t; }
+        // column sums: add the row lanes pairwise through LDS (nrl is a power of two; lane rl sits at float4 index
+        // rl * tpr + cg == threadIdx.x).  log2(nrl) steps, and the rounding error grows with the depth of the tree,
+        // not with the number of lanes (256 at W = 4: tests/test_latent_paths_gpu.py case 7 needs the tree)
+        float4 *l4 = (float4 *)col;
+        l4[threadIdx.x] = a4;
+        __syncthreads();
+        for (int s = nrl >> 1; s > 0; s >>= 1) {
+            if (rl < s) {
+                float4 t = l4[threadIdx.x];
+                const float4 u = l4[threadIdx.x + s * tpr];
+                t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w;
+                l4[threadIdx.x] = t;
             }
             __syncthreads();
         }
@@ -288,7 +295,7 @@ int lsr_latent_forward(const lsr_latent_dims *d, const lsr_latent_inputs *in,
     const dim3 grid(latent_bands(dd, out->z != nullptr), planes, d->num_views);
     hipStream_t s = (hipStream_t)stream;
     prof_begin(kStLatentFwd, s);
-    hipLaunchKernelGGL(k_latent_fwd, grid, dim3(kLatentThreads), sizeof(float) * d->width, s, dd, *in, *out);
+    hipLaunchKernelGGL(k_latent_fwd, grid, dim3(kLatentThreads), sizeof(float) * kLatentThreads * kLatentMaxCols, s, dd, *in, *out);
     prof_end(kStLatentFwd, s);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }

@@ -22,17 +22,19 @@ import torch
 import torch.nn.functional as F
 
 
-def rescale(x: torch.Tensor, factor: int) -> torch.Tensor:
+def rescale(x: torch.Tensor, factor: int | None, size: tuple[int, int] | None = None) -> torch.Tensor:
+    """Downscale by the integer `factor`, or to the explicit `size` = (out_h, out_w) (fractional and
+    per-axis scales; `factor` is then ignored)."""
     batch, (h, w) = x.shape[:-2], x.shape[-2:]
-    size = (h // factor, w // factor)
+    size = (h // factor, w // factor) if size is None else tuple(size)
     return F.interpolate(x.reshape(1, -1, h, w), size=size, mode="bilinear", align_corners=False,
                          antialias=True).reshape(*batch, *size)
 
 
 def latent_epilogue(features, mask, noise, color, factor: int, variational: bool = False,
-                    interval=(-30.0, 20.0)):
+                    interval=(-30.0, 20.0), size=None):
     """features (..., C|2C, H, W), mask (..., H, W), noise (..., C, H, W)|None, color (..., 3, H, W)|None
-    -> dict(sample, z, skip, logvar)."""
+    -> dict(sample, z, skip, logvar).  `size` as in `rescale`."""
     if variational:
         mean, logvar = features.chunk(2, dim=-3)
     else:
@@ -41,7 +43,7 @@ def latent_epilogue(features, mask, noise, color, factor: int, variational: bool
     logvar = torch.clamp(logvar, *interval)
     sample = mean if noise is None else mean + torch.exp(0.5 * logvar) * noise
     skip = None if color is None else torch.cat((color.detach(), sample), dim=-3)
-    return dict(sample=sample, z=rescale(sample, factor), skip=skip, logvar=logvar)
+    return dict(sample=sample, z=rescale(sample, factor, size), skip=skip, logvar=logvar)
 
 
 def aa_weight_matrix(in_size: int, out_size: int) -> torch.Tensor:
