@@ -174,6 +174,27 @@ int lsr_ply_sh_axes_matrix(double *out);
  * file cannot be created or fully written. */
 int lsr_ply_write_scene_host(const char *path, const float *rows_host, int64_t n, int32_t sh_coeffs);
 
+/*
+ * ---- point clouds: the sparse SfM cloud a 3DGS fit starts from ----
+ *
+ * The file the published trainer's storePly writes (x y z nx ny nz red green blue) and COLMAP conversions produce: one
+ * binary little-endian `vertex` element of scalar properties, of any PLY scalar type under either spelling (char / int8,
+ * uchar / uint8, short / int16, ushort / uint16, int / int32, uint / uint32, float / float32, double / float64) and in
+ * any order.  x y z are required, as float or double (doubles are rounded to float); red green blue are optional, must
+ * be uchar and come out divided by 255; everything else (nx ny nz, alpha, ...) is skipped by its size.
+ * LSR_EUNSUPPORTED: a format other than `binary_little_endian 1.0`, a list property, an element other than one `vertex`,
+ *   x y z or colours of another type, only some of the three colours, more than 1024 properties.
+ * LSR_EINVAL: the file cannot be opened, is not a PLY, has a malformed or over-long (> 255 bytes) header line, an unknown
+ *   scalar type or no `end_header`, a negative or overflowing vertex count, x, y or z missing, one of the six names given
+ *   twice, or fewer bytes than the header promises.
+ * Host only; the outputs are written only when every check has passed.
+ */
+int lsr_ply_read_points_header(const char *path, int64_t *n, int32_t *has_colors);
+
+/* xyz_host[n][3] and, where the file has colours and rgb_host is not NULL, rgb_host[n][3] in [0, 1] (HOST memory).  The
+ * header is parsed and checked again; capacity_points < n is LSR_EINVAL, xyz_host NULL with n > 0 LSR_ENULL. */
+int lsr_ply_read_points(const char *path, float *xyz_host, float *rgb_host, int64_t capacity_points);
+
 #ifdef __cplusplus
 }
 #endif

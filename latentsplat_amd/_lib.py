@@ -1,5 +1,5 @@
 """ctypes binding of ``liblsr_hip.so`` (C ABI: include/lsr_rasterizer.h, include/lsr_adapter.h, include/lsr_latent.h, include/lsr_ply.h,
-include/lsr_sh_rotate.h, include/lsr_depth_head.h, include/lsr_scene.h, include/lsr_loss.h, include/lsr_density.h, include/lsr_optim.h).
+include/lsr_sh_rotate.h, include/lsr_depth_head.h, include/lsr_scene.h, include/lsr_loss.h, include/lsr_density.h, include/lsr_optim.h, include/lsr_knn.h).
 
 The library is built in-tree by ``latentsplat_amd/csrc/Makefile`` (``__graft_entry__.build()``).
 There is no CPU fallback: if the shared object is missing or not loadable this module raises, and
@@ -215,6 +215,7 @@ class AdamTable(C.Structure):       # lsr_adam_table (include/lsr_optim.h)
 
 
 ADAM_MAX_TABLES, ADAM_MAX_WIDTH, ADAM_MAX_ROWS = 24, 4096, 1 << 40   # LSR_ADAM_MAX_*
+KNN_MAX_POINTS = 1 << 28                                            # LSR_KNN_MAX_POINTS (include/lsr_knn.h)
 
 
 def sh_rotate_table_floats(degree: int) -> int:
@@ -238,6 +239,7 @@ EXPORTS = (
     "lsr_photometric_workspace_bytes", "lsr_photometric_forward", "lsr_photometric_backward",
     "lsr_density_accumulate", "lsr_densify_workspace_bytes", "lsr_densify_plan", "lsr_densify_apply",
     "lsr_adam_step",
+    "lsr_knn3_workspace_bytes", "lsr_knn3", "lsr_ply_read_points_header", "lsr_ply_read_points",
 )
 
 _lib = None
@@ -387,6 +389,14 @@ def load():
     lib.lsr_densify_apply.argtypes = [I64, I64, P, P, I32, C.POINTER(DensifyTable), I32, P, P, P, I64, P]
     lib.lsr_adam_step.restype = C.c_int
     lib.lsr_adam_step.argtypes = [C.POINTER(AdamTable), I32, P, I64, P]
+    lib.lsr_knn3_workspace_bytes.restype = SZ
+    lib.lsr_knn3_workspace_bytes.argtypes = [I64]
+    lib.lsr_knn3.restype = C.c_int
+    lib.lsr_knn3.argtypes = [I64, P, P, P, P, P, P]
+    lib.lsr_ply_read_points_header.restype = C.c_int
+    lib.lsr_ply_read_points_header.argtypes = [C.c_char_p, C.POINTER(I64), C.POINTER(I32)]
+    lib.lsr_ply_read_points.restype = C.c_int
+    lib.lsr_ply_read_points.argtypes = [C.c_char_p, P, P, I64]
     _lib = lib
     return lib
 

@@ -175,6 +175,101 @@ int parse(FILE *f, Parsed *p) {
     return LSR_OK;
 }
 
+// ---- point clouds: the files the published trainer's storePly writes and COLMAP conversions produce ----
+
+constexpr int kMaxPointProps = 1024;      // scalar properties per vertex
+constexpr int kRowBatchBytes = 1 << 16;   // rows are read through a buffer of this size (>= one row: 1024 x 8 bytes)
+
+// Size in bytes of a PLY scalar type under either of its spellings, 0 for anything else.  *is_float: float / double.
+int scalar_size(const char *t, bool *is_float) {
+    static const struct { const char *a, *b; int size; bool flt; } types[] = {
+        {"char", "int8", 1, false}, {"uchar", "uint8", 1, false}, {"short", "int16", 2, false}, {"ushort", "uint16", 2, false},
+        {"int", "int32", 4, false}, {"uint", "uint32", 4, false}, {"float", "float32", 4, true}, {"double", "float64", 8, true}};
+    for (const auto &e : types)
+        if (!strcmp(t, e.a) || !strcmp(t, e.b)) { *is_float = e.flt; return e.size; }
+    return 0;
+}
+
+struct PointsParsed {
+    int64_t n, data_offset, stride;       // stride in bytes
+    int32_t xyz[3], xyz_size[3];          // byte offsets inside a row; 4 (float) or 8 (double)
+    int32_t rgb[3];                       // byte offsets of the uchar colours; has_colors says whether they are there
+    bool has_colors;
+};
+
+int parse_points(FILE *f, PointsParsed *out) {
+    PointsParsed P;
+    memset(&P, 0, sizeof(P));
+    static const char *const xyz_names[] = {"x", "y", "z"}, *const rgb_names[] = {"red", "green", "blue"};
+    bool seen_xyz[3] = {}, seen_rgb[3] = {};
+    bool have_format = false, have_element = false, ended = false;
+    int props = 0;
+    char line[kMaxLine + 1];
+    char *tok[kMaxTokens];
+    long consumed = 0;
+
+    if (read_line(f, line, &consumed) != 1 || strcmp(line, "ply") != 0) return LSR_EINVAL;
+    while (!ended) {
+        if (consumed > kMaxHeaderBytes) return LSR_EINVAL;
+        if (read_line(f, line, &consumed) != 1) return LSR_EINVAL;
+        if (!strncmp(line, "comment", 7) && (line[7] == 0 || line[7] == ' ' || line[7] == '\t')) continue;
+        if (!strncmp(line, "obj_info", 8) && (line[8] == 0 || line[8] == ' ' || line[8] == '\t')) continue;
+        const int nt = tokenize(line, tok);
+        if (nt == 0 || nt > kMaxTokens) return LSR_EINVAL;
+        if (!strcmp(tok[0], "end_header")) {
+            if (nt != 1) return LSR_EINVAL;
+            ended = true;
+        } else if (!strcmp(tok[0], "format")) {
+            if (nt != 3 || have_format || have_element) return LSR_EINVAL;
+            if (strcmp(tok[1], "binary_little_endian") != 0 || strcmp(tok[2], "1.0") != 0) return LSR_EUNSUPPORTED;
+            have_format = true;
+        } else if (!strcmp(tok[0], "element")) {
+            if (nt != 3 || !have_format) return LSR_EINVAL;
+            if (have_element || strcmp(tok[1], "vertex") != 0) return LSR_EUNSUPPORTED;
+            if (parse_i64(tok[2], &P.n) != 0 || P.n < 0) return LSR_EINVAL;
+            have_element = true;
+        } else if (!strcmp(tok[0], "property")) {
+            if (!have_element || nt < 3) return LSR_EINVAL;
+            if (!strcmp(tok[1], "list")) return LSR_EUNSUPPORTED;
+            if (nt != 3) return LSR_EINVAL;
+            bool is_float = false;
+            const int size = scalar_size(tok[1], &is_float);
+            if (!size) return LSR_EINVAL;                                   // not a PLY scalar type
+            if (props == kMaxPointProps) return LSR_EUNSUPPORTED;
+            ++props;
+            const int32_t at = (int32_t)P.stride;                           // <= 1024 x 8
+            P.stride += size;
+            for (int k = 0; k < 3; ++k) {
+                if (!strcmp(tok[2], xyz_names[k])) {
+                    if (seen_xyz[k]) return LSR_EINVAL;                     // given twice
+                    if (!is_float) return LSR_EUNSUPPORTED;
+                    seen_xyz[k] = true; P.xyz[k] = at; P.xyz_size[k] = size;
+                }
+                if (!strcmp(tok[2], rgb_names[k])) {
+                    if (seen_rgb[k]) return LSR_EINVAL;
+                    if (size != 1 || (strcmp(tok[1], "uchar") != 0 && strcmp(tok[1], "uint8") != 0)) return LSR_EUNSUPPORTED;
+                    seen_rgb[k] = true; P.rgb[k] = at;
+                }
+            }
+        } else {
+            return LSR_EINVAL;
+        }
+    }
+    if (!have_format || !have_element) return LSR_EINVAL;
+    if (!seen_xyz[0] || !seen_xyz[1] || !seen_xyz[2]) return LSR_EINVAL;
+    const int colours = (int)seen_rgb[0] + (int)seen_rgb[1] + (int)seen_rgb[2];
+    if (colours != 0 && colours != 3) return LSR_EUNSUPPORTED;              // only some of the three
+    P.has_colors = colours == 3;
+    P.data_offset = consumed;
+    // size: header + n * stride bytes must be there (stride >= 12 here); n * 3 floats must be a size the caller can hold
+    if (P.n > INT64_MAX / 16 / P.stride) return LSR_EINVAL;
+    if (fseeko(f, 0, SEEK_END) != 0) return LSR_EINVAL;
+    const int64_t size = (int64_t)ftello(f);
+    if (size < P.data_offset || size - P.data_offset < P.n * P.stride) return LSR_EINVAL;
+    *out = P;
+    return LSR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -204,6 +299,53 @@ int lsr_ply_read_rows(const char *path, float *rows_host, int64_t capacity_float
         if (fseeko(f, (off_t)p.layout.data_offset, SEEK_SET) != 0 ||
             fread(rows_host, sizeof(float), (size_t)p.row_floats, f) != (size_t)p.row_floats)
             rc = LSR_EINVAL;
+    }
+    fclose(f);
+    return rc;
+}
+
+int lsr_ply_read_points_header(const char *path, int64_t *n, int32_t *has_colors) {
+    if (!path || !n || !has_colors) return LSR_ENULL;
+    FILE *f = fopen(path, "rb");
+    if (!f) return LSR_EINVAL;
+    PointsParsed p;
+    const int rc = parse_points(f, &p);
+    fclose(f);
+    if (rc == LSR_OK) { *n = p.n; *has_colors = p.has_colors ? 1 : 0; }
+    return rc;
+}
+
+int lsr_ply_read_points(const char *path, float *xyz_host, float *rgb_host, int64_t capacity_points) {
+    if (!path) return LSR_ENULL;
+    FILE *f = fopen(path, "rb");
+    if (!f) return LSR_EINVAL;
+    PointsParsed p;
+    int rc = parse_points(f, &p);
+    if (rc == LSR_OK && capacity_points < p.n) rc = LSR_EINVAL;
+    if (rc == LSR_OK && p.n > 0 && !xyz_host) rc = LSR_ENULL;
+    if (rc == LSR_OK && p.n > 0) {
+        // (a file that shrinks between the size check and here gives a short read: reported, and the buffers then hold
+        // a prefix of the points)
+        static_assert(kMaxPointProps * 8 <= kRowBatchBytes, "one row fits the batch buffer");
+        unsigned char buf[kRowBatchBytes];
+        const int64_t per_batch = kRowBatchBytes / p.stride;
+        const bool colours = p.has_colors && rgb_host;
+        if (fseeko(f, (off_t)p.data_offset, SEEK_SET) != 0) rc = LSR_EINVAL;
+        for (int64_t done = 0; rc == LSR_OK && done < p.n; ) {
+            const int64_t rows = p.n - done < per_batch ? p.n - done : per_batch;
+            if (fread(buf, (size_t)p.stride, (size_t)rows, f) != (size_t)rows) { rc = LSR_EINVAL; break; }
+            for (int64_t r = 0; r < rows; ++r) {
+                const unsigned char *row = buf + r * p.stride;
+                for (int k = 0; k < 3; ++k) {
+                    float v;
+                    if (p.xyz_size[k] == 4) memcpy(&v, row + p.xyz[k], 4);
+                    else { double d; memcpy(&d, row + p.xyz[k], 8); v = (float)d; }
+                    xyz_host[3 * (done + r) + k] = v;
+                    if (colours) rgb_host[3 * (done + r) + k] = (float)row[p.rgb[k]] / 255.0f;
+                }
+            }
+            done += rows;
+        }
     }
     fclose(f);
     return rc;

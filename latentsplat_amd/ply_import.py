@@ -124,3 +124,21 @@ def load_ply(path, device, *, opacity: str = "logit") -> Scene3DGS:
     _lib.check(lib.lsr_ply_read_rows(os.fsencode(str(path)), C.c_void_p(host.data_ptr()), host.numel()),
                "lsr_ply_read_rows")
     return _scene(unpack_table(host.to(device, non_blocking=True), layout, opacity), layout.sh_coeffs)
+
+
+def load_points_ply(path, device):
+    """A point cloud file (the published trainer's ``points3D.ply``: binary little-endian ``x y z`` as float or double,
+    optional uchar ``red green blue``, anything else skipped) as ``(points (n, 3), colors (n, 3) in [0, 1] or None)``,
+    float32 on ``device``.  The library's host reader (``lsr_ply_read_points``); what
+    :meth:`latentsplat_amd.scene_model.GaussianScene.from_point_cloud` starts from."""
+    device = torch.device(device)
+    lib = _lib.load()
+    n, has_colors = C.c_int64(0), C.c_int32(0)
+    name = os.fsencode(str(path))
+    _lib.check(lib.lsr_ply_read_points_header(name, C.byref(n), C.byref(has_colors)), "lsr_ply_read_points_header")
+    pin = device.type == "cuda"
+    xyz = torch.empty((n.value, 3), dtype=torch.float32, pin_memory=pin)
+    rgb = torch.empty((n.value, 3), dtype=torch.float32, pin_memory=pin) if has_colors.value else None
+    ptr = lambda t: C.c_void_p(None if t is None or t.numel() == 0 else t.data_ptr())
+    _lib.check(lib.lsr_ply_read_points(name, ptr(xyz), ptr(rgb), n.value), "lsr_ply_read_points")
+    return xyz.to(device), None if rgb is None else rgb.to(device)

@@ -13,6 +13,7 @@ setting."""
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from math import isqrt
 from pathlib import Path
@@ -228,6 +229,44 @@ class GaussianScene(nn.Module):
                                     "export of export_ply). Such a file holds no trainable scene; read it with "
                                     "load_ply(path, device, opacity=\"raw\")")
         return cls(**rows_to_parameters(host.to(device), layout))
+
+    @classmethod
+    def from_point_cloud(cls, points: Tensor, colors: Optional[Tensor] = None, sh_degree: int = 3, *,
+                         initial_opacity: float = 0.1, min_dist2: float = 1e-7) -> "GaussianScene":
+        """The published trainer's ``create_from_pcd``: a scene that starts from a sparse point cloud.  ``_xyz`` are the
+        points ``(n, 3)`` (a float32 ROCm tensor, n >= 4), ``_features_dc`` is ``(colors - 0.5) / 0.28209479177387814``
+        with ``colors (n, 3)`` in [0, 1] (``None``: grey, zeros), ``_features_rest`` zeros up to ``sh_degree`` (0..4),
+        ``_opacity`` the logit of ``initial_opacity``, ``_rotation`` the identity, and every ``_scaling`` row
+        ``log(sqrt(max(d, min_dist2)))`` three times over, ``d`` the mean squared distance of the point to its three
+        nearest neighbours (:func:`latentsplat_amd.knn.mean_knn_dist2`: the search is the HIP kernel, the elementwise
+        tail plain torch).  ``active_sh_degree`` starts at 0.  Non-finite coordinates are refused (one host read)."""
+        from .knn import mean_knn_dist2
+        if not torch.is_tensor(points) or not points.is_cuda or points.dtype != torch.float32:
+            raise _lib.LsrError("from_point_cloud needs a float32 ROCm tensor of points (no CPU fallback)")
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise _lib.LsrError(f"points must be (n, 3), got {tuple(points.shape)}")
+        if not 0 <= int(sh_degree) <= 4:
+            raise _lib.LsrError("sh_degree must be in 0..4")
+        if not 0.0 < initial_opacity < 1.0 or not min_dist2 > 0.0:
+            raise _lib.LsrError("initial_opacity must lie in (0, 1) and min_dist2 must be positive")
+        n, dev = points.shape[0], points.device
+        points = points.detach().contiguous()
+        if colors is not None and (not torch.is_tensor(colors) or colors.dtype != torch.float32 or colors.device != dev
+                                   or tuple(colors.shape) != (n, 3)):
+            raise _lib.LsrError(f"colors must be a float32 tensor of shape {(n, 3)} on {dev}")
+        if not bool(torch.isfinite(points).all()):
+            raise _lib.LsrError("from_point_cloud: the points hold a non-finite coordinate")
+        dist2 = mean_knn_dist2(points)
+        scaling = torch.log(torch.sqrt(torch.clamp_min(dist2, min_dist2)))[:, None].repeat(1, 3)
+        K = (int(sh_degree) + 1) ** 2
+        dc = torch.zeros((n, 1, 3), dtype=torch.float32, device=dev)
+        if colors is not None:
+            dc[:, 0, :] = (colors.detach() - 0.5) / 0.28209479177387814
+        rotation = torch.zeros((n, 4), dtype=torch.float32, device=dev)
+        rotation[:, 0] = 1.0
+        opacity = torch.full((n, 1), math.log(initial_opacity / (1.0 - initial_opacity)), dtype=torch.float32, device=dev)
+        return cls(points, dc, torch.zeros((n, K - 1, 3), dtype=torch.float32, device=dev), opacity, scaling, rotation,
+                   active_sh_degree=0)
 
     @property
     def num_gaussians(self) -> int:

@@ -35,10 +35,18 @@ like the learning rates, a default and not a measurement.  `--drop F` removes a 
 the targets are rendered, so that there is something to grow back.  With densification on, `fit.json` also holds
 `gaussians_first`, `gaussians_last` and `densify_events` (the counts of every event).
 
+`--from-points` starts the fit from the file's point cloud alone: after the targets are rendered the
+scene is replaced by `GaussianScene.from_point_cloud(xyz, clamp(0.5 + 0.2820948 f_dc, 0, 1), sh_degree)` — the published
+`create_from_pcd`: scales from the 3-nearest-neighbour distances (`lsr_knn3`), identity rotations, opacity 0.1, active SH
+degree 0 — and `--noise` / `--drop` are ignored.  `--sh-degree-interval I` with I > 0 calls `oneup_sh_degree()` every I
+steps (default 0: never), without which a scene that starts at active degree 0 never trains its higher bands.  `fit.json`
+holds `from_points` and `active_sh_degree_last`.
+
 usage: python tools/fit_ply.py scene.ply --out DIR [--views 8] [--size 256] [--steps 200] [--noise 1.0] [--seed 0] [--distance 2.5]
                                [--lambda-dssim 0.0] [--drop 0.0] [--densify-interval 0] [--densify-from 0] [--densify-until STEPS]
                                [--densify-grad-threshold 2e-4/VIEWS] [--min-opacity 0.005] [--opacity-reset-interval 0]
-                               [--optimizer torch|fused|sparse] [--lr-position-final F] [--lr-position-max-steps S]"""
+                               [--optimizer torch|fused|sparse] [--lr-position-final F] [--lr-position-max-steps S]
+                               [--from-points] [--sh-degree-interval 0]"""
 from __future__ import annotations
 
 import argparse
@@ -96,12 +104,15 @@ def main(argv=None) -> dict:
                     help="on the mean view-space gradient (default 2e-4 / --views: a default, not a measurement)")
     ap.add_argument("--min-opacity", type=float, default=0.005, help="Gaussians below it are pruned at a densification")
     ap.add_argument("--opacity-reset-interval", type=int, default=0, help="reset the opacities every this many steps (0: never)")
+    ap.add_argument("--from-points", action="store_true",
+                    help="start from the file's points and DC colours alone (GaussianScene.from_point_cloud); --noise and --drop are ignored")
+    ap.add_argument("--sh-degree-interval", type=int, default=0, help="render one more SH band every this many steps (0: never, the default)")
     a = ap.parse_args(argv)
     if a.steps < 1 or a.views < 1:
         sys.exit("fit_ply needs at least one step and one view")
     if not 0.0 <= a.lambda_dssim <= 1.0:
         sys.exit("--lambda-dssim must be in [0, 1]")
-    if not 0.0 <= a.drop < 1.0 or a.densify_interval < 0 or a.opacity_reset_interval < 0:
+    if not 0.0 <= a.drop < 1.0 or a.densify_interval < 0 or a.opacity_reset_interval < 0 or a.sh_degree_interval < 0:
         sys.exit("--drop must be in [0, 1); the intervals must not be negative")
     if a.lr_position_final is not None and (a.lr_position_final < 0.0 or (a.lr_position_max_steps or a.steps) < 1):
         sys.exit("--lr-position-final must not be negative and --lr-position-max-steps must be positive")
@@ -120,10 +131,13 @@ def main(argv=None) -> dict:
         target = scene.render(views, a.size, a.size)[0]
         gen = torch.Generator().manual_seed(a.seed)
         noise = dict(UNIT_NOISE, _xyz=POSITION_NOISE * float(extent))
+        if a.from_points:
+            colors = (0.5 + 0.2820948 * scene._features_dc.detach()[:, 0, :]).clamp(0.0, 1.0)
+            scene = GaussianScene.from_point_cloud(scene._xyz.detach(), colors, sh_degree=scene.max_sh_degree)
         for name, p in scene.named_parameters():
-            if name in noise and a.noise:
+            if name in noise and a.noise and not a.from_points:
                 p.add_((torch.randn(p.shape, generator=gen) * (a.noise * noise[name])).to(dev))
-        if a.drop > 0.0:
+        if a.drop > 0.0 and not a.from_points:
             keep = (torch.rand(scene.num_gaussians, generator=gen) >= a.drop).to(dev)
             scene.replace_parameters_(**{name[1:]: p.detach()[keep] for name, p in scene.named_parameters()})
     rates = dict(_xyz=a.lr_position * float(extent), _features_dc=a.lr_dc,
@@ -178,13 +192,16 @@ def main(argv=None) -> dict:
                 events.append(dict(step=done, **counts))
         if control is not None and a.opacity_reset_interval and (step + 1) % a.opacity_reset_interval == 0:
             control.reset_opacity(opt)
+        if a.sh_degree_interval and (step + 1) % a.sh_degree_interval == 0:
+            scene.oneup_sh_degree()
     torch.cuda.synchronize(dev)
     per_step = (time.perf_counter() - t0) / (a.steps - warm)
     os.makedirs(a.out, exist_ok=True)
     scene.save_ply(os.path.join(a.out, "point_cloud.ply"))
     res = dict(loss_first=float(losses[0]), loss_last=float(losses[-1]), steps=a.steps, ms_per_step=1e3 * per_step,
                timed_steps=a.steps - warm, gaussians=scene.num_gaussians, sh_degree=scene.max_sh_degree, views=a.views,
-               size=a.size, noise=a.noise, seed=a.seed, extent=float(extent), lambda_dssim=a.lambda_dssim, optimizer=a.optimizer)
+               size=a.size, noise=a.noise, seed=a.seed, extent=float(extent), lambda_dssim=a.lambda_dssim, optimizer=a.optimizer,
+               from_points=bool(a.from_points), active_sh_degree_last=scene.active_sh_degree)
     if densify:
         res.update(gaussians_first=gaussians_first, gaussians_last=scene.num_gaussians, densify_events=events)
     with open(os.path.join(a.out, "fit.json"), "w") as f:
