@@ -30,6 +30,16 @@
  * negative LSR_E* code; nothing here throws.  The library never allocates device memory (its one
  * allocation is a 64-byte pinned host buffer per calling thread, through which lsr_forward_prepare
  * receives the pair count without a copy command).
+ *
+ * Non-finite and degenerate inputs (tests/test_poison_*.py).  A Gaussian whose mean or covariance
+ * holds a NaN or an Inf, or whose projected covariance has an overflowing determinant or no positive eigenvalue, is culled
+ * in every view: radius 0, no pixel, and every gradient row of it is exactly 0 whatever its opacity / colour / features
+ * hold; no other row and no view's camera gradient is affected.  Finite degenerate geometry (zero or rank-deficient
+ * covariances, huge ones, a mean at a camera centre or on the near-cull plane) follows the published arithmetic.  An
+ * opacity outside (0, 1) is blended as alpha = min(0.99, opacity * G), below 1/255 not at all.  A non-finite opacity,
+ * colour or feature on a VISIBLE Gaussian is contained to the tiles of its rectangle (pixels and gradient rows that share
+ * no tile with it are unaffected); inside them nothing is promised.  Float -> int conversions saturate (NaN -> 0) and every
+ * tile bound is clamped to the grid before use, so no input forms an index outside the workspaces.
  */
 #ifndef LSR_RASTERIZER_H
 #define LSR_RASTERIZER_H

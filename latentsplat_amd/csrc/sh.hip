@@ -609,7 +609,10 @@ k_sh_bwd(ShParams pk) {
         }
         __syncthreads();
         // ---- pass 2: thread = element of the contiguous coefficient-gradient runs ----
-        const bool rmw = shared && v0 > 0;
+        // a coefficient tensor shared by the views is summed over them: later chunks add to what earlier ones stored.  Per
+        // tensor, not per call: colour harmonics shared by the views next to per-view latent harmonics (or the reverse) run
+        // one view per chunk (`shared` is false) and must still accumulate the shared one
+        const bool rmw_c = d.vs_color == 0 && v0 > 0, rmw_f = d.vs_feat == 0 && v0 > 0;
         if (DEGC >= 0) {
             const int ks = p.ks[0];
             float *dst = p.g.color + (d.vs_color != 0 ? (size_t)v0 * d.vs_color : 0) + (size_t)g0 * ks;
@@ -661,7 +664,7 @@ k_sh_bwd(ShParams pk) {
                     dst[t] = a;
                 }
             };
-            if (rmw) colour_pass(std::true_type{}); else colour_pass(std::false_type{});
+            if (rmw_c) colour_pass(std::true_type{}); else colour_pass(std::false_type{});
         }
         if (hasF) {
             if (DEGC >= 0) __syncthreads();   // the colour element pass is done with the basis area
@@ -710,7 +713,7 @@ k_sh_bwd(ShParams pk) {
                     dst[t] = a;
                 }
             };
-            if (rmw) feature_pass(std::true_type{}); else feature_pass(std::false_type{});
+            if (rmw_f) feature_pass(std::true_type{}); else feature_pass(std::false_type{});
         }
     }
     if (d.vs_means == 0) {
