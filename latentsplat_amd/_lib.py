@@ -1,5 +1,5 @@
 """ctypes binding of ``liblsr_hip.so`` (C ABI: include/lsr_rasterizer.h, include/lsr_adapter.h, include/lsr_latent.h, include/lsr_ply.h,
-include/lsr_sh_rotate.h, include/lsr_depth_head.h, include/lsr_scene.h, include/lsr_loss.h, include/lsr_density.h, include/lsr_optim.h, include/lsr_knn.h).
+include/lsr_sh_rotate.h, include/lsr_depth_head.h, include/lsr_scene.h, include/lsr_loss.h, include/lsr_density.h, include/lsr_optim.h, include/lsr_knn.h, include/lsr_mcmc.h).
 
 The library is built in-tree by ``latentsplat_amd/csrc/Makefile`` (``__graft_entry__.build()``).
 There is no CPU fallback: if the shared object is missing or not loadable this module raises, and
@@ -218,6 +218,14 @@ ADAM_MAX_TABLES, ADAM_MAX_WIDTH, ADAM_MAX_ROWS = 24, 4096, 1 << 40   # LSR_ADAM_
 KNN_MAX_POINTS = 1 << 28                                            # LSR_KNN_MAX_POINTS (include/lsr_knn.h)
 
 
+class McmcTable(C.Structure):       # lsr_mcmc_table (include/lsr_mcmc.h)
+    _fields_ = [("table", C.c_void_p), ("width", C.c_int32), ("role", C.c_int32)]
+
+
+MCMC_COPY, MCMC_OPACITY, MCMC_SCALING, MCMC_MOMENT = 0, 1, 2, 3     # lsr_mcmc_table.role
+MCMC_MAX_ROWS, MCMC_MAX_TABLES, MCMC_MAX_WIDTH, MCMC_MAX_RATIO, MCMC_WEIGHT_BITS = 1 << 28, 24, 4096, 50, 30   # LSR_MCMC_*
+
+
 def sh_rotate_table_floats(degree: int) -> int:
     """LSR_SH_ROTATE_TABLE_FLOATS: sum of (2l+1)^2 over l <= degree."""
     return (degree + 1) * (2 * degree + 1) * (2 * degree + 3) // 3
@@ -240,6 +248,7 @@ EXPORTS = (
     "lsr_density_accumulate", "lsr_densify_workspace_bytes", "lsr_densify_plan", "lsr_densify_apply",
     "lsr_adam_step",
     "lsr_knn3_workspace_bytes", "lsr_knn3", "lsr_ply_read_points_header", "lsr_ply_read_points",
+    "lsr_mcmc_workspace_bytes", "lsr_mcmc_classify", "lsr_mcmc_sample", "lsr_mcmc_apply", "lsr_mcmc_noise",
 )
 
 _lib = None
@@ -397,6 +406,16 @@ def load():
     lib.lsr_ply_read_points_header.argtypes = [C.c_char_p, C.POINTER(I64), C.POINTER(I32)]
     lib.lsr_ply_read_points.restype = C.c_int
     lib.lsr_ply_read_points.argtypes = [C.c_char_p, P, P, I64]
+    lib.lsr_mcmc_workspace_bytes.restype = SZ
+    lib.lsr_mcmc_workspace_bytes.argtypes = [I64, I64]
+    lib.lsr_mcmc_classify.restype = C.c_int
+    lib.lsr_mcmc_classify.argtypes = [I64, P, C.c_float, P, P, P, P, P]
+    lib.lsr_mcmc_sample.restype = C.c_int
+    lib.lsr_mcmc_sample.argtypes = [I64, P, I64, P, P, P, P, P, P]
+    lib.lsr_mcmc_apply.restype = C.c_int
+    lib.lsr_mcmc_apply.argtypes = [I64, I64, P, P, P, C.POINTER(McmcTable), I32, C.c_float, P, P]
+    lib.lsr_mcmc_noise.restype = C.c_int
+    lib.lsr_mcmc_noise.argtypes = [I64, P, P, P, P, P, C.c_float, P]
     _lib = lib
     return lib
 

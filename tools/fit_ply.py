@@ -42,11 +42,20 @@ degree 0 — and `--noise` / `--drop` are ignored.  `--sh-degree-interval I` wit
 steps (default 0: never), without which a scene that starts at active degree 0 never trains its higher bands.  `fit.json`
 holds `from_points` and `active_sh_degree_last`.
 
+`--strategy mcmc` replaces adaptive density control by the MCMC strategy (`latentsplat_amd.MCMCControl`):
+`--densify-interval / --densify-from / --densify-until` then schedule `MCMCControl.step` (dead Gaussians are relocated onto
+live ones, then the scene grows by 5 % up to `--cap-max`, default the file's own count); the opacity and scale regulariser
+(`--opacity-reg`, `--scale-reg`) joins the loss; and after every optimizer step covariance-shaped noise is added to the
+positions (`--noise-lr` times the current position rate).  No gradient statistics are gathered.  `fit.json` then holds
+`strategy`, `cap_max`, `gaussians_first`, `gaussians_last` and `mcmc_events` (`step, dead, relocated, added, n_in, n_out` of
+every event).  `--strategy adc`, the default, is everything above.
+
 usage: python tools/fit_ply.py scene.ply --out DIR [--views 8] [--size 256] [--steps 200] [--noise 1.0] [--seed 0] [--distance 2.5]
                                [--lambda-dssim 0.0] [--drop 0.0] [--densify-interval 0] [--densify-from 0] [--densify-until STEPS]
                                [--densify-grad-threshold 2e-4/VIEWS] [--min-opacity 0.005] [--opacity-reset-interval 0]
                                [--optimizer torch|fused|sparse] [--lr-position-final F] [--lr-position-max-steps S]
-                               [--from-points] [--sh-degree-interval 0]"""
+                               [--from-points] [--sh-degree-interval 0]
+                               [--strategy adc|mcmc] [--cap-max N] [--noise-lr 5e5] [--opacity-reg 0.01] [--scale-reg 0.01]"""
 from __future__ import annotations
 
 import argparse
@@ -107,6 +116,12 @@ def main(argv=None) -> dict:
     ap.add_argument("--from-points", action="store_true",
                     help="start from the file's points and DC colours alone (GaussianScene.from_point_cloud); --noise and --drop are ignored")
     ap.add_argument("--sh-degree-interval", type=int, default=0, help="render one more SH band every this many steps (0: never, the default)")
+    ap.add_argument("--strategy", choices=("adc", "mcmc"), default="adc",
+                    help="what --densify-interval schedules: adc, adaptive density control (the default), or mcmc, relocation and growth to a cap")
+    ap.add_argument("--cap-max", type=int, default=None, help="mcmc: the largest number of Gaussians (default: the file's count)")
+    ap.add_argument("--noise-lr", type=float, default=5e5, help="mcmc: position noise, times the position rate (the published default)")
+    ap.add_argument("--opacity-reg", type=float, default=0.01, help="mcmc: weight of mean(sigmoid(opacity)) in the loss")
+    ap.add_argument("--scale-reg", type=float, default=0.01, help="mcmc: weight of mean(exp(scaling)) in the loss")
     a = ap.parse_args(argv)
     if a.steps < 1 or a.views < 1:
         sys.exit("fit_ply needs at least one step and one view")
@@ -116,6 +131,8 @@ def main(argv=None) -> dict:
         sys.exit("--drop must be in [0, 1); the intervals must not be negative")
     if a.lr_position_final is not None and (a.lr_position_final < 0.0 or (a.lr_position_max_steps or a.steps) < 1):
         sys.exit("--lr-position-final must not be negative and --lr-position-max-steps must be positive")
+    if a.cap_max is not None and a.cap_max < 1:
+        sys.exit("--cap-max must be positive")
     if not torch.cuda.is_available():
         sys.exit("fit_ply needs an MI355X: no ROCm device is visible (there is no CPU fallback)")
     from latentsplat_amd.rasterizer import build_view_table
@@ -124,6 +141,7 @@ def main(argv=None) -> dict:
     from latentsplat_amd.scene_model import GaussianScene
     dev = torch.device("cuda:0")
     scene = GaussianScene.from_ply(a.ply, dev)
+    gaussians_file = scene.num_gaussians
     with torch.no_grad():
         centre, extent = scene_extent(scene._xyz)
         ext, intr, near, far = circle_cameras(centre, extent, a.views, a.distance)
@@ -151,7 +169,13 @@ def main(argv=None) -> dict:
     sparse = a.optimizer == "sparse"
     xyz_group = next(g for g in opt.param_groups if g["name"] == "_xyz")
     gen_dev = torch.Generator(device=dev).manual_seed(a.seed)      # the children's offsets at a split
-    densify = a.densify_interval > 0
+    mcmc = None
+    if a.strategy == "mcmc":
+        from latentsplat_amd.mcmc import MCMCControl
+        cap_max = gaussians_file if a.cap_max is None else a.cap_max
+        mcmc = MCMCControl(scene, cap_max, a.min_opacity)
+        mcmc_until = a.steps if a.densify_until is None else a.densify_until
+    densify = a.densify_interval > 0 and mcmc is None
     control = None
     if densify:
         from latentsplat_amd.density import DensityControl
@@ -174,6 +198,8 @@ def main(argv=None) -> dict:
             means2D = None
             render, _, _, _, radii = scene.render(views, a.size, a.size)
         loss = photometric_loss(render, target, a.lambda_dssim) if a.lambda_dssim > 0 else (render - target).abs().mean()
+        if mcmc is not None:
+            loss = loss + mcmc.regularizer(a.opacity_reg, a.scale_reg)
         loss.backward()
         if a.lr_position_final is not None:
             xyz_group["lr"] = expon_lr(step, a.lr_position * float(extent), a.lr_position_final * float(extent),
@@ -190,6 +216,11 @@ def main(argv=None) -> dict:
                 size = 20.0 if a.opacity_reset_interval and done > a.opacity_reset_interval else 0.0
                 counts = control.densify_and_prune(opt, threshold, a.min_opacity, float(extent), size, generator=gen_dev)
                 events.append(dict(step=done, **counts))
+        if mcmc is not None:
+            done = step + 1
+            if a.densify_interval > 0 and a.densify_from < done <= mcmc_until and done % a.densify_interval == 0:
+                events.append(dict(step=done, **mcmc.step(opt, gen_dev)))
+            mcmc.inject_noise(xyz_group["lr"], a.noise_lr, gen_dev)
         if control is not None and a.opacity_reset_interval and (step + 1) % a.opacity_reset_interval == 0:
             control.reset_opacity(opt)
         if a.sh_degree_interval and (step + 1) % a.sh_degree_interval == 0:
@@ -204,6 +235,9 @@ def main(argv=None) -> dict:
                from_points=bool(a.from_points), active_sh_degree_last=scene.active_sh_degree)
     if densify:
         res.update(gaussians_first=gaussians_first, gaussians_last=scene.num_gaussians, densify_events=events)
+    if mcmc is not None:
+        res.update(strategy="mcmc", cap_max=cap_max, gaussians_first=gaussians_first, gaussians_last=scene.num_gaussians,
+                   mcmc_events=events)
     with open(os.path.join(a.out, "fit.json"), "w") as f:
         json.dump(res, f, indent=1)
     print(json.dumps(res))
