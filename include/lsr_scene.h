@@ -78,6 +78,28 @@ int lsr_scene_activate_forward(const lsr_scene_dims *dims, const lsr_scene_param
 int lsr_scene_activate_backward(const lsr_scene_dims *dims, const lsr_scene_params *params,
                                 const lsr_scene_out_grads *dout, const lsr_scene_in_grads *din, lsr_stream_t stream);
 
+/* The same map with the 3D smoothing filter of Mip-Splatting inside it: filter3d [n] is what lsr_filter3d_compute
+ * (lsr_filter3d.h) writes, one float per Gaussian, a constant of the map.  With s_k = exp(scaling_k), f = filter3d[g] and
+ * v_k = s_k^2 + f^2 (the Gaussian convolved with an isotropic Gaussian of variance f^2):
+ *   scales_k  = m sqrt(v_k)
+ *   cov3D     = R diag(m^2 v_k) R^T
+ *   opacities = sigmoid(opacity) c,  c = prod_k (s_k / sqrt(v_k))   — the determinant ratio, formed as three ratios each
+ *               at most 1 and never as sqrt(det / det)
+ *   shs and rotations as in the unfiltered map.  f == 0 gives the unfiltered values.
+ * The same kernel as lsr_scene_activate_forward, instantiated with the filter: one launch, 4 bytes more per Gaussian.  A
+ * non-finite or negative entry of filter3d is taken as it is (NaN in, NaN out for that Gaussian).  Same checks and codes as
+ * the unfiltered forward, plus LSR_ENULL for a NULL filter3d with n > 0. */
+int lsr_scene_activate_filtered_forward(const lsr_scene_dims *dims, const lsr_scene_params *params, const float *filter3d,
+                                        const lsr_scene_outputs *out, lsr_stream_t stream);
+
+/* Its backward; the filter receives no gradient.  With o = sigmoid(opacity), c as above and g_o the upstream gradient of
+ * opacities:  d opacity = g_o c o (1 - o);  M = R diag(m sqrt(v_k)), dM = 2 G M as in the unfiltered backward;
+ *   d scaling_k = m sqrt(v_k) (sum_i dM_ik R_ik) (s_k^2 / v_k)  +  g_o o c f^2 / v_k
+ * (d v_k / d scaling_k = 2 s_k^2; d log c / d scaling_k = f^2 / v_k);  dR_ik = dM_ik m sqrt(v_k), then as before.  A NULL
+ * upstream opacities gradient is zero in both places.  Same checks and codes as the filtered forward. */
+int lsr_scene_activate_filtered_backward(const lsr_scene_dims *dims, const lsr_scene_params *params, const float *filter3d,
+                                         const lsr_scene_out_grads *dout, const lsr_scene_in_grads *din, lsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

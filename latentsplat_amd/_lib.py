@@ -1,5 +1,5 @@
 """ctypes binding of ``liblsr_hip.so`` (C ABI: include/lsr_rasterizer.h, include/lsr_adapter.h, include/lsr_latent.h, include/lsr_ply.h,
-include/lsr_sh_rotate.h, include/lsr_depth_head.h, include/lsr_scene.h, include/lsr_loss.h, include/lsr_density.h, include/lsr_optim.h, include/lsr_knn.h, include/lsr_mcmc.h).
+include/lsr_sh_rotate.h, include/lsr_depth_head.h, include/lsr_scene.h, include/lsr_loss.h, include/lsr_density.h, include/lsr_optim.h, include/lsr_knn.h, include/lsr_mcmc.h, include/lsr_filter3d.h).
 
 The library is built in-tree by ``latentsplat_amd/csrc/Makefile`` (``__graft_entry__.build()``).
 There is no CPU fallback: if the shared object is missing or not loadable this module raises, and
@@ -224,6 +224,8 @@ class McmcTable(C.Structure):       # lsr_mcmc_table (include/lsr_mcmc.h)
 
 MCMC_COPY, MCMC_OPACITY, MCMC_SCALING, MCMC_MOMENT = 0, 1, 2, 3     # lsr_mcmc_table.role
 MCMC_MAX_ROWS, MCMC_MAX_TABLES, MCMC_MAX_WIDTH, MCMC_MAX_RATIO, MCMC_WEIGHT_BITS = 1 << 28, 24, 4096, 50, 30   # LSR_MCMC_*
+FILTER3D_PUBLISHED, FILTER3D_PER_VIEW = 0, 1                        # lsr_filter3d_compute mode (include/lsr_filter3d.h)
+FILTER3D_MAX_ROWS, FILTER3D_MAX_VIEWS = 1 << 28, 65536              # LSR_FILTER3D_MAX_*
 
 
 def sh_rotate_table_floats(degree: int) -> int:
@@ -249,6 +251,8 @@ EXPORTS = (
     "lsr_adam_step",
     "lsr_knn3_workspace_bytes", "lsr_knn3", "lsr_ply_read_points_header", "lsr_ply_read_points",
     "lsr_mcmc_workspace_bytes", "lsr_mcmc_classify", "lsr_mcmc_sample", "lsr_mcmc_apply", "lsr_mcmc_noise",
+    "lsr_filter3d_workspace_bytes", "lsr_filter3d_compute",
+    "lsr_scene_activate_filtered_forward", "lsr_scene_activate_filtered_backward",
 )
 
 _lib = None
@@ -416,6 +420,15 @@ def load():
     lib.lsr_mcmc_apply.argtypes = [I64, I64, P, P, P, C.POINTER(McmcTable), I32, C.c_float, P, P]
     lib.lsr_mcmc_noise.restype = C.c_int
     lib.lsr_mcmc_noise.argtypes = [I64, P, P, P, P, P, C.c_float, P]
+    lib.lsr_filter3d_workspace_bytes.restype = SZ
+    lib.lsr_filter3d_workspace_bytes.argtypes = [I64, I32]
+    lib.lsr_filter3d_compute.restype = C.c_int
+    lib.lsr_filter3d_compute.argtypes = [I64, P, I32, P, I32, C.c_float, C.c_float, I32, P, P, P, P]
+    lib.lsr_scene_activate_filtered_forward.restype = C.c_int
+    lib.lsr_scene_activate_filtered_forward.argtypes = [C.POINTER(SceneDims), C.POINTER(SceneParams), P, C.POINTER(SceneOutputs), P]
+    lib.lsr_scene_activate_filtered_backward.restype = C.c_int
+    lib.lsr_scene_activate_filtered_backward.argtypes = [C.POINTER(SceneDims), C.POINTER(SceneParams), P, C.POINTER(SceneOutGrads),
+                                                         C.POINTER(SceneInGrads), P]
     _lib = lib
     return lib
 

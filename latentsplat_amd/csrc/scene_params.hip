@@ -15,6 +15,12 @@
 //     staging them through LDS as ply.hip does).
 // Indices are 64-bit from the chunk base on (3 K n passes 2^31 near 30 M Gaussians); inside a chunk they are ints
 // (at most 75 * 256).  One owner per output element, no atomics: two calls give the same bits.
+//
+// The filtered pair (lsr_scene_activate_filtered_*) is the same two kernel bodies instantiated with FILTERED = true: with
+// the 3D smoothing filter f of the Gaussian (lsr_filter3d.h), s_k = exp(scaling_k) and v_k = s_k^2 + f^2, the scale that
+// enters M is m sqrt(v_k) and the opacity is multiplied by c = prod_k s_k / sqrt(v_k): three ratios, each at most 1, never
+// sqrt(det / det) (a product of six small scales leaves float32 long before a ratio does).  4 bytes more per Gaussian
+// each way.  Every statement of the unfiltered instantiation is the one it was: the same bits.
 #include <math.h>
 
 #include <algorithm>
@@ -34,8 +40,22 @@ __device__ __forceinline__ void scene_copy(float *__restrict__ dst, const float 
     for (int j = tid; j < count; j += kSceneChunk) dst[j] = src ? src[j] : 0.0f;
 }
 
-template <int K>
-__global__ __launch_bounds__(kSceneChunk) void k_scene_fwd(int64_t n, float m, lsr_scene_params p, lsr_scene_outputs o) {
+// The filtered scales of one Gaussian: r_k = sqrt(s_k^2 + f^2) and the ratios s_k / r_k (each <= 1), s_k = exp(ls[k]).
+__device__ __forceinline__ void scene_filtered_scales(const float *ls, float f, float (&s)[3], float (&v)[3], float (&r)[3],
+                                                      float (&ratio)[3]) {
+    const float f2 = f * f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        s[k] = expf(ls[k]);
+        v[k] = fmaf(s[k], s[k], f2);
+        r[k] = sqrtf(v[k]);
+        ratio[k] = s[k] / r[k];
+    }
+}
+
+template <int K, bool FILTERED>
+__global__ __launch_bounds__(kSceneChunk) void k_scene_fwd(int64_t n, float m, lsr_scene_params p, lsr_scene_outputs o,
+                                                          const float *filter3d) {
     constexpr int E = 3 * K, G = kSceneChunk;
     __shared__ float s_dc[3 * G];
     const int tid = threadIdx.x;
@@ -72,7 +92,15 @@ __global__ __launch_bounds__(kSceneChunk) void k_scene_fwd(int64_t n, float m, l
                 }
             }
         }
-        if (o.opacities && tid < nr) o.opacities[g0 + tid] = 1.0f / (1.0f + expf(-p.opacity[g0 + tid]));
+        if constexpr (FILTERED) {
+            if (o.opacities && tid < nr) {
+                float s[3], v[3], r[3], ratio[3];
+                scene_filtered_scales(p.scaling + 3 * (g0 + tid), filter3d[g0 + tid], s, v, r, ratio);
+                o.opacities[g0 + tid] = (1.0f / (1.0f + expf(-p.opacity[g0 + tid]))) * (ratio[0] * ratio[1] * ratio[2]);
+            }
+        } else {
+            if (o.opacities && tid < nr) o.opacities[g0 + tid] = 1.0f / (1.0f + expf(-p.opacity[g0 + tid]));
+        }
 
         // one Gaussian per lane: quaternion, scales, covariance
         if (geo && tid < nr) {
@@ -83,7 +111,14 @@ __global__ __launch_bounds__(kSceneChunk) void k_scene_fwd(int64_t n, float m, l
             w *= inv; x *= inv; y *= inv; z *= inv;
             if (o.rotations) reinterpret_cast<float4 *>(o.rotations)[gi] = make_float4(w, x, y, z);
             const float *ls = p.scaling + 3 * gi;
-            const float s0 = m * expf(ls[0]), s1 = m * expf(ls[1]), s2 = m * expf(ls[2]);
+            float s0, s1, s2;
+            if constexpr (FILTERED) {
+                float s[3], v[3], r[3], ratio[3];
+                scene_filtered_scales(ls, filter3d[gi], s, v, r, ratio);
+                s0 = m * r[0]; s1 = m * r[1]; s2 = m * r[2];
+            } else {
+                s0 = m * expf(ls[0]); s1 = m * expf(ls[1]); s2 = m * expf(ls[2]);
+            }
             if (o.scales) {
                 float *sc = o.scales + 3 * gi;
                 sc[0] = s0; sc[1] = s1; sc[2] = s2;
@@ -106,9 +141,9 @@ __global__ __launch_bounds__(kSceneChunk) void k_scene_fwd(int64_t n, float m, l
     }
 }
 
-template <int K>
+template <int K, bool FILTERED>
 __global__ __launch_bounds__(kSceneChunk) void k_scene_bwd(int64_t n, float m, lsr_scene_params p, lsr_scene_out_grads g,
-                                                          lsr_scene_in_grads d) {
+                                                          lsr_scene_in_grads d, const float *filter3d) {
     constexpr int E = 3 * K, G = kSceneChunk;
     __shared__ float s_dc[3 * G];
     const int tid = threadIdx.x;
@@ -163,9 +198,18 @@ __global__ __launch_bounds__(kSceneChunk) void k_scene_bwd(int64_t n, float m, l
                 }
             }
         }
-        if (d.opacity && tid < nr) {
-            const float o = 1.0f / (1.0f + expf(-p.opacity[g0 + tid]));
-            d.opacity[g0 + tid] = g.opacities ? g.opacities[g0 + tid] * o * (1.0f - o) : 0.0f;
+        if constexpr (FILTERED) {
+            if (d.opacity && tid < nr) {
+                float s[3], v[3], r[3], ratio[3];
+                scene_filtered_scales(p.scaling + 3 * (g0 + tid), filter3d[g0 + tid], s, v, r, ratio);
+                const float o = 1.0f / (1.0f + expf(-p.opacity[g0 + tid]));
+                d.opacity[g0 + tid] = g.opacities ? g.opacities[g0 + tid] * (ratio[0] * ratio[1] * ratio[2]) * (o * (1.0f - o)) : 0.0f;
+            }
+        } else {
+            if (d.opacity && tid < nr) {
+                const float o = 1.0f / (1.0f + expf(-p.opacity[g0 + tid]));
+                d.opacity[g0 + tid] = g.opacities ? g.opacities[g0 + tid] * o * (1.0f - o) : 0.0f;
+            }
         }
 
         // one Gaussian per lane
@@ -176,7 +220,24 @@ __global__ __launch_bounds__(kSceneChunk) void k_scene_bwd(int64_t n, float m, l
             const float inv = 1.0f / sqrtf(w * w + x * x + y * y + z * z);
             w *= inv; x *= inv; y *= inv; z *= inv;
             const float *ls = p.scaling + 3 * gi;
-            const float s[3] = {m * expf(ls[0]), m * expf(ls[1]), m * expf(ls[2])};
+            // s: the scale that enters M; FILTERED: chain[k] = d log s_k / d scaling_k = exp(2 scaling_k) / v_k, and
+            // extra[k] = g_o o c f^2 / v_k, the opacity coefficient's share
+            float s[3], chain[3], extra[3];
+            if constexpr (FILTERED) {
+                float e[3], v[3], r[3], ratio[3];
+                const float f = filter3d[gi];
+                scene_filtered_scales(ls, f, e, v, r, ratio);
+                const float go = g.opacities ? g.opacities[gi] : 0.0f;
+                const float goc = go * (1.0f / (1.0f + expf(-p.opacity[gi]))) * (ratio[0] * ratio[1] * ratio[2]);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    s[k] = m * r[k];
+                    chain[k] = ratio[k] * ratio[k];
+                    extra[k] = goc * ((f * f) / v[k]);
+                }
+            } else {
+                s[0] = m * expf(ls[0]); s[1] = m * expf(ls[1]); s[2] = m * expf(ls[2]);
+            }
             float gc[6];
 #pragma unroll
             for (int k = 0; k < 6; ++k) gc[k] = g.cov3D ? g.cov3D[6 * gi + k] : 0.0f;
@@ -196,6 +257,7 @@ __global__ __launch_bounds__(kSceneChunk) void k_scene_bwd(int64_t n, float m, l
                 const float dm1 = 2.0f * (Gm[3] * m0 + Gm[4] * m1 + Gm[5] * m2);
                 const float dm2 = 2.0f * (Gm[6] * m0 + Gm[7] * m1 + Gm[8] * m2);
                 dls[k] = (dm0 * R[k] + dm1 * R[3 + k] + dm2 * R[6 + k]) * s[k];
+                if constexpr (FILTERED) dls[k] = fmaf(dls[k], chain[k], extra[k]);
                 dR[k] = dm0 * s[k]; dR[3 + k] = dm1 * s[k]; dR[6 + k] = dm2 * s[k];
             }
             if (d.scaling) {
@@ -234,26 +296,34 @@ static unsigned scene_blocks(int64_t n) {
     return (unsigned)std::min<int64_t>((n + kSceneChunk - 1) / kSceneChunk, kSceneMaxBlocks);
 }
 
-static void launch_scene_fwd(const lsr_scene_dims &d, const lsr_scene_params &p, const lsr_scene_outputs &o, hipStream_t s) {
+// filter3d NULL: the unfiltered instantiation
+#define SCENE_LAUNCH(kernel, K, ...)                                                                              \
+    do {                                                                                                          \
+        if (filter3d) hipLaunchKernelGGL((kernel<K, true>), grid, block, 0, s, __VA_ARGS__, filter3d);            \
+        else hipLaunchKernelGGL((kernel<K, false>), grid, block, 0, s, __VA_ARGS__, (const float *)nullptr);      \
+    } while (0)
+
+static void launch_scene_fwd(const lsr_scene_dims &d, const lsr_scene_params &p, const lsr_scene_outputs &o, const float *filter3d,
+                             hipStream_t s) {
     const dim3 grid(scene_blocks(d.n)), block(kSceneChunk);
     switch (d.sh_coeffs) {
-        case 1: hipLaunchKernelGGL((k_scene_fwd<1>), grid, block, 0, s, d.n, d.scale_modifier, p, o); break;
-        case 4: hipLaunchKernelGGL((k_scene_fwd<4>), grid, block, 0, s, d.n, d.scale_modifier, p, o); break;
-        case 9: hipLaunchKernelGGL((k_scene_fwd<9>), grid, block, 0, s, d.n, d.scale_modifier, p, o); break;
-        case 16: hipLaunchKernelGGL((k_scene_fwd<16>), grid, block, 0, s, d.n, d.scale_modifier, p, o); break;
-        default: hipLaunchKernelGGL((k_scene_fwd<25>), grid, block, 0, s, d.n, d.scale_modifier, p, o); break;
+        case 1: SCENE_LAUNCH(k_scene_fwd, 1, d.n, d.scale_modifier, p, o); break;
+        case 4: SCENE_LAUNCH(k_scene_fwd, 4, d.n, d.scale_modifier, p, o); break;
+        case 9: SCENE_LAUNCH(k_scene_fwd, 9, d.n, d.scale_modifier, p, o); break;
+        case 16: SCENE_LAUNCH(k_scene_fwd, 16, d.n, d.scale_modifier, p, o); break;
+        default: SCENE_LAUNCH(k_scene_fwd, 25, d.n, d.scale_modifier, p, o); break;
     }
 }
 
 static void launch_scene_bwd(const lsr_scene_dims &d, const lsr_scene_params &p, const lsr_scene_out_grads &g,
-                             const lsr_scene_in_grads &o, hipStream_t s) {
+                             const lsr_scene_in_grads &o, const float *filter3d, hipStream_t s) {
     const dim3 grid(scene_blocks(d.n)), block(kSceneChunk);
     switch (d.sh_coeffs) {
-        case 1: hipLaunchKernelGGL((k_scene_bwd<1>), grid, block, 0, s, d.n, d.scale_modifier, p, g, o); break;
-        case 4: hipLaunchKernelGGL((k_scene_bwd<4>), grid, block, 0, s, d.n, d.scale_modifier, p, g, o); break;
-        case 9: hipLaunchKernelGGL((k_scene_bwd<9>), grid, block, 0, s, d.n, d.scale_modifier, p, g, o); break;
-        case 16: hipLaunchKernelGGL((k_scene_bwd<16>), grid, block, 0, s, d.n, d.scale_modifier, p, g, o); break;
-        default: hipLaunchKernelGGL((k_scene_bwd<25>), grid, block, 0, s, d.n, d.scale_modifier, p, g, o); break;
+        case 1: SCENE_LAUNCH(k_scene_bwd, 1, d.n, d.scale_modifier, p, g, o); break;
+        case 4: SCENE_LAUNCH(k_scene_bwd, 4, d.n, d.scale_modifier, p, g, o); break;
+        case 9: SCENE_LAUNCH(k_scene_bwd, 9, d.n, d.scale_modifier, p, g, o); break;
+        case 16: SCENE_LAUNCH(k_scene_bwd, 16, d.n, d.scale_modifier, p, g, o); break;
+        default: SCENE_LAUNCH(k_scene_bwd, 25, d.n, d.scale_modifier, p, g, o); break;
     }
 }
 
@@ -261,38 +331,58 @@ static void launch_scene_bwd(const lsr_scene_dims &d, const lsr_scene_params &p,
 
 using namespace lsr;
 
-extern "C" {
-
-int lsr_scene_activate_forward(const lsr_scene_dims *dims, const lsr_scene_params *params, const lsr_scene_outputs *out,
-                               lsr_stream_t stream) {
+static int scene_forward(const lsr_scene_dims *dims, const lsr_scene_params *params, const float *filter3d, bool filtered,
+                         const lsr_scene_outputs *out, lsr_stream_t stream) {
     note_hip_error(0);
     if (!out) return LSR_ENULL;
     const int rc = scene_check(dims, params);
     if (rc) return rc;
     if (dims->n == 0) return LSR_OK;
-    if (!params->features_dc || !params->opacity || !params->scaling || !params->rotation) return LSR_ENULL;
+    if (!params->features_dc || !params->opacity || !params->scaling || !params->rotation || (filtered && !filter3d)) return LSR_ENULL;
     if ((reinterpret_cast<uintptr_t>(params->rotation) | reinterpret_cast<uintptr_t>(out->rotations)) & 15) return LSR_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    launch_scene_fwd(*dims, *params, *out, s);
+    launch_scene_fwd(*dims, *params, *out, filtered ? filter3d : nullptr, s);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
     return LSR_OK;
 }
 
-int lsr_scene_activate_backward(const lsr_scene_dims *dims, const lsr_scene_params *params,
-                                const lsr_scene_out_grads *dout, const lsr_scene_in_grads *din, lsr_stream_t stream) {
+static int scene_backward(const lsr_scene_dims *dims, const lsr_scene_params *params, const float *filter3d, bool filtered,
+                          const lsr_scene_out_grads *dout, const lsr_scene_in_grads *din, lsr_stream_t stream) {
     note_hip_error(0);
     if (!dout || !din) return LSR_ENULL;
     const int rc = scene_check(dims, params);
     if (rc) return rc;
     if (dims->n == 0) return LSR_OK;
-    if (!params->opacity || !params->scaling || !params->rotation) return LSR_ENULL;
+    if (!params->opacity || !params->scaling || !params->rotation || (filtered && !filter3d)) return LSR_ENULL;
     if ((reinterpret_cast<uintptr_t>(params->rotation) | reinterpret_cast<uintptr_t>(din->rotation)) & 15) return LSR_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    launch_scene_bwd(*dims, *params, *dout, *din, s);
+    launch_scene_bwd(*dims, *params, *dout, *din, filtered ? filter3d : nullptr, s);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
     return LSR_OK;
+}
+
+extern "C" {
+
+int lsr_scene_activate_forward(const lsr_scene_dims *dims, const lsr_scene_params *params, const lsr_scene_outputs *out,
+                               lsr_stream_t stream) {
+    return scene_forward(dims, params, nullptr, false, out, stream);
+}
+
+int lsr_scene_activate_backward(const lsr_scene_dims *dims, const lsr_scene_params *params,
+                                const lsr_scene_out_grads *dout, const lsr_scene_in_grads *din, lsr_stream_t stream) {
+    return scene_backward(dims, params, nullptr, false, dout, din, stream);
+}
+
+int lsr_scene_activate_filtered_forward(const lsr_scene_dims *dims, const lsr_scene_params *params, const float *filter3d,
+                                        const lsr_scene_outputs *out, lsr_stream_t stream) {
+    return scene_forward(dims, params, filter3d, true, out, stream);
+}
+
+int lsr_scene_activate_filtered_backward(const lsr_scene_dims *dims, const lsr_scene_params *params, const float *filter3d,
+                                         const lsr_scene_out_grads *dout, const lsr_scene_in_grads *din, lsr_stream_t stream) {
+    return scene_backward(dims, params, filter3d, true, dout, din, stream);
 }
 
 }  // extern "C"

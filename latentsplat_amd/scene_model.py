@@ -59,15 +59,32 @@ def _prepare(features_dc: Tensor, features_rest: Tensor, opacity: Tensor, scalin
     return (dc, rest, op, sc, _quad(rot)), n, K
 
 
+def _filter(filter_3d, n: int, dev) -> Optional[Tensor]:
+    """A checked, detached, contiguous 3D filter of ``n`` entries on ``dev`` (``None`` stays ``None``).  A filter of another
+    length belongs to another scene, or to this one before a densification or a growth: refused before any launch."""
+    if filter_3d is None:
+        return None
+    if torch.is_tensor(filter_3d) and tuple(filter_3d.shape) not in ((n,), (n, 1)):
+        raise _lib.LsrError(f"filter_3d has shape {tuple(filter_3d.shape)} but the scene has {n} Gaussians: a 3D filter is computed "
+                            "for one set of Gaussians and is stale after a densification, a growth or a pruning; compute it again")
+    if not torch.is_tensor(filter_3d) or not filter_3d.is_cuda or filter_3d.dtype != torch.float32:
+        raise _lib.LsrError("the filtered activation needs float32 ROCm tensors (no CPU fallback): filter_3d is not one")
+    if filter_3d.device != dev:
+        raise _lib.LsrError(f"filter_3d must be on {dev}")
+    return filter_3d.detach().contiguous()
+
+
 def _dims(n: int, K: int, scale_modifier: float) -> _lib.SceneDims:
     return _lib.SceneDims(n=n, sh_coeffs=K, scale_modifier=float(scale_modifier), reserved0=0, reserved1=0)
 
 
 def activate_forward(features_dc: Tensor, features_rest: Tensor, opacity: Tensor, scaling: Tensor, rotation: Tensor,
-                     scale_modifier: float = 1.0, want: Optional[Sequence[str]] = None) -> dict:
+                     scale_modifier: float = 1.0, want: Optional[Sequence[str]] = None, filter_3d: Optional[Tensor] = None) -> dict:
     """``lsr_scene_activate_forward`` as it is (no autograd): the outputs named in ``want`` (default: all of ``shs,
-    opacities, cov3D, scales, rotations``) as a dict; the others are not computed."""
+    opacities, cov3D, scales, rotations``) as a dict; the others are not computed.  With ``filter_3d`` (``(n,)`` or
+    ``(n, 1)``, :func:`latentsplat_amd.filter3d.compute_filter_3d`): ``lsr_scene_activate_filtered_forward``."""
     params, n, K = _prepare(features_dc, features_rest, opacity, scaling, rotation)
+    filt = _filter(filter_3d, n, params[0].device)
     shapes = dict(shs=(n, K, 3), opacities=(n, 1), cov3D=(n, 6), scales=(n, 3), rotations=(n, 4))
     unknown = [k for k in (want or ()) if k not in shapes]
     if unknown:
@@ -80,18 +97,26 @@ def activate_forward(features_dc: Tensor, features_rest: Tensor, opacity: Tensor
     ptrs = _lib.SceneOutputs(**{k: _ptr(t) for k, t in out.items()})
     with torch.cuda.device(dev):
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.lsr_scene_activate_forward(C.byref(_dims(n, K, scale_modifier)),
-                                                  C.byref(_lib.SceneParams(*map(_ptr, params))), C.byref(ptrs), stream),
-                   "lsr_scene_activate_forward")
+        if filt is None:
+            _lib.check(lib.lsr_scene_activate_forward(C.byref(_dims(n, K, scale_modifier)),
+                                                      C.byref(_lib.SceneParams(*map(_ptr, params))), C.byref(ptrs), stream),
+                       "lsr_scene_activate_forward")
+        else:
+            _lib.check(lib.lsr_scene_activate_filtered_forward(C.byref(_dims(n, K, scale_modifier)),
+                                                               C.byref(_lib.SceneParams(*map(_ptr, params))), _ptr(filt),
+                                                               C.byref(ptrs), stream), "lsr_scene_activate_filtered_forward")
     return out
 
 
 def activate_backward(features_dc: Tensor, features_rest: Tensor, opacity: Tensor, scaling: Tensor, rotation: Tensor,
                       grad_shs: Optional[Tensor], grad_opacities: Optional[Tensor], grad_cov3D: Optional[Tensor],
-                      scale_modifier: float = 1.0, want: Optional[Sequence[str]] = None) -> dict:
+                      scale_modifier: float = 1.0, want: Optional[Sequence[str]] = None,
+                      filter_3d: Optional[Tensor] = None) -> dict:
     """``lsr_scene_activate_backward`` as it is: the gradients of the parameters named in ``want`` (default: all five)
-    for the given upstream gradients (``None`` = zero)."""
+    for the given upstream gradients (``None`` = zero).  With ``filter_3d``: ``lsr_scene_activate_filtered_backward`` (the
+    filter is a constant and gets no gradient)."""
     params, n, K = _prepare(features_dc, features_rest, opacity, scaling, rotation)
+    filt = _filter(filter_3d, n, params[0].device)
     unknown = [k for k in (want or ()) if k not in _PARAMS]
     if unknown:
         raise _lib.LsrError(f"unknown gradients {unknown}; expected some of {list(_PARAMS)}")
@@ -110,10 +135,16 @@ def activate_backward(features_dc: Tensor, features_rest: Tensor, opacity: Tenso
     grads = _lib.SceneInGrads(**{k: _ptr(t) for k, t in out.items()})
     with torch.cuda.device(dev):
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.lsr_scene_activate_backward(C.byref(_dims(n, K, scale_modifier)),
-                                                   C.byref(_lib.SceneParams(*map(_ptr, params))),
-                                                   C.byref(_lib.SceneOutGrads(*map(_ptr, ups))), C.byref(grads), stream),
-                   "lsr_scene_activate_backward")
+        if filt is None:
+            _lib.check(lib.lsr_scene_activate_backward(C.byref(_dims(n, K, scale_modifier)),
+                                                       C.byref(_lib.SceneParams(*map(_ptr, params))),
+                                                       C.byref(_lib.SceneOutGrads(*map(_ptr, ups))), C.byref(grads), stream),
+                       "lsr_scene_activate_backward")
+        else:
+            _lib.check(lib.lsr_scene_activate_filtered_backward(C.byref(_dims(n, K, scale_modifier)),
+                                                                C.byref(_lib.SceneParams(*map(_ptr, params))), _ptr(filt),
+                                                                C.byref(_lib.SceneOutGrads(*map(_ptr, ups))), C.byref(grads),
+                                                                stream), "lsr_scene_activate_filtered_backward")
     return out
 
 
@@ -139,6 +170,34 @@ class _ActivateScene(torch.autograd.Function):
             return (None,) * 7
         got = activate_backward(*ctx.saved_tensors, g_shs, g_opacities, g_cov3D, ctx.scale_modifier, want)
         return tuple(got.get(k) for k in _PARAMS) + (None, None)
+
+
+class _ActivateSceneFiltered(torch.autograd.Function):
+    """:class:`_ActivateScene` with the 3D filter inside the map (a constant: no gradient).  The opacity coefficient
+    depends on the scales, so the upstream gradient of the opacities reaches ``scaling`` too."""
+
+    @staticmethod
+    def forward(ctx, features_dc, features_rest, opacity, scaling, rotation, filter_3d, scale_modifier, geometry):
+        ctx.set_materialize_grads(False)
+        want = _FORWARD_OUTPUTS if geometry else _FORWARD_OUTPUTS[:3]
+        out = activate_forward(features_dc, features_rest, opacity, scaling, rotation, scale_modifier, want, filter_3d=filter_3d)
+        ctx.save_for_backward(features_dc, features_rest, opacity, scaling, rotation, filter_3d)
+        ctx.scale_modifier = scale_modifier
+        scales, rotations = out.get("scales"), out.get("rotations")
+        if geometry:
+            ctx.mark_non_differentiable(scales, rotations)
+        return out["shs"], out["opacities"], out["cov3D"], scales, rotations
+
+    @staticmethod
+    def backward(ctx, g_shs, g_opacities, g_cov3D, _g_scales, _g_rotations):
+        either = g_cov3D if g_cov3D is not None else g_opacities
+        reach = (g_shs, g_shs, g_opacities, either, g_cov3D)
+        want = [k for k, need, g in zip(_PARAMS, ctx.needs_input_grad, reach) if need and g is not None]
+        if not want:
+            return (None,) * 8
+        *params, filter_3d = ctx.saved_tensors
+        got = activate_backward(*params, g_shs, g_opacities, g_cov3D, ctx.scale_modifier, want, filter_3d=filter_3d)
+        return tuple(got.get(k) for k in _PARAMS) + (None, None, None)
 
 
 def activate_scene(features_dc: Tensor, features_rest: Tensor, opacity: Tensor, scaling: Tensor, rotation: Tensor,
@@ -298,26 +357,45 @@ class GaussianScene(nn.Module):
         if self.active_sh_degree < self.max_sh_degree:
             self.active_sh_degree += 1
 
-    def _activate(self, scale_modifier: float, geometry: bool):
+    def _activate(self, scale_modifier: float, geometry: bool, filter_3d: Optional[Tensor] = None):
+        if filter_3d is not None and torch.is_tensor(filter_3d) and filter_3d.numel() != self.num_gaussians:
+            _filter(filter_3d, self.num_gaussians, self._xyz.device)          # stale: refused whatever the device
         if not self._xyz.is_cuda:
             raise _lib.LsrError("a GaussianScene is activated and rendered on the MI355X: move it to a ROCm ('cuda') device; "
                                 "there is no CPU fallback")
+        if filter_3d is not None:
+            filt = _filter(filter_3d, self.num_gaussians, self._xyz.device)
+            return _ActivateSceneFiltered.apply(self._features_dc, self._features_rest, self._opacity, self._scaling,
+                                                self._rotation, filt, float(scale_modifier), geometry)
         return _ActivateScene.apply(self._features_dc, self._features_rest, self._opacity, self._scaling, self._rotation,
                                     float(scale_modifier), geometry)
 
-    def activated(self, scale_modifier: float = 1.0) -> Scene3DGS:
+    def compute_filter_3d(self, views: Tensor, width: int, **kw) -> Tensor:
+        """The 3D smoothing filter of this scene's positions for the training cameras ``views`` (a table of
+        ``build_view_table`` / ``make_view_table``) at image width ``width``: ``(n, 1)``, one HIP pass
+        (:func:`latentsplat_amd.filter3d.compute_filter_3d`, which ``kw`` goes to).  The scene does not keep it: it is
+        neither a parameter nor a buffer.  The caller holds the tensor, passes it to :meth:`activated`, :meth:`render` and
+        :meth:`save_ply`, and computes it again when the Gaussians were densified, grown, pruned or have moved."""
+        from .filter3d import compute_filter_3d
+        return compute_filter_3d(self._xyz, views, width, **kw)
+
+    def activated(self, scale_modifier: float = 1.0, filter_3d: Optional[Tensor] = None) -> Scene3DGS:
         """The scene as the rasterizer takes it (differentiable in the parameters; ``scales`` and ``rotations`` are
-        values only).  ``means`` is ``_xyz`` itself; ``sh_degree`` the active degree, ``shs`` all stored bands."""
-        shs, opacities, cov, scales, rotations = self._activate(scale_modifier, True)
+        values only).  ``means`` is ``_xyz`` itself; ``sh_degree`` the active degree, ``shs`` all stored bands.  With
+        ``filter_3d`` (:meth:`compute_filter_3d`) the 3D smoothing filter is inside the activation; ``None`` is the
+        unfiltered map."""
+        shs, opacities, cov, scales, rotations = self._activate(scale_modifier, True, filter_3d)
         return Scene3DGS(means=self._xyz, covariances=cov, opacities=opacities, shs=shs, scales=scales,
                          rotations=rotations, sh_degree=self.active_sh_degree)
 
-    def render(self, views: Tensor, height: int, width: int, scale_modifier: float = 1.0, **kw):
+    def render(self, views: Tensor, height: int, width: int, scale_modifier: float = 1.0, filter_3d: Optional[Tensor] = None,
+               **kw):
         """``rasterize_views`` of the activated scene: ``(color, feature, mask, depth, radii)``.  ``views`` is a table
         of ``build_view_table`` / ``make_view_table`` (one that requires grad receives the camera gradient); ``kw``
-        goes to ``rasterize_views``.  All stored SH coefficients are passed with ``sh_degree=active_sh_degree``."""
+        goes to ``rasterize_views``.  All stored SH coefficients are passed with ``sh_degree=active_sh_degree``.
+        ``filter_3d`` (:meth:`compute_filter_3d`): render the scene with the 3D smoothing filter inside the activation."""
         from .rasterizer import rasterize_views
-        shs, opacities, cov, _, _ = self._activate(scale_modifier, False)
+        shs, opacities, cov, _, _ = self._activate(scale_modifier, False, filter_3d)
         return rasterize_views(views, height, width, self.active_sh_degree, self._xyz, cov, opacities, shs=shs, **kw)
 
     def rows(self) -> Tensor:
@@ -325,10 +403,19 @@ class GaussianScene(nn.Module):
         return parameters_to_rows(self._xyz, self._features_dc, self._features_rest, self._opacity, self._scaling,
                                   self._rotation)
 
-    def save_ply(self, path) -> None:
+    def save_ply(self, path, filter_3d: Optional[Tensor] = None) -> None:
         """Write the raw parameters as a standard 3DGS scene file.  The values go out as they are: a scene that was
-        loaded and is saved untouched has bit-identical rows."""
-        rows = self.rows().cpu()
+        loaded and is saved untouched has bit-identical rows.  With ``filter_3d`` the FUSED scene is written instead:
+        opacity logits and log-scales with the 3D smoothing filter baked in
+        (:func:`latentsplat_amd.filter3d.fused_parameters`), so that any viewer shows the filtered scene; the other
+        columns as they are."""
+        if filter_3d is None:
+            rows = self.rows().cpu()
+        else:
+            from .filter3d import fused_parameters
+            _filter(filter_3d, self.num_gaussians, self._xyz.device)
+            opacity, scaling = fused_parameters(self._opacity, self._scaling, filter_3d)
+            rows = parameters_to_rows(self._xyz, self._features_dc, self._features_rest, opacity, scaling, self._rotation).cpu()
         path = Path(path)
         path.parent.mkdir(exist_ok=True, parents=True)
         _lib.check(_lib.load().lsr_ply_write_scene_host(os.fsencode(str(path)), C.c_void_p(rows.data_ptr()), rows.shape[0],

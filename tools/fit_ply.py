@@ -50,12 +50,20 @@ positions (`--noise-lr` times the current position rate).  No gradient statistic
 `strategy`, `cap_max`, `gaussians_first`, `gaussians_last` and `mcmc_events` (`step, dead, relocated, added, n_in, n_out` of
 every event).  `--strategy adc`, the default, is everything above.
 
+`--filter-3d` trains with the 3D smoothing filter of Mip-Splatting: `scene.compute_filter_3d(views,
+size)` before the first step, after every densification / MCMC event (the filter of another row count is refused) and every
+`--filter-3d-interval` steps (default 100, the published cadence); every render of the fit takes it (`filter_3d=`), the
+targets do not.  Besides the raw `point_cloud.ply`, `point_cloud_fused.ply` holds the scene with the filter baked into
+opacities and scales, which any viewer shows filtered.  `fit.json` then holds `filter_3d`, `filter_3d_interval`,
+`filter_3d_events` (`step, reason, gaussians` of every computation) and `fused_ply`.
+
 usage: python tools/fit_ply.py scene.ply --out DIR [--views 8] [--size 256] [--steps 200] [--noise 1.0] [--seed 0] [--distance 2.5]
                                [--lambda-dssim 0.0] [--drop 0.0] [--densify-interval 0] [--densify-from 0] [--densify-until STEPS]
                                [--densify-grad-threshold 2e-4/VIEWS] [--min-opacity 0.005] [--opacity-reset-interval 0]
                                [--optimizer torch|fused|sparse] [--lr-position-final F] [--lr-position-max-steps S]
                                [--from-points] [--sh-degree-interval 0]
-                               [--strategy adc|mcmc] [--cap-max N] [--noise-lr 5e5] [--opacity-reg 0.01] [--scale-reg 0.01]"""
+                               [--strategy adc|mcmc] [--cap-max N] [--noise-lr 5e5] [--opacity-reg 0.01] [--scale-reg 0.01]
+                               [--filter-3d] [--filter-3d-interval 100]"""
 from __future__ import annotations
 
 import argparse
@@ -122,6 +130,9 @@ def main(argv=None) -> dict:
     ap.add_argument("--noise-lr", type=float, default=5e5, help="mcmc: position noise, times the position rate (the published default)")
     ap.add_argument("--opacity-reg", type=float, default=0.01, help="mcmc: weight of mean(sigmoid(opacity)) in the loss")
     ap.add_argument("--scale-reg", type=float, default=0.01, help="mcmc: weight of mean(exp(scaling)) in the loss")
+    ap.add_argument("--filter-3d", action="store_true",
+                    help="train with the 3D smoothing filter of Mip-Splatting and also write point_cloud_fused.ply")
+    ap.add_argument("--filter-3d-interval", type=int, default=100, help="recompute the 3D filter every this many steps (the published cadence)")
     a = ap.parse_args(argv)
     if a.steps < 1 or a.views < 1:
         sys.exit("fit_ply needs at least one step and one view")
@@ -131,6 +142,8 @@ def main(argv=None) -> dict:
         sys.exit("--drop must be in [0, 1); the intervals must not be negative")
     if a.lr_position_final is not None and (a.lr_position_final < 0.0 or (a.lr_position_max_steps or a.steps) < 1):
         sys.exit("--lr-position-final must not be negative and --lr-position-max-steps must be positive")
+    if a.filter_3d_interval < 1:
+        sys.exit("--filter-3d-interval must be positive")
     if a.cap_max is not None and a.cap_max < 1:
         sys.exit("--cap-max must be positive")
     if not torch.cuda.is_available():
@@ -183,6 +196,15 @@ def main(argv=None) -> dict:
         until = a.steps if a.densify_until is None else a.densify_until
         threshold = 2e-4 / a.views if a.densify_grad_threshold is None else a.densify_grad_threshold
     gaussians_first, events = scene.num_gaussians, []
+    filter_3d, filter_events = None, []
+
+    def refresh_filter(step, reason):
+        nonlocal filter_3d
+        if a.filter_3d:
+            filter_3d = scene.compute_filter_3d(views, a.size)
+            filter_events.append(dict(step=step, reason=reason, gaussians=scene.num_gaussians))
+
+    refresh_filter(0, "start")
     warm = min(WARMUP_STEPS, a.steps // 2)
     losses = []
     t0 = None
@@ -193,10 +215,10 @@ def main(argv=None) -> dict:
         opt.zero_grad(set_to_none=True)
         if densify and step < until:
             means2D = torch.zeros((a.views, scene.num_gaussians, 3), device=dev, requires_grad=True)
-            render, _, _, _, radii = scene.render(views, a.size, a.size, means2D=means2D)
+            render, _, _, _, radii = scene.render(views, a.size, a.size, filter_3d=filter_3d, means2D=means2D)
         else:
             means2D = None
-            render, _, _, _, radii = scene.render(views, a.size, a.size)
+            render, _, _, _, radii = scene.render(views, a.size, a.size, filter_3d=filter_3d)
         loss = photometric_loss(render, target, a.lambda_dssim) if a.lambda_dssim > 0 else (render - target).abs().mean()
         if mcmc is not None:
             loss = loss + mcmc.regularizer(a.opacity_reg, a.scale_reg)
@@ -216,15 +238,19 @@ def main(argv=None) -> dict:
                 size = 20.0 if a.opacity_reset_interval and done > a.opacity_reset_interval else 0.0
                 counts = control.densify_and_prune(opt, threshold, a.min_opacity, float(extent), size, generator=gen_dev)
                 events.append(dict(step=done, **counts))
+                refresh_filter(done, "densify")
         if mcmc is not None:
             done = step + 1
             if a.densify_interval > 0 and a.densify_from < done <= mcmc_until and done % a.densify_interval == 0:
                 events.append(dict(step=done, **mcmc.step(opt, gen_dev)))
+                refresh_filter(done, "mcmc")
             mcmc.inject_noise(xyz_group["lr"], a.noise_lr, gen_dev)
         if control is not None and a.opacity_reset_interval and (step + 1) % a.opacity_reset_interval == 0:
             control.reset_opacity(opt)
         if a.sh_degree_interval and (step + 1) % a.sh_degree_interval == 0:
             scene.oneup_sh_degree()
+        if (step + 1) % a.filter_3d_interval == 0 and not (filter_events and filter_events[-1]["step"] == step + 1):
+            refresh_filter(step + 1, "interval")
     torch.cuda.synchronize(dev)
     per_step = (time.perf_counter() - t0) / (a.steps - warm)
     os.makedirs(a.out, exist_ok=True)
@@ -238,6 +264,10 @@ def main(argv=None) -> dict:
     if mcmc is not None:
         res.update(strategy="mcmc", cap_max=cap_max, gaussians_first=gaussians_first, gaussians_last=scene.num_gaussians,
                    mcmc_events=events)
+    if a.filter_3d:
+        scene.save_ply(os.path.join(a.out, "point_cloud_fused.ply"), filter_3d=filter_3d)
+        res.update(filter_3d=True, filter_3d_interval=a.filter_3d_interval, filter_3d_events=filter_events,
+                   fused_ply="point_cloud_fused.ply")
     with open(os.path.join(a.out, "fit.json"), "w") as f:
         json.dump(res, f, indent=1)
     print(json.dumps(res))
