@@ -6,7 +6,8 @@ Only what the hot path needs: ``csrc/`` (HIP kernels + C ABI), ``rasterizer`` (d
 geometry and SH coefficient rotation), ``depth_head`` (the encoder's depth logits to the adapter's
 depths and opacities; the op itself is ``latentsplat_amd.depth_head.depth_head``), ``ply_export`` / ``ply_import`` (3DGS
 ``.ply`` files out and in), ``scene_model`` (a trainable 3DGS scene: raw parameters activated in HIP), ``density`` (its adaptive density control: clone, split, prune in HIP), ``mcmc`` (the MCMC strategy: relocate dead Gaussians, grow to a cap, covariance-shaped noise, in HIP), ``filter3d`` (the 3D smoothing filter of Mip-Splatting: the sampling-rate bound per Gaussian and the filtered activation, in HIP), ``knn`` (exact 3-nearest-neighbour distances in HIP: the point-cloud initialisation of a scene), ``optim`` (its Adam step fused into one HIP launch, with a visibility-sparse mode), ``losses`` (the 3DGS photometric loss, L1 + D-SSIM,
-and the SSIM metric in HIP) and ``synthetic`` (seeded scenes for tests / bench).
+and the SSIM metric in HIP), ``bilagrid`` (bilateral-grid appearance compensation between render and loss: per-image grids of
+colour affines sliced by position and luminance, and their total variation, in HIP) and ``synthetic`` (seeded scenes for tests / bench).
 """
 __version__ = "0.1.0"
 
@@ -20,6 +21,7 @@ _LAZY = {"rotate_sh": "sh_rotate", "GaussianAdapter": "gaussian_adapter", "Gauss
          "DensityControl": "density",
          "MCMCControl": "mcmc", "sample_by_weight": "mcmc", "relocation_values": "mcmc", "inject_noise": "mcmc",
          "compute_filter_3d": "filter3d", "activate_scene_filtered": "filter3d", "fused_parameters": "filter3d",
+         "bilagrid_slice": "bilagrid", "bilagrid_tv": "bilagrid", "BilateralGrid": "bilagrid",
          "knn3": "knn", "mean_knn_dist2": "knn", "load_points_ply": "ply_import",
          "adam_step": "optim", "SceneAdam": "optim", "expon_lr": "optim", "visible_from_radii": "optim"}
 

@@ -1,5 +1,5 @@
 """ctypes binding of ``liblsr_hip.so`` (C ABI: include/lsr_rasterizer.h, include/lsr_adapter.h, include/lsr_latent.h, include/lsr_ply.h,
-include/lsr_sh_rotate.h, include/lsr_depth_head.h, include/lsr_scene.h, include/lsr_loss.h, include/lsr_density.h, include/lsr_optim.h, include/lsr_knn.h, include/lsr_mcmc.h, include/lsr_filter3d.h).
+include/lsr_sh_rotate.h, include/lsr_depth_head.h, include/lsr_scene.h, include/lsr_loss.h, include/lsr_density.h, include/lsr_optim.h, include/lsr_knn.h, include/lsr_mcmc.h, include/lsr_filter3d.h, include/lsr_bilagrid.h).
 
 The library is built in-tree by ``latentsplat_amd/csrc/Makefile`` (``__graft_entry__.build()``).
 There is no CPU fallback: if the shared object is missing or not loadable this module raises, and
@@ -193,6 +193,13 @@ class PhotometricDims(C.Structure):  # lsr_photometric_dims (include/lsr_loss.h)
                 ("lambda_dssim", C.c_float), ("cov_norm", C.c_float), ("crop", C.c_int32), ("reserved0", C.c_int32)]
 
 
+class BilagridDims(C.Structure):     # lsr_bilagrid_dims (include/lsr_bilagrid.h)
+    _fields_ = [(n, C.c_int32) for n in ("num_views", "height", "width", "num_grids", "grid_l", "grid_y", "grid_x", "reserved0")]
+
+
+BILAGRID_MAX_XY, BILAGRID_MAX_L = 64, 16                            # LSR_BILAGRID_MAX_*
+
+
 class DensifyParams(C.Structure):   # lsr_densify_params (include/lsr_density.h)
     _fields_ = [("grad_threshold", C.c_float), ("dense_extent", C.c_float), ("min_opacity", C.c_float),
                 ("max_screen_size", C.c_float), ("world_limit", C.c_float), ("n_split", C.c_int32),
@@ -253,6 +260,8 @@ EXPORTS = (
     "lsr_mcmc_workspace_bytes", "lsr_mcmc_classify", "lsr_mcmc_sample", "lsr_mcmc_apply", "lsr_mcmc_noise",
     "lsr_filter3d_workspace_bytes", "lsr_filter3d_compute",
     "lsr_scene_activate_filtered_forward", "lsr_scene_activate_filtered_backward",
+    "lsr_bilagrid_slice_path", "lsr_bilagrid_slice_forward", "lsr_bilagrid_slice_backward",
+    "lsr_bilagrid_tv_workspace_bytes", "lsr_bilagrid_tv_forward", "lsr_bilagrid_tv_backward",
 )
 
 _lib = None
@@ -429,6 +438,18 @@ def load():
     lib.lsr_scene_activate_filtered_backward.restype = C.c_int
     lib.lsr_scene_activate_filtered_backward.argtypes = [C.POINTER(SceneDims), C.POINTER(SceneParams), P, C.POINTER(SceneOutGrads),
                                                          C.POINTER(SceneInGrads), P]
+    lib.lsr_bilagrid_slice_path.restype = C.c_int
+    lib.lsr_bilagrid_slice_path.argtypes = [C.POINTER(BilagridDims)]
+    lib.lsr_bilagrid_slice_forward.restype = C.c_int
+    lib.lsr_bilagrid_slice_forward.argtypes = [C.POINTER(BilagridDims), P, P, P, P, P]
+    lib.lsr_bilagrid_slice_backward.restype = C.c_int
+    lib.lsr_bilagrid_slice_backward.argtypes = [C.POINTER(BilagridDims), P, P, P, P, P, P, P]
+    lib.lsr_bilagrid_tv_workspace_bytes.restype = SZ
+    lib.lsr_bilagrid_tv_workspace_bytes.argtypes = [C.POINTER(BilagridDims)]
+    lib.lsr_bilagrid_tv_forward.restype = C.c_int
+    lib.lsr_bilagrid_tv_forward.argtypes = [C.POINTER(BilagridDims), P, P, P, P]
+    lib.lsr_bilagrid_tv_backward.restype = C.c_int
+    lib.lsr_bilagrid_tv_backward.argtypes = [C.POINTER(BilagridDims), P, P, P, P]
     _lib = lib
     return lib
 

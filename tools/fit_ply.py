@@ -57,13 +57,24 @@ targets do not.  Besides the raw `point_cloud.ply`, `point_cloud_fused.ply` hold
 opacities and scales, which any viewer shows filtered.  `fit.json` then holds `filter_3d`, `filter_3d_interval`,
 `filter_3d_events` (`step, reason, gaussians` of every computation) and `fused_ply`.
 
+`--bilateral-grid X Y L` trains with bilateral-grid appearance compensation (`latentsplat_amd.BilateralGrid`):
+every fitted render goes through one X x Y x L grid of colour affines per view before the loss (`1 1 1`: one affine per view,
+the published trainer's exposure compensation; `16 16 8`: the published grid), `--tv-weight` (default 10, the published one)
+times the grids' total variation joins the loss, and the grids take their steps from a `torch.optim.Adam` of their own at
+`--bilateral-grid-lr` (default 2e-3, the published one; like the other rates a default, not a measurement), so the scene's
+optimizer and its re-keying at densification are untouched.  `--target-jitter S` with S > 0 gives every target view a seeded
+per-channel affine (gain uniform in [1 - S, 1 + S], offset uniform in [-S / 4, S / 4]) from a generator of its own: photographs
+that disagree, for the grids to absorb.  `fit.json` then holds `bilateral_grid`, `tv_weight` and `tv_last`, and/or
+`target_jitter`; `bilateral_grids.pt` holds the module's state dict.
+
 usage: python tools/fit_ply.py scene.ply --out DIR [--views 8] [--size 256] [--steps 200] [--noise 1.0] [--seed 0] [--distance 2.5]
                                [--lambda-dssim 0.0] [--drop 0.0] [--densify-interval 0] [--densify-from 0] [--densify-until STEPS]
                                [--densify-grad-threshold 2e-4/VIEWS] [--min-opacity 0.005] [--opacity-reset-interval 0]
                                [--optimizer torch|fused|sparse] [--lr-position-final F] [--lr-position-max-steps S]
                                [--from-points] [--sh-degree-interval 0]
                                [--strategy adc|mcmc] [--cap-max N] [--noise-lr 5e5] [--opacity-reg 0.01] [--scale-reg 0.01]
-                               [--filter-3d] [--filter-3d-interval 100]"""
+                               [--filter-3d] [--filter-3d-interval 100]
+                               [--bilateral-grid X Y L] [--bilateral-grid-lr 2e-3] [--tv-weight 10] [--target-jitter 0]"""
 from __future__ import annotations
 
 import argparse
@@ -133,6 +144,13 @@ def main(argv=None) -> dict:
     ap.add_argument("--filter-3d", action="store_true",
                     help="train with the 3D smoothing filter of Mip-Splatting and also write point_cloud_fused.ply")
     ap.add_argument("--filter-3d-interval", type=int, default=100, help="recompute the 3D filter every this many steps (the published cadence)")
+    ap.add_argument("--bilateral-grid", type=int, nargs=3, default=None, metavar=("X", "Y", "L"),
+                    help="one X x Y x L bilateral grid of colour affines per view between render and loss (default: none; "
+                         "1 1 1: one affine per view; 16 16 8: the published grid)")
+    ap.add_argument("--bilateral-grid-lr", type=float, default=2e-3, help="Adam rate of the grids (the published default, not a measurement)")
+    ap.add_argument("--tv-weight", type=float, default=10.0, help="weight of the grids' total variation in the loss (the published default)")
+    ap.add_argument("--target-jitter", type=float, default=0.0,
+                    help="S > 0: a seeded per-channel affine on every target view, gain in [1 - S, 1 + S], offset in [-S / 4, S / 4] (default 0: none)")
     a = ap.parse_args(argv)
     if a.steps < 1 or a.views < 1:
         sys.exit("fit_ply needs at least one step and one view")
@@ -146,6 +164,10 @@ def main(argv=None) -> dict:
         sys.exit("--filter-3d-interval must be positive")
     if a.cap_max is not None and a.cap_max < 1:
         sys.exit("--cap-max must be positive")
+    if a.target_jitter < 0.0 or a.tv_weight < 0.0 or a.bilateral_grid_lr <= 0.0:
+        sys.exit("--target-jitter and --tv-weight must not be negative, --bilateral-grid-lr must be positive")
+    if a.bilateral_grid is not None and not (1 <= a.bilateral_grid[0] <= 64 and 1 <= a.bilateral_grid[1] <= 64 and 1 <= a.bilateral_grid[2] <= 16):
+        sys.exit("--bilateral-grid X Y L takes 1..64 nodes in x and y and 1..16 in luminance")
     if not torch.cuda.is_available():
         sys.exit("fit_ply needs an MI355X: no ROCm device is visible (there is no CPU fallback)")
     from latentsplat_amd.rasterizer import build_view_table
@@ -160,6 +182,11 @@ def main(argv=None) -> dict:
         ext, intr, near, far = circle_cameras(centre, extent, a.views, a.distance)
         views = build_view_table(ext, intr, near, far, torch.zeros(3, device=dev))
         target = scene.render(views, a.size, a.size)[0]
+        if a.target_jitter > 0.0:       # a generator of its own: the perturbation below draws what it always drew
+            gen_jitter = torch.Generator().manual_seed(a.seed + 0x5eed)
+            gain = 1.0 + a.target_jitter * (2.0 * torch.rand(a.views, 3, generator=gen_jitter) - 1.0)
+            offset = 0.25 * a.target_jitter * (2.0 * torch.rand(a.views, 3, generator=gen_jitter) - 1.0)
+            target = target * gain.to(dev)[:, :, None, None] + offset.to(dev)[:, :, None, None]
         gen = torch.Generator().manual_seed(a.seed)
         noise = dict(UNIT_NOISE, _xyz=POSITION_NOISE * float(extent))
         if a.from_points:
@@ -195,6 +222,12 @@ def main(argv=None) -> dict:
         control = DensityControl(scene)
         until = a.steps if a.densify_until is None else a.densify_until
         threshold = 2e-4 / a.views if a.densify_grad_threshold is None else a.densify_grad_threshold
+    grids, tv = None, None
+    if a.bilateral_grid is not None:
+        from latentsplat_amd.bilagrid import BilateralGrid
+        grids = BilateralGrid(a.views, *a.bilateral_grid).to(dev)
+        grid_opt = torch.optim.Adam(grids.parameters(), lr=a.bilateral_grid_lr, eps=1e-15)
+        view_idx = torch.arange(a.views, dtype=torch.int32, device=dev)
     gaussians_first, events = scene.num_gaussians, []
     filter_3d, filter_events = None, []
 
@@ -219,10 +252,18 @@ def main(argv=None) -> dict:
         else:
             means2D = None
             render, _, _, _, radii = scene.render(views, a.size, a.size, filter_3d=filter_3d)
+        if grids is not None:
+            grid_opt.zero_grad(set_to_none=True)
+            render = grids(render, view_idx)
         loss = photometric_loss(render, target, a.lambda_dssim) if a.lambda_dssim > 0 else (render - target).abs().mean()
         if mcmc is not None:
             loss = loss + mcmc.regularizer(a.opacity_reg, a.scale_reg)
+        if grids is not None:
+            tv = grids.tv_loss()
+            loss = loss + a.tv_weight * tv
         loss.backward()
+        if grids is not None:
+            grid_opt.step()
         if a.lr_position_final is not None:
             xyz_group["lr"] = expon_lr(step, a.lr_position * float(extent), a.lr_position_final * float(extent),
                                        a.lr_position_max_steps or a.steps)
@@ -268,6 +309,11 @@ def main(argv=None) -> dict:
         scene.save_ply(os.path.join(a.out, "point_cloud_fused.ply"), filter_3d=filter_3d)
         res.update(filter_3d=True, filter_3d_interval=a.filter_3d_interval, filter_3d_events=filter_events,
                    fused_ply="point_cloud_fused.ply")
+    if grids is not None:
+        torch.save(grids.state_dict(), os.path.join(a.out, "bilateral_grids.pt"))
+        res.update(bilateral_grid=list(a.bilateral_grid), tv_weight=a.tv_weight, tv_last=float(tv.detach()))
+    if a.target_jitter > 0.0:
+        res.update(target_jitter=a.target_jitter)
     with open(os.path.join(a.out, "fit.json"), "w") as f:
         json.dump(res, f, indent=1)
     print(json.dumps(res))
