@@ -116,12 +116,14 @@ struct RenderFwdParams {
 // contributing pixel has alpha T = 0 everywhere on the sub-block, i.e. no gradient (the stopping entry of a pixel is not
 // blended and lies beyond the pixel's n_contrib).
 template <int NCHP, int WPB, bool RECORD = false>
-__global__ void __launch_bounds__(LSR_WAVE * WPB, (RECORD && WPB == 12) ? 6 : 1)   // (the RECORD instance of 2 x 12 must stay within six waves per SIMD)
+__global__ void __launch_bounds__(LSR_WAVE * WPB, ((RECORD || NCHP == 4) && WPB == 12) ? 6 : 1)   // (the instances of 2 x 12 must stay within six waves per SIMD)
 k_render_fwd(RenderFwdParams p) {
     // Staged entries, one record per list entry: (x, y, a2, c2) (b2, log2(255 o), z / 255, -1 / 255) payload / 255 ...
     // (lsr_blend.h: the loop works in units of 255 alpha).  The odd float4 stride keeps the per-lane staging
     // stores bank-conflict free.  Slot 64 is a null record (x = NaN: never kept) that pads the sub-block lists.
     constexpr int kEnt = (2 + NCHP / 4) | 1;
+    // the plain 4- and 8-channel instances composite two list entries per trip of their inner loop (below)
+    constexpr bool kTwoEntries = !RECORD && (NCHP == 4 || NCHP == 8);
     // One shared object, entries first: the byte offsets kept in the lists are then plain LDS
     // addresses (base 0 folds into the ds_read immediate, no address arithmetic per entry).
     struct Lds {
@@ -227,7 +229,9 @@ k_render_fwd(RenderFwdParams p) {
         for (int c = 0; c < NCHP; ++c) acc[c] = float2_t{0.0f, 0.0f};
         uint32_t stop_pos0 = 0, stop_pos1 = 0;
         float kmax = kAlphaMax255;
-        asm volatile("" : "+v"(kmax));   // kept in a register: as a literal it makes both v_min 64-bit encodings
+        // kept in a register: as a literal it makes both v_min 64-bit encodings.  (Not in the two-entry instances: the loop of
+        // the 4-channel one has no register to spare, and the compiler then quiets the laundered value with a v_max in every trip.)
+        if (!kTwoEntries) asm volatile("" : "+v"(kmax));
         // lanes whose two pixels are both finished (only consulted between batches)
         uint64_t done0 = __ballot(!inside0), done1 = __ballot(!inside1);
 
@@ -328,18 +332,37 @@ k_render_fwd(RenderFwdParams p) {
             // Measured between two builds (profiles/r05_ab_knobs.md): the RECORD instance 0.228 -> 0.221 ms per 16 views, the
             // plain instance 0.2051 -> 0.2080 — so only here.
             uint32_t off_next = RECORD ? lp[0] : 0u;
-            auto entry_step = [&](uint32_t i) __attribute__((always_inline)) {
-                const uint32_t off = RECORD ? off_next : lp[i];
-                const float4 *E = (const float4 *)(ent_base + off);
-                const float4 a = E[0], b = E[1];
-                if (RECORD) off_next = lp[i + 1];
+            // The staging above reads the batch's records only in lanes that stage an entry, so their global loads could still be
+            // outstanding here and every trip of the loop below would carry the waits for them: wait once, on the last load.
+            if (kTwoEntries) asm volatile("" :: "v"(cur.pay[NCHP / 4 - 1].w));
+            // One entry is evaluated in two parts.  entry_front is everything that depends only on the staged record and on
+            // the pixel coordinates: the record reads, the exponent, 255 alpha and the two keep masks.  entry_back is the part
+            // that hangs on the transmittance: alpha T, the room test, the selects and the accumulations, and the rare stop.
+            struct Front {
+                uint32_t off;
                 float2_t pay[NCHP / 2];     // (c, c+1) pairs: either half is broadcast to both pixels by the packed ops' op_sel
+                float2_t zk;                // (z / 255, -1 / 255)
+                float2_t al;                // 255 alpha
+                uint64_t ok0, ok1;
+            };
+            auto read_pay = [&](Front &f) __attribute__((always_inline)) {
+                const float4 *E = (const float4 *)(ent_base + f.off);
 #pragma unroll
                 for (int c4 = 0; c4 < NCHP / 4; ++c4) {
                     const float4 t = E[2 + c4];
-                    pay[2 * c4] = float2_t{t.x, t.y}; pay[2 * c4 + 1] = float2_t{t.z, t.w};
+                    f.pay[2 * c4] = float2_t{t.x, t.y}; f.pay[2 * c4 + 1] = float2_t{t.z, t.w};
                 }
-                const float2_t zk = float2_t{b.z, b.w};   // (z / 255, -1 / 255)
+            };
+            // late_pay: the payload is left to entry_back (the second entry of a trip: it then takes the registers the first
+            // entry's payload has left)
+            auto entry_front = [&](uint32_t off, uint32_t i, bool late_pay) __attribute__((always_inline)) -> Front {
+                Front f;
+                f.off = off;
+                const float4 *E = (const float4 *)(ent_base + off);
+                const float4 a = E[0], b = E[1];
+                if (RECORD) off_next = lp[i + 1];
+                if (!late_pay) read_pay(f);
+                f.zk = float2_t{b.z, b.w};
                 // e'(dx) = dx (a2 dx + b2 dy) + (c2 dy^2 + l2o') for dx = dx0, dx0 - 1 (lsr_blend.h; the backward
                 // performs the identical sequence)
                 const float2_t d2 = float2_t{a.x, a.x} - pxx;
@@ -348,23 +371,28 @@ k_render_fwd(RenderFwdParams p) {
                 const float s = __builtin_fmaf(a.w * dy, dy, b.y);
                 const float2_t p1 = __builtin_elementwise_fma(float2_t{a.z, a.z}, d2, float2_t{t, t});
                 const float2_t ex = __builtin_elementwise_fma(p1, d2, float2_t{s, s});
-                float2_t al;                                                                                   // 255 alpha
                 if (RECORD) {   // (v_min as written: fminf makes the compiler re-canonicalise kmax in every iteration of this register-tight instance)
                     const float e0 = fast_exp2(ex.x), e1 = fast_exp2(ex.y);
                     float m0, m1;
                     asm("v_min_f32 %0, %1, %2" : "=v"(m0) : "v"(kmax), "v"(e0));
                     asm("v_min_f32 %0, %1, %2" : "=v"(m1) : "v"(kmax), "v"(e1));
-                    al = float2_t{m0, m1};
-                } else al = float2_t{fminf(kmax, fast_exp2(ex.x)), fminf(kmax, fast_exp2(ex.y))};
+                    f.al = float2_t{m0, m1};
+                } else f.al = float2_t{fminf(kmax, fast_exp2(ex.x)), fminf(kmax, fast_exp2(ex.y))};
                 // keep <=> 0 <= e' <= l2o' (alpha >= 1/255 and power <= 0): one unsigned comparison of the float bits
                 const uint32_t lim = __float_as_uint(b.y);
-                const uint64_t ok0 = __ballot(__float_as_uint(ex.x) <= lim), ok1 = __ballot(__float_as_uint(ex.y) <= lim);
+                f.ok0 = __ballot(__float_as_uint(ex.x) <= lim); f.ok1 = __ballot(__float_as_uint(ex.y) <= lim);
+                return f;
+            };
+            // `behind`: the entry right behind this one whose front part is already done (two entries per trip), or nullptr
+            auto entry_back = [&](Front &f, Front *behind, bool late_pay) __attribute__((always_inline)) {
+                const uint64_t ok0 = f.ok0, ok1 = f.ok1;
+                if (late_pay) read_pay(f);
                 // aT = 255 alpha T, tT = T (1 - alpha): ONE asm block, so that the compiler's hazard recognizer (which puts a wait
                 // state behind every packed-f32 result that the next instruction reads; the hardware needs none:
                 // tools/microbench/pk_hazard.hip) cannot separate the pair
                 float2_t aT, tT;
-                if (RECORD) asm("v_pk_mul_f32 %0, %2, %3\n\tv_pk_fma_f32 %1, %0, %4, %3" : "=&v"(aT), "=v"(tT) : "v"(al), "v"(T2), "s"(kz2));
-                else asm("v_pk_mul_f32 %0, %2, %3\n\tv_pk_fma_f32 %1, %0, %4, %3 op_sel:[0,1,0]" : "=&v"(aT), "=v"(tT) : "v"(al), "v"(T2), "v"(zk));
+                if (RECORD) asm("v_pk_mul_f32 %0, %2, %3\n\tv_pk_fma_f32 %1, %0, %4, %3" : "=&v"(aT), "=v"(tT) : "v"(f.al), "v"(T2), "s"(kz2));
+                else asm("v_pk_mul_f32 %0, %2, %3\n\tv_pk_fma_f32 %1, %0, %4, %3 op_sel:[0,1,0]" : "=&v"(aT), "=v"(tT) : "v"(f.al), "v"(T2), "v"(f.zk));
                 const uint64_t room0 = __ballot(tT.x >= LSR_T_EPS), room1 = __ballot(tT.y >= LSR_T_EPS);
                 const uint64_t stop0 = ok0 & ~room0, stop1 = ok1 & ~room1;
                 const uint64_t hit0 = ok0 & room0, hit1 = ok1 & room1;
@@ -377,23 +405,42 @@ k_render_fwd(RenderFwdParams p) {
                 }
 #pragma unroll
                 for (int c = 0; c < NCHP; c += 2) {
-                    pk_fma_splat<false>(acc[c], pay[c / 2], ww);
-                    pk_fma_splat<true>(acc[c + 1], pay[c / 2], ww);
+                    pk_fma_splat<false>(acc[c], f.pay[c / 2], ww);
+                    pk_fma_splat<true>(acc[c + 1], f.pay[c / 2], ww);
                 }
-                pk_fma_splat<false>(D2, zk, ww);     // depth  += (z / 255) w'
+                pk_fma_splat<false>(D2, f.zk, ww);     // depth  += (z / 255) w'
                 if (RECORD) asm("v_pk_fma_f32 %0, %1, %2, %0" : "+v"(T2) : "s"(kz2), "v"(ww));   // T -= w' / 255
-                else pk_fma_splat<true>(T2, zk, ww);
+                else pk_fma_splat<true>(T2, f.zk, ww);
                 if (stop0 | stop1) {  // rare, wave-uniform: a pixel's transmittance ran out here
                     // 1-based list position of the stopping entry, from its staging slot
-                    const uint32_t pos = base + 1u + (off - wave_off) / (uint32_t)(kEnt * 16);
+                    const uint32_t pos = base + 1u + (f.off - wave_off) / (uint32_t)(kEnt * 16);
                     const bool st0 = __builtin_amdgcn_inverse_ballot_w64(stop0), st1 = __builtin_amdgcn_inverse_ballot_w64(stop1);
                     stop_pos0 = st0 ? pos : stop_pos0;
                     stop_pos1 = st1 ? pos : stop_pos1;
                     pxx = float2_t{st0 ? __builtin_nanf("") : pxx.x, st1 ? __builtin_nanf("") : pxx.y};   // never kept again
                     done0 |= stop0; done1 |= stop1;
+                    // the entry behind was evaluated at the old coordinates: the stopped pixel must not keep it
+                    if (behind) { behind->ok0 &= ~stop0; behind->ok1 &= ~stop1; }
                 }
             };
-            if (!RECORD) {
+            auto entry_step = [&](uint32_t i) __attribute__((always_inline)) {
+                Front f = entry_front(RECORD ? off_next : lp[i], i, false);
+                entry_back(f, nullptr, false);
+            };
+            if (kTwoEntries) {
+                // Two entries per trip: both list words in one read, the front parts of both entries ahead of the two
+                // transmittance chains (A before B), so that B's reads and exponent fill the slots A's chain leaves.  An odd nk
+                // ends with a single entry (rounding up to the null record that pads every list measured slower:
+                // profiles/fwd_two_entries_ab.md).
+                const uint32_t paired = nk & ~1u;
+                for (uint32_t i = 0; i < paired; i += 2u) {
+                    const uint32_t offA = lp[i], offB = lp[i + 1];
+                    Front fa = entry_front(offA, i, false), fb = entry_front(offB, i + 1u, true);
+                    entry_back(fa, &fb, false);
+                    entry_back(fb, nullptr, true);
+                }
+                if (paired < nk) entry_step(paired);
+            } else if (!RECORD) {
                 for (uint32_t i = 0; i < nk; ++i) entry_step(i);
             } else {
                 // chunks of 32 iterations (the history register); after a chunk the eight lanes of a group OR their
