@@ -241,7 +241,8 @@ def _grad_case(hip_device, case, with_aux, edit_scene=None):
 def _grad_scene(hip_device, sc, H, W, with_aux, row_checks=None):
     """Every input gradient of ``sc`` through rasterize_views against the oracle.  ``row_checks``: optional
     {view: (rows, {"means": row_tol, "cov": row_tol})} — those rows of dL/dmeans3D / dL/dcov3D of that view are ALSO held,
-    on their own, to the per-row mixed bar (a row much smaller than the tensor's largest is not hidden by it)."""
+    on their own, to the per-row mixed bar (a row much smaller than the tensor's largest is not hidden by it).
+    Returns the HIP gradients of the per-view / shared inputs."""
     from latentsplat_amd.rasterizer import rasterize_views
     bi = util.boundary_inputs(sc, H, W, bg=(0.3, 0.1, 0.5))
     V = bi["V"]
@@ -305,6 +306,7 @@ def _grad_scene(hip_device, sc, H, W, with_aux, row_checks=None):
             util.assert_grad_close_except_fragile(got[v].detach().cpu().numpy()[rows], want[v][rows], local(frag[v][0]),
                                                   local(frag[v][1]), ABS_TOL, f"dL/d{name} rows[view {v}]", clean_tol=CLEAN_TOL,
                                                   row_tol=tols[name])
+    return dict(means=means.grad, cov=cov6.grad, opac=opac.grad, m2d=m2d.grad, feat=None if feats is None else feats.grad)
 
 
 GRAD_CASES = {

@@ -207,6 +207,31 @@ class HipRun:
         hdr = self._view(self.geom, self.layout.geom_header, 32, torch.int32).cpu().numpy()
         return f, int(hdr[6])
 
+    def header(self):
+        """The 64 words of the geometry workspace's header (lsr_internal.h kHdr*)."""
+        return self._view(self.geom, self.layout.geom_header, 256, torch.int32).cpu().numpy().view(np.uint32).copy()
+
+    def _item_block(self, k):
+        """Offset and bytes of the k-th of the four consecutive per-item blocks of lsr_internal.h::geom_layout (tile_order,
+        item_cost, tile_order2, half_count); the public layout exports only the last one and tile_start in front of them."""
+        up = lambda x: (x + 255) // 256 * 256
+        n = 2 * self.d.num_views * self.T
+        block = up(n * 4)
+        first = int(self.layout.geom_half_count) - 3 * block
+        assert first == up(int(self.layout.geom_tile_start) + (self.d.num_views * self.T + 1) * 4), \
+            "the geometry workspace's layout changed: tile_order / item_cost / tile_order2 are not where tests/util.py looks"
+        return first + k * block, n * 4
+
+    def item_cost(self):
+        """(V*T, 2) lock-step iterations the RECORD forward counted per half-tile item (defined when header word 9 is set)."""
+        off, nbytes = self._item_block(1)
+        return self._view(self.geom, off, nbytes, torch.int32).cpu().numpy().astype(np.int64).reshape(-1, 2)
+
+    def tile_order2(self):
+        """The 2 V T work items `view T + tile | half << 28` in the order k_order_items gave them (header word 9)."""
+        off, nbytes = self._item_block(2)
+        return self._view(self.geom, off, nbytes, torch.int32).cpu().numpy().view(np.uint32).astype(np.int64)
+
     def n_contrib(self):
         n = self.d.num_views * self.d.height * self.d.width
         return self._view(self.img, self.layout.img_n_contrib, n * 4, torch.int32).cpu().numpy().reshape(
