@@ -1,5 +1,5 @@
 """ctypes binding of ``liblsr_hip.so`` (C ABI: include/lsr_rasterizer.h, include/lsr_adapter.h, include/lsr_latent.h, include/lsr_ply.h,
-include/lsr_sh_rotate.h, include/lsr_depth_head.h, include/lsr_scene.h, include/lsr_loss.h, include/lsr_density.h, include/lsr_optim.h, include/lsr_knn.h, include/lsr_mcmc.h, include/lsr_filter3d.h, include/lsr_bilagrid.h).
+include/lsr_sh_rotate.h, include/lsr_depth_head.h, include/lsr_scene.h, include/lsr_loss.h, include/lsr_density.h, include/lsr_optim.h, include/lsr_knn.h, include/lsr_mcmc.h, include/lsr_filter3d.h, include/lsr_bilagrid.h, include/lsr_transform.h).
 
 The library is built in-tree by ``latentsplat_amd/csrc/Makefile`` (``__graft_entry__.build()``).
 There is no CPU fallback: if the shared object is missing or not loadable this module raises, and
@@ -235,6 +235,27 @@ FILTER3D_PUBLISHED, FILTER3D_PER_VIEW = 0, 1                        # lsr_filter
 FILTER3D_MAX_ROWS, FILTER3D_MAX_VIEWS = 1 << 28, 65536              # LSR_FILTER3D_MAX_*
 
 
+class TransformDims(C.Structure):    # lsr_transform_dims (include/lsr_transform.h)
+    _fields_ = [("n", C.c_int64), ("sh_coeffs", C.c_int32), ("num_transforms", C.c_int32),
+                ("reserved0", C.c_int32), ("reserved1", C.c_int32)]
+
+
+class TransformIn(C.Structure):      # lsr_transform_in
+    _fields_ = [(n, C.c_void_p) for n in ("xyz", "features_rest", "scaling", "rotation")]
+
+
+class TransformOut(C.Structure):     # lsr_transform_out
+    _fields_ = [(n, C.c_void_p) for n in ("xyz", "features_rest", "scaling", "rotation")]
+
+
+TRANSFORM_MAX_DEGREE, TRANSFORM_HEADER_FLOATS = 4, 20               # LSR_TRANSFORM_*
+
+
+def transform_record_floats(degree: int) -> int:
+    """LSR_TRANSFORM_RECORD_FLOATS: the 20-float header and the band blocks 1..degree (20, 29, 54, 103, 184)."""
+    return TRANSFORM_HEADER_FLOATS + sh_rotate_table_floats(degree) - 1
+
+
 def sh_rotate_table_floats(degree: int) -> int:
     """LSR_SH_ROTATE_TABLE_FLOATS: sum of (2l+1)^2 over l <= degree."""
     return (degree + 1) * (2 * degree + 1) * (2 * degree + 3) // 3
@@ -262,6 +283,7 @@ EXPORTS = (
     "lsr_scene_activate_filtered_forward", "lsr_scene_activate_filtered_backward",
     "lsr_bilagrid_slice_path", "lsr_bilagrid_slice_forward", "lsr_bilagrid_slice_backward",
     "lsr_bilagrid_tv_workspace_bytes", "lsr_bilagrid_tv_forward", "lsr_bilagrid_tv_backward",
+    "lsr_transform_records", "lsr_scene_transform",
 )
 
 _lib = None
@@ -450,6 +472,10 @@ def load():
     lib.lsr_bilagrid_tv_forward.argtypes = [C.POINTER(BilagridDims), P, P, P, P]
     lib.lsr_bilagrid_tv_backward.restype = C.c_int
     lib.lsr_bilagrid_tv_backward.argtypes = [C.POINTER(BilagridDims), P, P, P, P]
+    lib.lsr_transform_records.restype = C.c_int
+    lib.lsr_transform_records.argtypes = [I32, P, I32, I32, P, P]
+    lib.lsr_scene_transform.restype = C.c_int
+    lib.lsr_scene_transform.argtypes = [C.POINTER(TransformDims), P, P, C.POINTER(TransformIn), C.POINTER(TransformOut), P]
     _lib = lib
     return lib
 

@@ -379,24 +379,111 @@ class GaussianScene(nn.Module):
         from .filter3d import compute_filter_3d
         return compute_filter_3d(self._xyz, views, width, **kw)
 
-    def activated(self, scale_modifier: float = 1.0, filter_3d: Optional[Tensor] = None) -> Scene3DGS:
+    def _posed(self, transforms: Tensor, transform_idx: Optional[Tensor], filter_3d, scale_modifier: float, geometry: bool,
+               check: bool = True):
+        """The means and the activation of the scene moved by ``transforms``: the canonical parameters through
+        :func:`latentsplat_amd.transform.transform_scene`, then through the unchanged activation."""
+        from .transform import transform_scene
+        if filter_3d is not None:
+            raise _lib.LsrError("transforms together with filter_3d: the 3D filter of a posed scene depends on where its parts "
+                                "stand in front of the cameras and is the caller's to compute; pose the parameters with "
+                                "transform_scene and pass the filter of the posed means to activate_scene_filtered")
+        if not self._xyz.is_cuda:
+            raise _lib.LsrError("a GaussianScene is activated and rendered on the MI355X: move it to a ROCm ('cuda') device; "
+                                "there is no CPU fallback")
+        xyz, rest, scaling, rotation = transform_scene(self._xyz, self._features_rest, self._scaling, self._rotation,
+                                                       transforms, transform_idx, check=check)
+        return xyz, _ActivateScene.apply(self._features_dc, rest, self._opacity, scaling, rotation, float(scale_modifier), geometry)
+
+    def activated(self, scale_modifier: float = 1.0, filter_3d: Optional[Tensor] = None, transforms: Optional[Tensor] = None,
+                  transform_idx: Optional[Tensor] = None, check_transforms: bool = True) -> Scene3DGS:
         """The scene as the rasterizer takes it (differentiable in the parameters; ``scales`` and ``rotations`` are
         values only).  ``means`` is ``_xyz`` itself; ``sh_degree`` the active degree, ``shs`` all stored bands.  With
         ``filter_3d`` (:meth:`compute_filter_3d`) the 3D smoothing filter is inside the activation; ``None`` is the
-        unfiltered map."""
+        unfiltered map.  ``transforms`` / ``transform_idx``: the posed scene, as in :meth:`render` (``means`` is then the
+        posed positions)."""
+        if transforms is not None:
+            xyz, (shs, opacities, cov, scales, rotations) = self._posed(transforms, transform_idx, filter_3d, scale_modifier, True,
+                                                                        check_transforms)
+            return Scene3DGS(means=xyz, covariances=cov, opacities=opacities, shs=shs, scales=scales, rotations=rotations,
+                             sh_degree=self.active_sh_degree)
         shs, opacities, cov, scales, rotations = self._activate(scale_modifier, True, filter_3d)
         return Scene3DGS(means=self._xyz, covariances=cov, opacities=opacities, shs=shs, scales=scales,
                          rotations=rotations, sh_degree=self.active_sh_degree)
 
     def render(self, views: Tensor, height: int, width: int, scale_modifier: float = 1.0, filter_3d: Optional[Tensor] = None,
-               **kw):
+               transforms: Optional[Tensor] = None, transform_idx: Optional[Tensor] = None, check_transforms: bool = True, **kw):
         """``rasterize_views`` of the activated scene: ``(color, feature, mask, depth, radii)``.  ``views`` is a table
         of ``build_view_table`` / ``make_view_table`` (one that requires grad receives the camera gradient); ``kw``
         goes to ``rasterize_views``.  All stored SH coefficients are passed with ``sh_degree=active_sh_degree``.
-        ``filter_3d`` (:meth:`compute_filter_3d`): render the scene with the 3D smoothing filter inside the activation."""
+        ``filter_3d`` (:meth:`compute_filter_3d`): render the scene with the 3D smoothing filter inside the activation.
+
+        ``transforms`` (``(4, 4)`` or ``(T, 4, 4)`` similarities on the scene's device) with ``transform_idx`` (integer
+        ``(n,)``: the transform of each Gaussian; ``None``: transform 0 for all; out of range: not moved) render the POSED
+        scene: the canonical parameters go through :func:`latentsplat_amd.transform.transform_scene` (one more HIP launch;
+        view-dependent colour rotated with the part) and then through the unchanged activation and rasterizer, so the
+        gradients arrive at the canonical parameters; the transforms receive none.  ``check_transforms=True`` refuses what is
+        not a similarity with one host read (a device sync) per call; a training loop that poses parts every step passes
+        ``check_transforms=False``, which reads nothing back.  ``transforms=None`` is the code path
+        without it.  Together with ``filter_3d`` it is refused: the filter of a posed scene is the caller's to compute."""
         from .rasterizer import rasterize_views
+        if transforms is not None:
+            xyz, (shs, opacities, cov, _, _) = self._posed(transforms, transform_idx, filter_3d, scale_modifier, False, check_transforms)
+            return rasterize_views(views, height, width, self.active_sh_degree, xyz, cov, opacities, shs=shs, **kw)
         shs, opacities, cov, _, _ = self._activate(scale_modifier, False, filter_3d)
         return rasterize_views(views, height, width, self.active_sh_degree, self._xyz, cov, opacities, shs=shs, **kw)
+
+    def transform_(self, M: Tensor, idx: Optional[Tensor] = None) -> "GaussianScene":
+        """Move the scene in place by the similarity ``M (4, 4)`` (or ``(T, 4, 4)`` with ``idx (n,)`` naming the transform
+        of each Gaussian; out of range: not moved), under ``no_grad``: ``_xyz``, ``_features_rest`` (every SH band rotated
+        with the scene), ``_scaling`` and ``_rotation`` are overwritten by one HIP launch
+        (:func:`latentsplat_amd.transform.transform_scene_`); ``_features_dc`` and ``_opacity`` stay.  ``M`` may live on
+        any device; anything that is not a similarity is refused.  Returns ``self``.
+
+        What does not survive: the optimizer moments of ``_xyz``, ``_features_rest``, ``_scaling`` and ``_rotation`` (the
+        first moment would have to be rotated with the parameters and ``exp_avg_sq`` is not covariant under a rotation at
+        all), so the caller resets their optimizer state; and a ``filter_3d`` computed before, which must be multiplied by
+        ``s`` (with cameras moved by :func:`latentsplat_amd.transform.transform_cameras`) or computed again."""
+        from .transform import transform_scene_
+        if not self._xyz.is_cuda:
+            raise _lib.LsrError("a GaussianScene is transformed on the MI355X: move it to a ROCm ('cuda') device; there is no "
+                                "CPU fallback")
+        if not torch.is_tensor(M):
+            raise _lib.LsrError("transform_ takes a (4, 4) or (T, 4, 4) tensor")
+        with torch.no_grad():
+            if M.device != self._xyz.device:
+                from .transform import _matrices
+                M = _matrices(M, True).to(self._xyz.device)
+                transform_scene_(self._xyz, self._features_rest, self._scaling, self._rotation, M, idx, check=False)
+            else:
+                transform_scene_(self._xyz, self._features_rest, self._scaling, self._rotation, M, idx)
+        return self
+
+    @classmethod
+    def merge(cls, scenes: Sequence["GaussianScene"], transforms: Optional[Tensor] = None) -> "GaussianScene":
+        """One scene from several: the rows concatenated in order, ``_features_rest`` zero-padded to the highest stored
+        degree, ``active_sh_degree`` the maximum.  With ``transforms (len(scenes), 4, 4)`` scene ``i`` is moved by
+        transform ``i`` first, in ONE launch over the merged tensors with the scene number as the per-Gaussian index
+        (two captures brought into one coordinate system).  The scenes must be on one device."""
+        scenes = list(scenes)
+        if not scenes or any(not isinstance(sc, GaussianScene) for sc in scenes):
+            raise _lib.LsrError("merge takes a non-empty sequence of GaussianScene")
+        dev = scenes[0]._xyz.device
+        if any(sc._xyz.device != dev for sc in scenes):
+            raise _lib.LsrError("merge: the scenes must be on one device")
+        if transforms is not None and (not torch.is_tensor(transforms) or tuple(transforms.shape) != (len(scenes), 4, 4)):
+            raise _lib.LsrError(f"merge: transforms must be ({len(scenes)}, 4, 4), one per scene")
+        rest_rows = max(sc._features_rest.shape[1] for sc in scenes)
+        with torch.no_grad():
+            cat = lambda name: torch.cat([getattr(sc, name).detach() for sc in scenes], dim=0)
+            rest = torch.cat([torch.nn.functional.pad(sc._features_rest.detach(), (0, 0, 0, rest_rows - sc._features_rest.shape[1]))
+                              for sc in scenes], dim=0)
+            merged = cls(cat("_xyz"), cat("_features_dc"), rest, cat("_opacity"), cat("_scaling"), cat("_rotation"),
+                         active_sh_degree=max(sc.active_sh_degree for sc in scenes))
+            if transforms is not None:
+                counts = torch.tensor([sc.num_gaussians for sc in scenes], device=dev)
+                merged.transform_(transforms, torch.repeat_interleave(torch.arange(len(scenes), device=dev), counts))
+        return merged
 
     def rows(self) -> Tensor:
         """The scene as rows of a scene file (:func:`parameters_to_rows`), on the parameters' device."""
