@@ -485,6 +485,13 @@ class GaussianScene(nn.Module):
                 merged.transform_(transforms, torch.repeat_interleave(torch.arange(len(scenes), device=dev), counts))
         return merged
 
+    def quantize(self, **kw):
+        """The scene with its view-dependent colour and its shape replaced by codebook indices
+        (:func:`latentsplat_amd.vq.quantize_scene`, which ``kw`` goes to): a
+        :class:`latentsplat_amd.vq.QuantizedScene`."""
+        from .vq import quantize_scene
+        return quantize_scene(self, **kw)
+
     def rows(self) -> Tensor:
         """The scene as rows of a scene file (:func:`parameters_to_rows`), on the parameters' device."""
         return parameters_to_rows(self._xyz, self._features_dc, self._features_rest, self._opacity, self._scaling,
