@@ -8,7 +8,7 @@ depths and opacities; the op itself is ``latentsplat_amd.depth_head.depth_head``
 ``.ply`` files out and in), ``scene_model`` (a trainable 3DGS scene: raw parameters activated in HIP), ``density`` (its adaptive density control: clone, split, prune in HIP), ``mcmc`` (the MCMC strategy: relocate dead Gaussians, grow to a cap, covariance-shaped noise, in HIP), ``filter3d`` (the 3D smoothing filter of Mip-Splatting: the sampling-rate bound per Gaussian and the filtered activation, in HIP), ``knn`` (exact 3-nearest-neighbour distances in HIP: the point-cloud initialisation of a scene), ``optim`` (its Adam step fused into one HIP launch, with a visibility-sparse mode), ``losses`` (the 3DGS photometric loss, L1 + D-SSIM,
 and the SSIM metric in HIP), ``bilagrid`` (bilateral-grid appearance compensation between render and loss: per-image grids of
 colour affines sliced by position and luminance, and their total variation, in HIP), ``transform`` (similarity transforms of a
-scene: positions, quaternions, log-scales and every SH band of the view-dependent colour in one HIP pass; posed parts, merge), ``vq`` (codebook compression of a scene: weighted k-means with a fused distance-and-argmin on the f32 matrix
+scene: positions, quaternions, log-scales and every SH band of the view-dependent colour in one HIP pass; posed parts, merge), ``pose`` (the same transforms as learnable quaternions, translations and log-scales: the pose gradient of a scene's rigid parts in one HIP pass, reduced per part without atomics), ``vq`` (codebook compression of a scene: weighted k-means with a fused distance-and-argmin on the f32 matrix
 instruction and a bit-reproducible float64 centroid update, in HIP; quantised scenes in and out of one compressed file) and ``synthetic`` (seeded scenes for tests / bench).
 """
 __version__ = "0.1.0"
@@ -27,6 +27,7 @@ _LAZY = {"rotate_sh": "sh_rotate", "GaussianAdapter": "gaussian_adapter", "Gauss
          "knn3": "knn", "mean_knn_dist2": "knn", "load_points_ply": "ply_import",
          "similarity_matrix": "transform", "invert_similarity": "transform", "transform_records": "transform",
          "transform_scene": "transform", "transform_cameras": "transform",
+         "pose_matrices": "pose", "pose_scene": "pose", "PartPoses": "pose",
          "vq_assign": "vq", "vq_update": "vq", "kmeans": "vq", "quantize_scene": "vq", "QuantizedScene": "vq",
          "contribution_weights": "vq",
          "adam_step": "optim", "SceneAdam": "optim", "expon_lr": "optim", "visible_from_radii": "optim"}

@@ -1,5 +1,5 @@
 """ctypes binding of ``liblsr_hip.so`` (C ABI: include/lsr_rasterizer.h, include/lsr_adapter.h, include/lsr_latent.h, include/lsr_ply.h,
-include/lsr_sh_rotate.h, include/lsr_depth_head.h, include/lsr_scene.h, include/lsr_loss.h, include/lsr_density.h, include/lsr_optim.h, include/lsr_knn.h, include/lsr_mcmc.h, include/lsr_filter3d.h, include/lsr_bilagrid.h, include/lsr_transform.h, include/lsr_vq.h).
+include/lsr_sh_rotate.h, include/lsr_depth_head.h, include/lsr_scene.h, include/lsr_loss.h, include/lsr_density.h, include/lsr_optim.h, include/lsr_knn.h, include/lsr_mcmc.h, include/lsr_filter3d.h, include/lsr_bilagrid.h, include/lsr_transform.h, include/lsr_vq.h, include/lsr_pose.h).
 
 The library is built in-tree by ``latentsplat_amd/csrc/Makefile`` (``__graft_entry__.build()``).
 There is no CPU fallback: if the shared object is missing or not loadable this module raises, and
@@ -251,6 +251,14 @@ class TransformOut(C.Structure):     # lsr_transform_out
 TRANSFORM_MAX_DEGREE, TRANSFORM_HEADER_FLOATS = 4, 20               # LSR_TRANSFORM_*
 
 
+class PoseGradIn(C.Structure):       # lsr_pose_grad_in (include/lsr_pose.h)
+    _fields_ = [(n, C.c_void_p) for n in ("xyz", "rotation", "features_rest", "g_xyz", "g_features_rest", "g_scaling",
+                                          "g_rotation")]
+
+
+POSE_MAX_TRANSFORMS = 256                                           # LSR_POSE_MAX_TRANSFORMS
+
+
 class VqDims(C.Structure):           # lsr_vq_dims (include/lsr_vq.h)
     _fields_ = [("n", C.c_int64), ("k", C.c_int32), ("d", C.c_int32), ("reserved0", C.c_int32), ("reserved1", C.c_int32)]
 
@@ -293,6 +301,7 @@ EXPORTS = (
     "lsr_bilagrid_tv_workspace_bytes", "lsr_bilagrid_tv_forward", "lsr_bilagrid_tv_backward",
     "lsr_transform_records", "lsr_scene_transform",
     "lsr_vq_workspace_bytes", "lsr_vq_assign", "lsr_vq_update",
+    "lsr_pose_matrices", "lsr_pose_grad_workspace_bytes", "lsr_scene_pose_grad",
 )
 
 _lib = None
@@ -485,6 +494,12 @@ def load():
     lib.lsr_transform_records.argtypes = [I32, P, I32, I32, P, P]
     lib.lsr_scene_transform.restype = C.c_int
     lib.lsr_scene_transform.argtypes = [C.POINTER(TransformDims), P, P, C.POINTER(TransformIn), C.POINTER(TransformOut), P]
+    lib.lsr_pose_matrices.restype = C.c_int
+    lib.lsr_pose_matrices.argtypes = [I32, P, P, P, P, P]
+    lib.lsr_pose_grad_workspace_bytes.restype = SZ
+    lib.lsr_pose_grad_workspace_bytes.argtypes = [I64, I32, I32]
+    lib.lsr_scene_pose_grad.restype = C.c_int
+    lib.lsr_scene_pose_grad.argtypes = [C.POINTER(TransformDims), P, P, P, C.POINTER(PoseGradIn), P, SZ, P, P, P, P]
     lib.lsr_vq_workspace_bytes.restype = SZ
     lib.lsr_vq_workspace_bytes.argtypes = [I64, I32, I32]
     lib.lsr_vq_assign.restype = C.c_int

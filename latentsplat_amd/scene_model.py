@@ -379,11 +379,16 @@ class GaussianScene(nn.Module):
         from .filter3d import compute_filter_3d
         return compute_filter_3d(self._xyz, views, width, **kw)
 
-    def _posed(self, transforms: Tensor, transform_idx: Optional[Tensor], filter_3d, scale_modifier: float, geometry: bool,
-               check: bool = True):
+    def _posed(self, transforms: Optional[Tensor], transform_idx: Optional[Tensor], filter_3d, scale_modifier: float,
+               geometry: bool, check: bool = True, poses=None):
         """The means and the activation of the scene moved by ``transforms``: the canonical parameters through
-        :func:`latentsplat_amd.transform.transform_scene`, then through the unchanged activation."""
+        :func:`latentsplat_amd.transform.transform_scene`, then through the unchanged activation.  With ``poses`` (a
+        :class:`latentsplat_amd.pose.PartPoses`) instead: through :func:`latentsplat_amd.pose.pose_scene`, which also hands
+        the poses their gradient."""
         from .transform import transform_scene
+        if poses is not None and transforms is not None:
+            raise _lib.LsrError("poses together with transforms: a scene is posed by one or the other (poses are the "
+                                "differentiable form of the same similarities)")
         if filter_3d is not None:
             raise _lib.LsrError("transforms together with filter_3d: the 3D filter of a posed scene depends on where its parts "
                                 "stand in front of the cameras and is the caller's to compute; pose the parameters with "
@@ -391,20 +396,23 @@ class GaussianScene(nn.Module):
         if not self._xyz.is_cuda:
             raise _lib.LsrError("a GaussianScene is activated and rendered on the MI355X: move it to a ROCm ('cuda') device; "
                                 "there is no CPU fallback")
-        xyz, rest, scaling, rotation = transform_scene(self._xyz, self._features_rest, self._scaling, self._rotation,
-                                                       transforms, transform_idx, check=check)
+        if poses is not None:
+            xyz, rest, scaling, rotation = poses(self._xyz, self._features_rest, self._scaling, self._rotation, transform_idx)
+        else:
+            xyz, rest, scaling, rotation = transform_scene(self._xyz, self._features_rest, self._scaling, self._rotation,
+                                                           transforms, transform_idx, check=check)
         return xyz, _ActivateScene.apply(self._features_dc, rest, self._opacity, scaling, rotation, float(scale_modifier), geometry)
 
     def activated(self, scale_modifier: float = 1.0, filter_3d: Optional[Tensor] = None, transforms: Optional[Tensor] = None,
-                  transform_idx: Optional[Tensor] = None, check_transforms: bool = True) -> Scene3DGS:
+                  transform_idx: Optional[Tensor] = None, check_transforms: bool = True, poses=None) -> Scene3DGS:
         """The scene as the rasterizer takes it (differentiable in the parameters; ``scales`` and ``rotations`` are
         values only).  ``means`` is ``_xyz`` itself; ``sh_degree`` the active degree, ``shs`` all stored bands.  With
         ``filter_3d`` (:meth:`compute_filter_3d`) the 3D smoothing filter is inside the activation; ``None`` is the
         unfiltered map.  ``transforms`` / ``transform_idx``: the posed scene, as in :meth:`render` (``means`` is then the
-        posed positions)."""
-        if transforms is not None:
+        posed positions); ``poses``: the same with differentiable poses, as in :meth:`render`."""
+        if transforms is not None or poses is not None:
             xyz, (shs, opacities, cov, scales, rotations) = self._posed(transforms, transform_idx, filter_3d, scale_modifier, True,
-                                                                        check_transforms)
+                                                                        check_transforms, poses)
             return Scene3DGS(means=xyz, covariances=cov, opacities=opacities, shs=shs, scales=scales, rotations=rotations,
                              sh_degree=self.active_sh_degree)
         shs, opacities, cov, scales, rotations = self._activate(scale_modifier, True, filter_3d)
@@ -412,7 +420,8 @@ class GaussianScene(nn.Module):
                          rotations=rotations, sh_degree=self.active_sh_degree)
 
     def render(self, views: Tensor, height: int, width: int, scale_modifier: float = 1.0, filter_3d: Optional[Tensor] = None,
-               transforms: Optional[Tensor] = None, transform_idx: Optional[Tensor] = None, check_transforms: bool = True, **kw):
+               transforms: Optional[Tensor] = None, transform_idx: Optional[Tensor] = None, check_transforms: bool = True,
+               poses=None, **kw):
         """``rasterize_views`` of the activated scene: ``(color, feature, mask, depth, radii)``.  ``views`` is a table
         of ``build_view_table`` / ``make_view_table`` (one that requires grad receives the camera gradient); ``kw``
         goes to ``rasterize_views``.  All stored SH coefficients are passed with ``sh_degree=active_sh_degree``.
@@ -425,10 +434,16 @@ class GaussianScene(nn.Module):
         gradients arrive at the canonical parameters; the transforms receive none.  ``check_transforms=True`` refuses what is
         not a similarity with one host read (a device sync) per call; a training loop that poses parts every step passes
         ``check_transforms=False``, which reads nothing back.  ``transforms=None`` is the code path
-        without it.  Together with ``filter_3d`` it is refused: the filter of a posed scene is the caller's to compute."""
+        without it.  Together with ``filter_3d`` it is refused: the filter of a posed scene is the caller's to compute.
+
+        ``poses`` (a :class:`latentsplat_amd.pose.PartPoses`, with the same ``transform_idx``) poses the parts by learnable
+        quaternions, translations and log-scales instead: the same posed scene, through
+        :func:`latentsplat_amd.pose.pose_scene`, and the poses receive their gradient too.  It excludes ``transforms`` and,
+        like it, ``filter_3d``; ``poses=None`` leaves every other path as it is."""
         from .rasterizer import rasterize_views
-        if transforms is not None:
-            xyz, (shs, opacities, cov, _, _) = self._posed(transforms, transform_idx, filter_3d, scale_modifier, False, check_transforms)
+        if transforms is not None or poses is not None:
+            xyz, (shs, opacities, cov, _, _) = self._posed(transforms, transform_idx, filter_3d, scale_modifier, False,
+                                                           check_transforms, poses)
             return rasterize_views(views, height, width, self.active_sh_degree, xyz, cov, opacities, shs=shs, **kw)
         shs, opacities, cov, _, _ = self._activate(scale_modifier, False, filter_3d)
         return rasterize_views(views, height, width, self.active_sh_degree, self._xyz, cov, opacities, shs=shs, **kw)

@@ -13,8 +13,9 @@ Moving a scene is more than moving its means.  For ``M = [[sR, t], [0, 1]]`` (``
 :func:`transform_scene` is that map as a ``torch.autograd.Function`` over ``lsr_transform_records`` /
 ``lsr_scene_transform`` (csrc/scene_transform.hip, C ABI include/lsr_transform.h): one launch over the parameters each
 way, the backward being the same kernel on the records of the adjoint map.  Several transforms with a per-Gaussian index
-pose the rigid parts of a scene in the same launch.  The transforms are data: they receive no gradient (pose optimisation
-of parts is a follow-up), as the cameras in ``lsr_adapter_backward``.  Covariance-form scenes (``Scene3DGS``, the latent
+pose the rigid parts of a scene in the same launch.  The transforms are data here: a 4x4 matrix is not a chart of the
+similarity group and receives no gradient; :func:`latentsplat_amd.pose.pose_scene` is the same map with the poses as
+quaternions, translations and log-scales, and differentiable in them.  Covariance-form scenes (``Scene3DGS``, the latent
 ``Gaussians``) are not covered.  The kernels take float32 ROCm tensors only; there is no CPU fallback.
 :func:`similarity_matrix`, :func:`invert_similarity` and :func:`transform_cameras` are plain torch and run anywhere."""
 from __future__ import annotations
@@ -238,8 +239,10 @@ def transform_scene(xyz: Tensor, features_rest: Tensor, scaling: Tensor, rotatio
     transform of each Gaussian, ``None`` gives every Gaussian transform 0.  A Gaussian whose ``idx`` lies outside
     ``[0, T)`` passes through bit for bit, and so does its gradient.  ``check`` as in :func:`transform_records` (one host
     read; ``check=False`` for a training loop that poses parts every step).  One HIP launch over the parameters forward
-    and one backward (the same kernel on the adjoint records, which the forward prepares) plus the small records launches;
-    the transforms receive no gradient.  float32 ROCm tensors only."""
+    and one backward (the same kernel on the adjoint records, which the forward prepares) plus the small records launches.
+    The transforms receive no gradient, also when they require one: a 4x4 matrix is not a chart of the similarity group.
+    To fit poses use :func:`latentsplat_amd.pose.pose_scene` (quaternion, translation, log-scale per transform; the same
+    forward bits).  float32 ROCm tensors only."""
     n, K = _check_scene(xyz, features_rest, scaling, rotation)
     M = _matrices(transforms, check)
     if M.device != xyz.device:
