@@ -277,32 +277,99 @@ def sh_rotate_table_floats(degree: int) -> int:
     return (degree + 1) * (2 * degree + 1) * (2 * degree + 3) // 3
 
 
-EXPORTS = (
-    "lsr_abi_version", "lsr_error_string", "lsr_last_hip_error", "lsr_geom_workspace_bytes",
-    "lsr_image_workspace_bytes", "lsr_binning_workspace_bytes", "lsr_grad_workspace_bytes",
-    "lsr_get_layout", "lsr_build_views", "lsr_build_views_depth", "lsr_pack_view", "lsr_forward_prepare", "lsr_forward_render", "lsr_forward_nosync", "lsr_forward_speculative", "lsr_forward_front",
-    "lsr_forward_status", "lsr_forward_abandon", "lsr_backward", "lsr_view_grad_workspace_bytes", "lsr_backward_views",
-    "lsr_profile_enable", "lsr_profile_num_stages", "lsr_profile_stage_name", "lsr_profile_read",
-    "lsr_debug_set_knob", "lsr_set_projection_contraction", "lsr_get_projection_contraction",
-    "lsr_adapter_forward", "lsr_adapter_backward", "lsr_latent_forward", "lsr_latent_backward",
-    "lsr_ply_pack", "lsr_ply_write_host", "lsr_ply_read_header", "lsr_ply_read_rows", "lsr_ply_unpack",
-    "lsr_ply_pack_scene", "lsr_ply_sh_axes_matrix", "lsr_ply_write_scene_host",
-    "lsr_sh_rotation_matrices", "lsr_sh_rotate_forward", "lsr_sh_rotate_backward",
-    "lsr_depth_head_forward", "lsr_depth_head_backward",
-    "lsr_scene_activate_forward", "lsr_scene_activate_backward",
-    "lsr_photometric_workspace_bytes", "lsr_photometric_forward", "lsr_photometric_backward",
-    "lsr_density_accumulate", "lsr_densify_workspace_bytes", "lsr_densify_plan", "lsr_densify_apply",
-    "lsr_adam_step",
-    "lsr_knn3_workspace_bytes", "lsr_knn3", "lsr_ply_read_points_header", "lsr_ply_read_points",
-    "lsr_mcmc_workspace_bytes", "lsr_mcmc_classify", "lsr_mcmc_sample", "lsr_mcmc_apply", "lsr_mcmc_noise",
-    "lsr_filter3d_workspace_bytes", "lsr_filter3d_compute",
-    "lsr_scene_activate_filtered_forward", "lsr_scene_activate_filtered_backward",
-    "lsr_bilagrid_slice_path", "lsr_bilagrid_slice_forward", "lsr_bilagrid_slice_backward",
-    "lsr_bilagrid_tv_workspace_bytes", "lsr_bilagrid_tv_forward", "lsr_bilagrid_tv_backward",
-    "lsr_transform_records", "lsr_scene_transform",
-    "lsr_vq_workspace_bytes", "lsr_vq_assign", "lsr_vq_update",
-    "lsr_pose_matrices", "lsr_pose_grad_workspace_bytes", "lsr_scene_pose_grad",
-)
+_P, _I32, _I64, _SZ, _F, _INT, _STR = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t, C.c_float, C.c_int, C.c_char_p
+_ptr_to = C.POINTER
+_FWD = [_ptr_to(Dims), _ptr_to(Inputs), _P, _P, _P, _I64, _I32, _ptr_to(Outputs)]
+_BWD = [_ptr_to(Dims), _ptr_to(Inputs), _P, _P, _P, _I64, _P, _ptr_to(Outputs), _ptr_to(OutGrads), _P, _ptr_to(InGrads), _P]
+_SCENE = [_ptr_to(SceneDims), _ptr_to(SceneParams)]
+
+# every export of the library: name -> (restype, argtypes); argtypes None = left unset (no arguments, or ctypes' conversions)
+PROTOTYPES = {
+    "lsr_abi_version": (_INT, None),
+    "lsr_error_string": (_STR, [_INT]),
+    "lsr_last_hip_error": (_INT, None),
+    "lsr_geom_workspace_bytes": (_SZ, [_ptr_to(Dims)]),
+    "lsr_image_workspace_bytes": (_SZ, [_ptr_to(Dims)]),
+    "lsr_binning_workspace_bytes": (_SZ, [_ptr_to(Dims), _I64, _I32]),
+    "lsr_grad_workspace_bytes": (_SZ, [_ptr_to(Dims)]),
+    "lsr_get_layout": (_INT, [_ptr_to(Dims), _I64, _ptr_to(Layout)]),
+    "lsr_build_views": (_INT, [_I32, _P, _P, _P, _P, _P, _I32, _I32, _P, _P]),
+    "lsr_build_views_depth": (_INT, [_I32, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P]),
+    "lsr_pack_view": (_INT, [_P, _P, _P, _P, _F, _F, _P, _P, _P, _P]),
+    "lsr_forward_prepare": (_INT, [_ptr_to(Dims), _ptr_to(Inputs), _P, _P, _ptr_to(_I64), _ptr_to(_I32), _P]),
+    "lsr_forward_render": (_INT, _FWD + [_P]),
+    "lsr_forward_nosync": (_INT, _FWD + [_P]),
+    "lsr_forward_speculative": (_INT, _FWD + [_ptr_to(_I64), _ptr_to(_I32), _ptr_to(_I32), _P]),
+    "lsr_forward_front": (_INT, [_ptr_to(Dims), _ptr_to(Inputs), _P, _P, _I64, _P]),
+    "lsr_forward_status": (_INT, [_ptr_to(Dims), _P, _ptr_to(_I64), _ptr_to(_I32), _ptr_to(_I32), _P]),
+    "lsr_forward_abandon": (_INT, [_P]),
+    "lsr_backward": (_INT, _BWD),
+    "lsr_view_grad_workspace_bytes": (_SZ, [_ptr_to(Dims)]),
+    "lsr_backward_views": (_INT, _BWD + [_P, _P]),
+    "lsr_profile_enable": (None, [_INT]),
+    "lsr_profile_num_stages": (_INT, None),
+    "lsr_profile_stage_name": (_STR, [_INT]),
+    "lsr_profile_read": (_INT, [_ptr_to(C.c_double), _ptr_to(_I64)]),
+    "lsr_debug_set_knob": (_INT, [_STR, _INT]),
+    "lsr_set_projection_contraction": (_INT, [_INT]),
+    "lsr_get_projection_contraction": (_INT, None),
+    "lsr_adapter_forward": (_INT, [_ptr_to(AdapterDims), _ptr_to(AdapterInputs), _ptr_to(AdapterOutputs), _P]),
+    "lsr_adapter_backward": (_INT, [_ptr_to(AdapterDims), _ptr_to(AdapterInputs), _ptr_to(AdapterOutGrads),
+                                    _ptr_to(AdapterInGrads), _P]),
+    "lsr_latent_forward": (_INT, [_ptr_to(LatentDims), _ptr_to(LatentInputs), _ptr_to(LatentOutputs), _P]),
+    "lsr_latent_backward": (_INT, [_ptr_to(LatentDims), _ptr_to(LatentInputs), _ptr_to(LatentOutGrads), _P, _P]),
+    "lsr_ply_pack": (_INT, [_I64, _I32, _ptr_to(PlyInputs), _P, _P]),
+    "lsr_ply_write_host": (_INT, [_STR, _P, _I64]),
+    "lsr_ply_read_header": (_INT, [_STR, _ptr_to(PlyLayout)]),
+    "lsr_ply_read_rows": (_INT, [_STR, _P, _I64]),
+    "lsr_ply_unpack": (_INT, [_ptr_to(PlyLayout), _P, _I32, _ptr_to(PlyOutputs), _P]),
+    "lsr_ply_pack_scene": (_INT, [_I64, _ptr_to(PlySceneInputs), _ptr_to(PlySceneOpts), _P, _P]),
+    "lsr_ply_sh_axes_matrix": (_INT, [_P]),
+    "lsr_ply_write_scene_host": (_INT, [_STR, _P, _I64, _I32]),
+    "lsr_sh_rotation_matrices": (_INT, [_I32, _P, _I64, _I64, _I32, _P, _P]),
+    "lsr_sh_rotate_forward": (_INT, [_ptr_to(ShRotateDims)] + [_P] * 7),
+    "lsr_sh_rotate_backward": (_INT, [_ptr_to(ShRotateDims)] + [_P] * 7),
+    "lsr_depth_head_forward": (_INT, [_ptr_to(DepthHeadDims)] + [_P] * 8),
+    "lsr_depth_head_backward": (_INT, [_ptr_to(DepthHeadDims)] + [_P] * 8),
+    "lsr_scene_activate_forward": (_INT, _SCENE + [_ptr_to(SceneOutputs), _P]),
+    "lsr_scene_activate_backward": (_INT, _SCENE + [_ptr_to(SceneOutGrads), _ptr_to(SceneInGrads), _P]),
+    "lsr_photometric_workspace_bytes": (_SZ, [_ptr_to(PhotometricDims)]),
+    "lsr_photometric_forward": (_INT, [_ptr_to(PhotometricDims)] + [_P] * 9),
+    "lsr_photometric_backward": (_INT, [_ptr_to(PhotometricDims)] + [_P] * 6),
+    "lsr_density_accumulate": (_INT, [_I32, _I64, _P, _P, _P, _P, _P, _P]),
+    "lsr_densify_workspace_bytes": (_SZ, [_I64]),
+    "lsr_densify_plan": (_INT, [_I64, _P, _P, _P, _P, _P, _ptr_to(DensifyParams), _P, _I64, _P, _P, _P]),
+    "lsr_densify_apply": (_INT, [_I64, _I64, _P, _P, _I32, _ptr_to(DensifyTable), _I32, _P, _P, _P, _I64, _P]),
+    "lsr_adam_step": (_INT, [_ptr_to(AdamTable), _I32, _P, _I64, _P]),
+    "lsr_knn3_workspace_bytes": (_SZ, [_I64]),
+    "lsr_knn3": (_INT, [_I64, _P, _P, _P, _P, _P, _P]),
+    "lsr_ply_read_points_header": (_INT, [_STR, _ptr_to(_I64), _ptr_to(_I32)]),
+    "lsr_ply_read_points": (_INT, [_STR, _P, _P, _I64]),
+    "lsr_mcmc_workspace_bytes": (_SZ, [_I64, _I64]),
+    "lsr_mcmc_classify": (_INT, [_I64, _P, _F, _P, _P, _P, _P, _P]),
+    "lsr_mcmc_sample": (_INT, [_I64, _P, _I64, _P, _P, _P, _P, _P, _P]),
+    "lsr_mcmc_apply": (_INT, [_I64, _I64, _P, _P, _P, _ptr_to(McmcTable), _I32, _F, _P, _P]),
+    "lsr_mcmc_noise": (_INT, [_I64, _P, _P, _P, _P, _P, _F, _P]),
+    "lsr_filter3d_workspace_bytes": (_SZ, [_I64, _I32]),
+    "lsr_filter3d_compute": (_INT, [_I64, _P, _I32, _P, _I32, _F, _F, _I32, _P, _P, _P, _P]),
+    "lsr_scene_activate_filtered_forward": (_INT, _SCENE + [_P, _ptr_to(SceneOutputs), _P]),
+    "lsr_scene_activate_filtered_backward": (_INT, _SCENE + [_P, _ptr_to(SceneOutGrads), _ptr_to(SceneInGrads), _P]),
+    "lsr_bilagrid_slice_path": (_INT, [_ptr_to(BilagridDims)]),
+    "lsr_bilagrid_slice_forward": (_INT, [_ptr_to(BilagridDims)] + [_P] * 5),
+    "lsr_bilagrid_slice_backward": (_INT, [_ptr_to(BilagridDims)] + [_P] * 7),
+    "lsr_bilagrid_tv_workspace_bytes": (_SZ, [_ptr_to(BilagridDims)]),
+    "lsr_bilagrid_tv_forward": (_INT, [_ptr_to(BilagridDims)] + [_P] * 4),
+    "lsr_bilagrid_tv_backward": (_INT, [_ptr_to(BilagridDims)] + [_P] * 4),
+    "lsr_transform_records": (_INT, [_I32, _P, _I32, _I32, _P, _P]),
+    "lsr_scene_transform": (_INT, [_ptr_to(TransformDims), _P, _P, _ptr_to(TransformIn), _ptr_to(TransformOut), _P]),
+    "lsr_vq_workspace_bytes": (_SZ, [_I64, _I32, _I32]),
+    "lsr_vq_assign": (_INT, [_ptr_to(VqDims)] + [_P] * 6),
+    "lsr_vq_update": (_INT, [_ptr_to(VqDims)] + [_P] * 8),
+    "lsr_pose_matrices": (_INT, [_I32, _P, _P, _P, _P, _P]),
+    "lsr_pose_grad_workspace_bytes": (_SZ, [_I64, _I32, _I32]),
+    "lsr_scene_pose_grad": (_INT, [_ptr_to(TransformDims), _P, _P, _P, _ptr_to(PoseGradIn), _P, _SZ, _P, _P, _P, _P]),
+}
+EXPORTS = tuple(PROTOTYPES)
 
 _lib = None
 ABI_VERSION = 10    # include/lsr_rasterizer.h LSR_ABI_VERSION
@@ -335,184 +402,25 @@ def load():
         lib = C.CDLL(_SO)
     except OSError as e:  # e.g. libamdhip64 missing on a machine without ROCm
         raise LsrError(f"cannot load {_SO}: {e}") from e
-    P, I32, I64, SZ = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t
-    lib.lsr_abi_version.restype = C.c_int
-    # checked before any other prototype is bound: the structs below are this version's (an older or newer build would
+    lib.lsr_abi_version.restype = PROTOTYPES["lsr_abi_version"][0]
+    # checked before any other prototype is bound: the structs above are this version's (an older or newer build would
     # be handed structs of the wrong size; there is no compatibility mode)
     abi = lib.lsr_abi_version()
     if abi != ABI_VERSION:
         raise LsrError(f"{_SO}: ABI version {abi}, this package needs {ABI_VERSION}; rebuild it "
                        "(`python -c 'import __graft_entry__ as g; g.build()'`)")
-    lib.lsr_error_string.restype = C.c_char_p
-    lib.lsr_error_string.argtypes = [C.c_int]
-    lib.lsr_last_hip_error.restype = C.c_int
-    for name in ("lsr_geom_workspace_bytes", "lsr_image_workspace_bytes", "lsr_grad_workspace_bytes",
-                 "lsr_view_grad_workspace_bytes"):
-        getattr(lib, name).restype = SZ
-        getattr(lib, name).argtypes = [C.POINTER(Dims)]
-    lib.lsr_binning_workspace_bytes.restype = SZ
-    lib.lsr_binning_workspace_bytes.argtypes = [C.POINTER(Dims), I64, I32]
-    lib.lsr_get_layout.restype = C.c_int
-    lib.lsr_get_layout.argtypes = [C.POINTER(Dims), I64, C.POINTER(Layout)]
-    lib.lsr_build_views.restype = C.c_int
-    lib.lsr_build_views.argtypes = [I32, P, P, P, P, P, I32, I32, P, P]
-    lib.lsr_build_views_depth.restype = C.c_int
-    lib.lsr_build_views_depth.argtypes = [I32, P, P, P, P, P, I32, I32, I32, P, P]
-    lib.lsr_pack_view.restype = C.c_int
-    lib.lsr_pack_view.argtypes = [P, P, P, P, C.c_float, C.c_float, P, P, P, P]
-    lib.lsr_forward_prepare.restype = C.c_int
-    lib.lsr_forward_prepare.argtypes = [C.POINTER(Dims), C.POINTER(Inputs), P, P, C.POINTER(I64),
-                                        C.POINTER(I32), P]
-    lib.lsr_forward_render.restype = C.c_int
-    lib.lsr_forward_render.argtypes = [C.POINTER(Dims), C.POINTER(Inputs), P, P, P, I64, I32,
-                                       C.POINTER(Outputs), P]
-    lib.lsr_forward_nosync.restype = C.c_int
-    lib.lsr_forward_nosync.argtypes = [C.POINTER(Dims), C.POINTER(Inputs), P, P, P, I64, I32, C.POINTER(Outputs), P]
-    lib.lsr_forward_speculative.restype = C.c_int
-    lib.lsr_forward_speculative.argtypes = [C.POINTER(Dims), C.POINTER(Inputs), P, P, P, I64, I32, C.POINTER(Outputs),
-                                            C.POINTER(I64), C.POINTER(I32), C.POINTER(I32), P]
-    lib.lsr_forward_front.restype = C.c_int
-    lib.lsr_forward_front.argtypes = [C.POINTER(Dims), C.POINTER(Inputs), P, P, I64, P]
-    lib.lsr_forward_abandon.restype = C.c_int
-    lib.lsr_forward_abandon.argtypes = [P]
-    lib.lsr_forward_status.restype = C.c_int
-    lib.lsr_forward_status.argtypes = [C.POINTER(Dims), P, C.POINTER(I64), C.POINTER(I32), C.POINTER(I32), P]
-    lib.lsr_backward.restype = C.c_int
-    lib.lsr_backward.argtypes = [C.POINTER(Dims), C.POINTER(Inputs), P, P, P, I64, P, C.POINTER(Outputs),
-                                 C.POINTER(OutGrads), P, C.POINTER(InGrads), P]
-    lib.lsr_backward_views.restype = C.c_int
-    lib.lsr_backward_views.argtypes = [C.POINTER(Dims), C.POINTER(Inputs), P, P, P, I64, P, C.POINTER(Outputs),
-                                       C.POINTER(OutGrads), P, C.POINTER(InGrads), P, P, P]
-    lib.lsr_profile_enable.argtypes = [C.c_int]
-    lib.lsr_profile_stage_name.restype = C.c_char_p
-    lib.lsr_profile_stage_name.argtypes = [C.c_int]
-    lib.lsr_profile_read.argtypes = [C.POINTER(C.c_double), C.POINTER(I64)]
-    lib.lsr_debug_set_knob.restype = C.c_int
-    lib.lsr_debug_set_knob.argtypes = [C.c_char_p, C.c_int]
-    lib.lsr_set_projection_contraction.restype = C.c_int
-    lib.lsr_set_projection_contraction.argtypes = [C.c_int]
-    lib.lsr_get_projection_contraction.restype = C.c_int
-    lib.lsr_adapter_forward.restype = C.c_int
-    lib.lsr_adapter_forward.argtypes = [C.POINTER(AdapterDims), C.POINTER(AdapterInputs),
-                                        C.POINTER(AdapterOutputs), P]
-    lib.lsr_adapter_backward.restype = C.c_int
-    lib.lsr_adapter_backward.argtypes = [C.POINTER(AdapterDims), C.POINTER(AdapterInputs),
-                                         C.POINTER(AdapterOutGrads), C.POINTER(AdapterInGrads), P]
-    lib.lsr_latent_forward.restype = C.c_int
-    lib.lsr_latent_forward.argtypes = [C.POINTER(LatentDims), C.POINTER(LatentInputs),
-                                       C.POINTER(LatentOutputs), P]
-    lib.lsr_latent_backward.restype = C.c_int
-    lib.lsr_latent_backward.argtypes = [C.POINTER(LatentDims), C.POINTER(LatentInputs),
-                                        C.POINTER(LatentOutGrads), P, P]
-    lib.lsr_ply_pack.restype = C.c_int
-    lib.lsr_ply_pack.argtypes = [I64, I32, C.POINTER(PlyInputs), P, P]
-    lib.lsr_ply_write_host.restype = C.c_int
-    lib.lsr_ply_write_host.argtypes = [C.c_char_p, P, I64]
-    lib.lsr_ply_read_header.restype = C.c_int
-    lib.lsr_ply_read_header.argtypes = [C.c_char_p, C.POINTER(PlyLayout)]
-    lib.lsr_ply_read_rows.restype = C.c_int
-    lib.lsr_ply_read_rows.argtypes = [C.c_char_p, P, I64]
-    lib.lsr_ply_unpack.restype = C.c_int
-    lib.lsr_ply_unpack.argtypes = [C.POINTER(PlyLayout), P, I32, C.POINTER(PlyOutputs), P]
-    lib.lsr_ply_pack_scene.restype = C.c_int
-    lib.lsr_ply_pack_scene.argtypes = [I64, C.POINTER(PlySceneInputs), C.POINTER(PlySceneOpts), P, P]
-    lib.lsr_ply_sh_axes_matrix.restype = C.c_int
-    lib.lsr_ply_sh_axes_matrix.argtypes = [P]
-    lib.lsr_ply_write_scene_host.restype = C.c_int
-    lib.lsr_ply_write_scene_host.argtypes = [C.c_char_p, P, I64, I32]
-    lib.lsr_sh_rotation_matrices.restype = C.c_int
-    lib.lsr_sh_rotation_matrices.argtypes = [I32, P, I64, I64, I32, P, P]
-    lib.lsr_sh_rotate_forward.restype = C.c_int
-    lib.lsr_sh_rotate_forward.argtypes = [C.POINTER(ShRotateDims), P, P, P, P, P, P, P]
-    lib.lsr_sh_rotate_backward.restype = C.c_int
-    lib.lsr_sh_rotate_backward.argtypes = [C.POINTER(ShRotateDims), P, P, P, P, P, P, P]
-    lib.lsr_depth_head_forward.restype = C.c_int
-    lib.lsr_depth_head_forward.argtypes = [C.POINTER(DepthHeadDims), P, P, P, P, P, P, P, P]
-    lib.lsr_depth_head_backward.restype = C.c_int
-    lib.lsr_depth_head_backward.argtypes = [C.POINTER(DepthHeadDims), P, P, P, P, P, P, P, P]
-    lib.lsr_scene_activate_forward.restype = C.c_int
-    lib.lsr_scene_activate_forward.argtypes = [C.POINTER(SceneDims), C.POINTER(SceneParams), C.POINTER(SceneOutputs), P]
-    lib.lsr_scene_activate_backward.restype = C.c_int
-    lib.lsr_scene_activate_backward.argtypes = [C.POINTER(SceneDims), C.POINTER(SceneParams), C.POINTER(SceneOutGrads),
-                                                C.POINTER(SceneInGrads), P]
-    lib.lsr_photometric_workspace_bytes.restype = SZ
-    lib.lsr_photometric_workspace_bytes.argtypes = [C.POINTER(PhotometricDims)]
-    lib.lsr_photometric_forward.restype = C.c_int
-    lib.lsr_photometric_forward.argtypes = [C.POINTER(PhotometricDims), P, P, P, P, P, P, P, P, P]
-    lib.lsr_photometric_backward.restype = C.c_int
-    lib.lsr_photometric_backward.argtypes = [C.POINTER(PhotometricDims), P, P, P, P, P, P]
-    lib.lsr_density_accumulate.restype = C.c_int
-    lib.lsr_density_accumulate.argtypes = [I32, I64, P, P, P, P, P, P]
-    lib.lsr_densify_workspace_bytes.restype = SZ
-    lib.lsr_densify_workspace_bytes.argtypes = [I64]
-    lib.lsr_densify_plan.restype = C.c_int
-    lib.lsr_densify_plan.argtypes = [I64, P, P, P, P, P, C.POINTER(DensifyParams), P, I64, P, P, P]
-    lib.lsr_densify_apply.restype = C.c_int
-    lib.lsr_densify_apply.argtypes = [I64, I64, P, P, I32, C.POINTER(DensifyTable), I32, P, P, P, I64, P]
-    lib.lsr_adam_step.restype = C.c_int
-    lib.lsr_adam_step.argtypes = [C.POINTER(AdamTable), I32, P, I64, P]
-    lib.lsr_knn3_workspace_bytes.restype = SZ
-    lib.lsr_knn3_workspace_bytes.argtypes = [I64]
-    lib.lsr_knn3.restype = C.c_int
-    lib.lsr_knn3.argtypes = [I64, P, P, P, P, P, P]
-    lib.lsr_ply_read_points_header.restype = C.c_int
-    lib.lsr_ply_read_points_header.argtypes = [C.c_char_p, C.POINTER(I64), C.POINTER(I32)]
-    lib.lsr_ply_read_points.restype = C.c_int
-    lib.lsr_ply_read_points.argtypes = [C.c_char_p, P, P, I64]
-    lib.lsr_mcmc_workspace_bytes.restype = SZ
-    lib.lsr_mcmc_workspace_bytes.argtypes = [I64, I64]
-    lib.lsr_mcmc_classify.restype = C.c_int
-    lib.lsr_mcmc_classify.argtypes = [I64, P, C.c_float, P, P, P, P, P]
-    lib.lsr_mcmc_sample.restype = C.c_int
-    lib.lsr_mcmc_sample.argtypes = [I64, P, I64, P, P, P, P, P, P]
-    lib.lsr_mcmc_apply.restype = C.c_int
-    lib.lsr_mcmc_apply.argtypes = [I64, I64, P, P, P, C.POINTER(McmcTable), I32, C.c_float, P, P]
-    lib.lsr_mcmc_noise.restype = C.c_int
-    lib.lsr_mcmc_noise.argtypes = [I64, P, P, P, P, P, C.c_float, P]
-    lib.lsr_filter3d_workspace_bytes.restype = SZ
-    lib.lsr_filter3d_workspace_bytes.argtypes = [I64, I32]
-    lib.lsr_filter3d_compute.restype = C.c_int
-    lib.lsr_filter3d_compute.argtypes = [I64, P, I32, P, I32, C.c_float, C.c_float, I32, P, P, P, P]
-    lib.lsr_scene_activate_filtered_forward.restype = C.c_int
-    lib.lsr_scene_activate_filtered_forward.argtypes = [C.POINTER(SceneDims), C.POINTER(SceneParams), P, C.POINTER(SceneOutputs), P]
-    lib.lsr_scene_activate_filtered_backward.restype = C.c_int
-    lib.lsr_scene_activate_filtered_backward.argtypes = [C.POINTER(SceneDims), C.POINTER(SceneParams), P, C.POINTER(SceneOutGrads),
-                                                         C.POINTER(SceneInGrads), P]
-    lib.lsr_bilagrid_slice_path.restype = C.c_int
-    lib.lsr_bilagrid_slice_path.argtypes = [C.POINTER(BilagridDims)]
-    lib.lsr_bilagrid_slice_forward.restype = C.c_int
-    lib.lsr_bilagrid_slice_forward.argtypes = [C.POINTER(BilagridDims), P, P, P, P, P]
-    lib.lsr_bilagrid_slice_backward.restype = C.c_int
-    lib.lsr_bilagrid_slice_backward.argtypes = [C.POINTER(BilagridDims), P, P, P, P, P, P, P]
-    lib.lsr_bilagrid_tv_workspace_bytes.restype = SZ
-    lib.lsr_bilagrid_tv_workspace_bytes.argtypes = [C.POINTER(BilagridDims)]
-    lib.lsr_bilagrid_tv_forward.restype = C.c_int
-    lib.lsr_bilagrid_tv_forward.argtypes = [C.POINTER(BilagridDims), P, P, P, P]
-    lib.lsr_bilagrid_tv_backward.restype = C.c_int
-    lib.lsr_bilagrid_tv_backward.argtypes = [C.POINTER(BilagridDims), P, P, P, P]
-    lib.lsr_transform_records.restype = C.c_int
-    lib.lsr_transform_records.argtypes = [I32, P, I32, I32, P, P]
-    lib.lsr_scene_transform.restype = C.c_int
-    lib.lsr_scene_transform.argtypes = [C.POINTER(TransformDims), P, P, C.POINTER(TransformIn), C.POINTER(TransformOut), P]
-    lib.lsr_pose_matrices.restype = C.c_int
-    lib.lsr_pose_matrices.argtypes = [I32, P, P, P, P, P]
-    lib.lsr_pose_grad_workspace_bytes.restype = SZ
-    lib.lsr_pose_grad_workspace_bytes.argtypes = [I64, I32, I32]
-    lib.lsr_scene_pose_grad.restype = C.c_int
-    lib.lsr_scene_pose_grad.argtypes = [C.POINTER(TransformDims), P, P, P, C.POINTER(PoseGradIn), P, SZ, P, P, P, P]
-    lib.lsr_vq_workspace_bytes.restype = SZ
-    lib.lsr_vq_workspace_bytes.argtypes = [I64, I32, I32]
-    lib.lsr_vq_assign.restype = C.c_int
-    lib.lsr_vq_assign.argtypes = [C.POINTER(VqDims), P, P, P, P, P, P]
-    lib.lsr_vq_update.restype = C.c_int
-    lib.lsr_vq_update.argtypes = [C.POINTER(VqDims), P, P, P, P, P, P, P, P]
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype = restype
+        if argtypes is not None:
+            fn.argtypes = argtypes
     _lib = lib
     return lib
 
 
 def set_knob(name: str, value: int) -> None:
     """Override one LSR_* development knob of the library for the rest of the process (A/B experiments only)."""
-    check(load().lsr_debug_set_knob(name.encode(), int(value)), "lsr_debug_set_knob")
+    call("lsr_debug_set_knob", name.encode(), int(value))
 
 
 def profile_enable(on, only: tuple = ()) -> None:
@@ -533,8 +441,13 @@ def profile_read() -> dict:
     lib = load()
     n = lib.lsr_profile_num_stages()
     ms, cnt = (C.c_double * n)(), (C.c_int64 * n)()
-    check(lib.lsr_profile_read(ms, cnt), "lsr_profile_read")
+    call("lsr_profile_read", ms, cnt)
     return {lib.lsr_profile_stage_name(i).decode(): (ms[i], cnt[i]) for i in range(n)}
+
+
+def call(name: str, *args) -> None:
+    """``lib.<name>(*args)``, and :class:`LsrError` with that name unless it returns LSR_OK."""
+    check(getattr(load(), name)(*args), name)
 
 
 def check(rc: int, what: str):

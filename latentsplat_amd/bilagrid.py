@@ -24,11 +24,8 @@ import ctypes as C
 import torch
 from torch import Tensor, nn
 
-from . import _lib
-
-
-def _ptr(t: Tensor) -> C.c_void_p:
-    return C.c_void_p(t.data_ptr())
+from . import _args, _lib
+from ._args import ptr
 
 
 def _check_grids(what: str, grids: Tensor) -> None:
@@ -70,11 +67,9 @@ def slice_forward(grids: Tensor, image: Tensor, grid_idx: Tensor) -> Tensor:
     _check_slice(grids, image, grid_idx)
     g, x, idx = grids.detach().contiguous(), image.detach().contiguous(), grid_idx.contiguous()
     out = torch.empty_like(x)
-    lib = _lib.load()
     with torch.cuda.device(x.device):
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        _lib.check(lib.lsr_bilagrid_slice_forward(C.byref(_dims(g, x.shape)), _ptr(g), _ptr(x), _ptr(idx), _ptr(out), stream),
-                   "lsr_bilagrid_slice_forward")
+        stream = _args.stream(x)
+        _lib.call("lsr_bilagrid_slice_forward", C.byref(_dims(g, x.shape)), ptr(g), ptr(x), ptr(idx), ptr(out), stream)
     return out
 
 
@@ -97,11 +92,9 @@ def slice_backward(grids: Tensor, image: Tensor, grid_idx: Tensor, grad_out: Ten
           or not grad_grids.is_contiguous()):
         raise _lib.LsrError("grad_grids must be a contiguous float32 tensor of the grids' shape on their device")
     grad_image = torch.empty_like(x)
-    lib = _lib.load()
     with torch.cuda.device(x.device):
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        _lib.check(lib.lsr_bilagrid_slice_backward(C.byref(_dims(g, x.shape)), _ptr(g), _ptr(x), _ptr(idx), _ptr(up), _ptr(grad_image),
-                                                   _ptr(grad_grids) if want_grids else None, stream), "lsr_bilagrid_slice_backward")
+        _lib.call("lsr_bilagrid_slice_backward", C.byref(_dims(g, x.shape)), ptr(g), ptr(x), ptr(idx), ptr(up),
+                  ptr(grad_image), ptr(grad_grids) if want_grids else None, _args.stream(x))
     return grad_image, grad_grids
 
 
@@ -112,10 +105,9 @@ def tv_forward(grids: Tensor) -> Tensor:
     lib = _lib.load()
     dims = _dims(g)
     tv = torch.empty(1, dtype=torch.float32, device=g.device)
-    workspace = torch.empty(max(lib.lsr_bilagrid_tv_workspace_bytes(C.byref(dims)), 16), dtype=torch.uint8, device=g.device)
+    workspace = _args.workspace(max(lib.lsr_bilagrid_tv_workspace_bytes(C.byref(dims)), 16), g.device)
     with torch.cuda.device(g.device):
-        stream = C.c_void_p(torch.cuda.current_stream(g.device).cuda_stream)
-        _lib.check(lib.lsr_bilagrid_tv_forward(C.byref(dims), _ptr(g), _ptr(workspace), _ptr(tv), stream), "lsr_bilagrid_tv_forward")
+        _lib.call("lsr_bilagrid_tv_forward", C.byref(dims), ptr(g), ptr(workspace), ptr(tv), _args.stream(g))
     return tv
 
 
@@ -127,10 +119,8 @@ def tv_backward(grids: Tensor, grad_tv: Tensor) -> Tensor:
         raise _lib.LsrError("grad_tv must be a float32 tensor of one element on the grids' device")
     g, up = grids.detach().contiguous(), grad_tv.detach().contiguous()
     grad = torch.empty_like(g)
-    lib = _lib.load()
     with torch.cuda.device(g.device):
-        stream = C.c_void_p(torch.cuda.current_stream(g.device).cuda_stream)
-        _lib.check(lib.lsr_bilagrid_tv_backward(C.byref(_dims(g)), _ptr(g), _ptr(up), _ptr(grad), stream), "lsr_bilagrid_tv_backward")
+        _lib.call("lsr_bilagrid_tv_backward", C.byref(_dims(g)), ptr(g), ptr(up), ptr(grad), _args.stream(g))
     return grad
 
 

@@ -255,9 +255,7 @@ int lsr_adapter_forward(const lsr_adapter_dims *d, const lsr_adapter_inputs *in,
     if (d->cov_elems == 9) hipLaunchKernelGGL(k_adapter_fwd<9>, grid, dim3(kAdapterThreads), 0, s, *d, *in, *out);
     else hipLaunchKernelGGL(k_adapter_fwd<6>, grid, dim3(kAdapterThreads), 0, s, *d, *in, *out);
     prof_end(kStAdapterFwd, s);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    return launch_status();
 }
 
 int lsr_adapter_backward(const lsr_adapter_dims *d, const lsr_adapter_inputs *in,
@@ -275,9 +273,7 @@ int lsr_adapter_backward(const lsr_adapter_dims *d, const lsr_adapter_inputs *in
     if (d->cov_elems == 9) hipLaunchKernelGGL(k_adapter_bwd<9>, grid, dim3(kAdapterThreads), 0, s, *d, *in, *dout, *din);
     else hipLaunchKernelGGL(k_adapter_bwd<6>, grid, dim3(kAdapterThreads), 0, s, *d, *in, *dout, *din);
     prof_end(kStAdapterBwd, s);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    return launch_status();
 }
 
 }  // extern "C"

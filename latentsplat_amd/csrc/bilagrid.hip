@@ -512,9 +512,7 @@ int lsr_bilagrid_slice_forward(const lsr_bilagrid_dims *dims, const float *grids
     if (path == 32) hipLaunchKernelGGL((k_bg_slice_fwd<32, true>), blocks, dim3(kBgThreads), lds, st, a);
     else if (path == 16) hipLaunchKernelGGL((k_bg_slice_fwd<16, true>), blocks, dim3(kBgThreads), lds, st, a);
     else hipLaunchKernelGGL((k_bg_slice_fwd<kBgDirectTile, false>), blocks, dim3(kBgThreads), 0, st, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    return launch_status();
 }
 
 int lsr_bilagrid_slice_backward(const lsr_bilagrid_dims *dims, const float *grids, const float *image, const int32_t *grid_idx,
@@ -536,9 +534,7 @@ int lsr_bilagrid_slice_backward(const lsr_bilagrid_dims *dims, const float *grid
     if (path == 32) hipLaunchKernelGGL((k_bg_slice_bwd<32, true>), blocks, dim3(kBgThreads), lds, st, a);
     else if (path == 16) hipLaunchKernelGGL((k_bg_slice_bwd<16, true>), blocks, dim3(kBgThreads), lds, st, a);
     else hipLaunchKernelGGL((k_bg_slice_bwd<kBgDirectTile, false>), blocks, dim3(kBgThreads), 0, st, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    return launch_status();
 }
 
 size_t lsr_bilagrid_tv_workspace_bytes(const lsr_bilagrid_dims *dims) {
@@ -558,9 +554,7 @@ int lsr_bilagrid_tv_forward(const lsr_bilagrid_dims *dims, const float *grids, v
     hipLaunchKernelGGL(k_bg_tv_fwd, dim3(blocks), dim3(kBgThreads), 0, st, s, grids, (double *)workspace);
     hipLaunchKernelGGL(k_bg_tv_finish, dim3(1), dim3(kBgThreads), 0, st, (const double *)workspace, blocks,
                        tv_inv_count(*dims, dims->grid_x), tv_inv_count(*dims, dims->grid_y), tv_inv_count(*dims, dims->grid_l), tv);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    return launch_status();
 }
 
 int lsr_bilagrid_tv_backward(const lsr_bilagrid_dims *dims, const float *grids, const float *grad_tv, float *grad_grids,
@@ -573,9 +567,7 @@ int lsr_bilagrid_tv_backward(const lsr_bilagrid_dims *dims, const float *grids, 
     hipLaunchKernelGGL(k_bg_tv_bwd, dim3(tv_blocks(s.total)), dim3(kBgThreads), 0, (hipStream_t)stream, s, grids, grad_tv,
                        (float)(2.0 * tv_inv_count(*dims, dims->grid_x)), (float)(2.0 * tv_inv_count(*dims, dims->grid_y)),
                        (float)(2.0 * tv_inv_count(*dims, dims->grid_l)), grad_grids);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    return launch_status();
 }
 
 }  // extern "C"

@@ -242,9 +242,7 @@ int lsr_density_accumulate(int32_t V, int64_t n, const float *grad_means2D, cons
     const unsigned blocks = (unsigned)std::min<int64_t>((n + kDensityThreads - 1) / kDensityThreads, kDensityMaxBlocks);
     hipLaunchKernelGGL(k_density_accumulate, dim3(blocks), dim3(kDensityThreads), 0, (hipStream_t)stream, (int)V, n,
                        grad_means2D, radii, grad_accum, denom, max_radii);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    return launch_status();
 }
 
 size_t lsr_densify_workspace_bytes(int64_t n) {
@@ -273,9 +271,7 @@ int lsr_densify_plan(int64_t n, const float *opacity, const float *scaling, cons
                        denom, max_radii, p, ws);
     hipLaunchKernelGGL(k_densify_scan, dim3(1), dim3(kPlanScanThreads), 0, s, chunks, (int)p.n_split, ws.sums, counts);
     hipLaunchKernelGGL(k_densify_emit, dim3((unsigned)chunks), dim3(kPlanChunk), 0, s, n, (int)p.n_split, ws, counts, map);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    return launch_status();
 }
 
 int lsr_densify_apply(int64_t n, int64_t n_out, const uint32_t *map, const uint32_t *counts, int32_t n_split,
@@ -312,9 +308,7 @@ int lsr_densify_apply(int64_t n, int64_t n_out, const uint32_t *map, const uint3
     a.num_tables = num_tables; a.n_split = n_split; a.n = n; a.n_out = n_out; a.eps_rows = eps ? eps_rows : 0;
     a.map = map; a.counts = counts; a.scaling = scaling; a.rotation = rotation; a.eps = eps;
     hipLaunchKernelGGL(k_densify_apply, dim3((unsigned)blocks), dim3(kApplyThreads), 0, (hipStream_t)stream, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    return launch_status();
 }
 
 }  // extern "C"

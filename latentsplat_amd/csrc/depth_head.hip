@@ -279,9 +279,7 @@ int lsr_depth_head_forward(const lsr_depth_head_dims *d, const float *logits, co
         const unsigned blocks = (unsigned)((a.groups + kDhThreads / 64 - 1) / (kDhThreads / 64));
         hipLaunchKernelGGL(k_depth_head_fwd<64>, dim3(blocks), dim3(kDhThreads), 0, s, a, logits, near, far, uniforms, depth, opacity, index);
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    return launch_status();
 }
 
 int lsr_depth_head_backward(const lsr_depth_head_dims *d, const float *logits, const float *near, const float *far,
@@ -304,9 +302,7 @@ int lsr_depth_head_backward(const lsr_depth_head_dims *d, const float *logits, c
         const unsigned blocks = (unsigned)((a.groups + kDhThreads / 64 - 1) / (kDhThreads / 64));
         hipLaunchKernelGGL(k_depth_head_bwd<64>, dim3(blocks), dim3(kDhThreads), 0, s, a, logits, near, far, index, g_depth, g_opacity, d_logits);
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    return launch_status();
 }
 
 }  // extern "C"

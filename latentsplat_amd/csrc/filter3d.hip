@@ -185,9 +185,7 @@ int lsr_filter3d_compute(int64_t n, const float *xyz, int32_t num_views, const f
     hipLaunchKernelGGL(k_filter3d_pass, dim3(pass_blocks), dim3(kFilterThreads), 0, s, (int)n, xyz, (int)num_views, (const FilterCam *)cams,
                        (const FilterHeader *)header, &header->max_bits, filter, seen);
     hipLaunchKernelGGL(k_filter3d_unseen, dim3(blocks), dim3(kFilterThreads), 0, s, (int)n, (const FilterHeader *)header, filter);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    return launch_status();
 }
 
 }  // extern "C"

@@ -390,9 +390,7 @@ int lsr_knn3(int64_t n, const float *points, float *mean_dist2, float *dist2, in
     hipLaunchKernelGGL(k_knn_group_boxes, dim3((unsigned)groups), dim3(kGroup), 0, s, chunks, chunk_boxes, group_boxes);
     hipLaunchKernelGGL(k_knn_search, dim3((unsigned)((n + kQueries - 1) / kQueries)), dim3(kQueries), 0, s, n, chunks, groups, sorted, chunk_boxes,
                        group_boxes, mean_dist2, dist2, index);
-    e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    return launch_status();
 }
 
 }  // extern "C"

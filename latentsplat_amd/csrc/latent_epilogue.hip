@@ -297,9 +297,7 @@ int lsr_latent_forward(const lsr_latent_dims *d, const lsr_latent_inputs *in,
     prof_begin(kStLatentFwd, s);
     hipLaunchKernelGGL(k_latent_fwd, grid, dim3(kLatentThreads), sizeof(float) * kLatentThreads * kLatentMaxCols, s, dd, *in, *out);
     prof_end(kStLatentFwd, s);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    return launch_status();
 }
 
 int lsr_latent_backward(const lsr_latent_dims *d, const lsr_latent_inputs *in,
@@ -315,9 +313,7 @@ int lsr_latent_backward(const lsr_latent_dims *d, const lsr_latent_inputs *in,
     prof_begin(kStLatentBwd, s);
     hipLaunchKernelGGL(k_latent_bwd, grid, dim3(kLatentThreads), 0, s, *d, *in, *dout, d_features);
     prof_end(kStLatentBwd, s);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    return launch_status();
 }
 
 }  // extern "C"

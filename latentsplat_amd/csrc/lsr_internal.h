@@ -252,6 +252,12 @@ enum Stage { kStPreprocess = 0, kStTileScan, kStScatter, kStSort, kStRenderFwd, 
 void prof_begin(int stage, hipStream_t s);
 void prof_end(int stage, hipStream_t s);
 void note_hip_error(int hip_error);   // what lsr_last_hip_error() returns for this thread
+// how an entry point ends after its last launch: LSR_OK, or LSR_ELAUNCH with the HIP error noted for the caller's thread
+inline int launch_status() {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
+    return LSR_OK;
+}
 
 // Workspace clears are kernels, not hipMemsetAsync: captured memset nodes were observed not to clear on
 // back-to-back hipGraph replays (ROCm 7.2), which the latency mode relies on.

@@ -359,9 +359,7 @@ __global__ __launch_bounds__(kMcmcThreads) void k_mcmc_noise(int64_t n, float *_
 }
 
 static int launched() {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    return launch_status();
 }
 
 }  // namespace lsr

@@ -178,9 +178,7 @@ int lsr_adam_step(const lsr_adam_table *tables, int32_t num_tables, const uint8_
     a.visible = visible;
     a.num_tables = used;
     hipLaunchKernelGGL(k_adam_step, dim3((unsigned)blocks), dim3(kAdamThreads), 0, (hipStream_t)stream, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    return launch_status();
 }
 
 }  // extern "C"

@@ -345,9 +345,7 @@ int lsr_photometric_forward(const lsr_photometric_dims *dims, const float *image
                            dims->channels * shape.tiles_x * shape.tiles_y, 1.0 / (cropped * dims->channels),
                            1.0 / ((double)pixels * dims->channels), dims->lambda_dssim, loss, l1, ssim);
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    return launch_status();
 }
 
 int lsr_photometric_backward(const lsr_photometric_dims *dims, const float *image, const float *target, const float *saved,
@@ -359,9 +357,7 @@ int lsr_photometric_backward(const lsr_photometric_dims *dims, const float *imag
     const int64_t n = (int64_t)dims->num_images * dims->channels * dims->height * dims->width;
     PhotoBwdArgs a{photo_shape(*dims), dims->lambda_dssim, (float)(1.0 / (double)n), photo_shift(*dims), image, target, saved, grad_loss, grad_image, n};
     hipLaunchKernelGGL(k_photo_bwd, dim3((unsigned)photo_tiles(*dims)), dim3(kPhThreads), 0, (hipStream_t)stream, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    return launch_status();
 }
 
 }  // extern "C"

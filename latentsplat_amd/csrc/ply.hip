@@ -10,6 +10,7 @@
 #include "lsr_eig3.h"
 #include "lsr_internal.h"
 #include "lsr_ply.h"
+#include "lsr_sh_shape.h"
 #define LSR_SH_AXES_TABLE_QUALIFIER __device__
 #include "lsr_sh_axes_table.h"
 
@@ -212,7 +213,6 @@ static void launch_ply_unpack(const lsr_ply_layout &L, int rpb, int threads, siz
 // No atomics; one owner per row.
 constexpr int kPlyPackRows = 128;                    // 128 * (89 + 9) floats = 49 KiB at degree 4
 
-constexpr int sh_degree_of(int K) { return K == 1 ? 0 : K == 4 ? 1 : K == 9 ? 2 : K == 16 ? 3 : 4; }
 constexpr int sh_axes_table_floats(int deg) { return (deg + 1) * (2 * deg + 1) * (2 * deg + 3) / 3; }
 
 // f[0 .. 2L] <- M_L f, M row-major in LDS
@@ -373,9 +373,7 @@ int lsr_ply_pack(int64_t n, int32_t d_sh, const lsr_ply_inputs *in, float *verti
         return LSR_ENULL;
     if ((n + 255) / 256 > 0x7fffffffLL) return LSR_EUNSUPPORTED;
     hipLaunchKernelGGL(k_ply_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, d_sh, *in, vertices);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    return launch_status();
 }
 
 int lsr_ply_unpack(const lsr_ply_layout *layout, const float *rows, int32_t flags, const lsr_ply_outputs *out,
@@ -385,7 +383,7 @@ int lsr_ply_unpack(const lsr_ply_layout *layout, const float *rows, int32_t flag
     const lsr_ply_layout &L = *layout;
     const int K = L.sh_coeffs;
     if (L.n < 0 || L.stride < 1 || L.stride > LSR_PLY_MAX_STRIDE || (flags & ~LSR_PLY_OPACITY_RAW)) return LSR_EINVAL;
-    if (K != 1 && K != 4 && K != 9 && K != 16 && K != 25) return LSR_EINVAL;
+    if (!sh_valid_coeffs(K)) return LSR_EINVAL;
     // every offset the kernel may read lies inside the row (and with it inside the workgroup's LDS block)
     const auto inside = [&](const int32_t *o, int count) {
         for (int k = 0; k < count; ++k)
@@ -408,25 +406,16 @@ int lsr_ply_unpack(const lsr_ply_layout *layout, const float *rows, int32_t flag
     const size_t lds = 16 + (size_t)rpb * per_row;
     if ((L.n + rpb - 1) / rpb > 0x7fffffffLL) return LSR_EUNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
-    switch (K) {
-        case 1: launch_ply_unpack<1>(L, rpb, threads, lds, flags, rows, *out, s); break;
-        case 4: launch_ply_unpack<4>(L, rpb, threads, lds, flags, rows, *out, s); break;
-        case 9: launch_ply_unpack<9>(L, rpb, threads, lds, flags, rows, *out, s); break;
-        case 16: launch_ply_unpack<16>(L, rpb, threads, lds, flags, rows, *out, s); break;
-        default: launch_ply_unpack<25>(L, rpb, threads, lds, flags, rows, *out, s); break;
-    }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    dispatch_sh_coeffs(K, [&](auto k) { launch_ply_unpack<decltype(k)::value>(L, rpb, threads, lds, flags, rows, *out, s); });
+    return launch_status();
 }
 
 int lsr_ply_pack_scene(int64_t n, const lsr_ply_scene_inputs *in, const lsr_ply_scene_opts *opts, float *rows,
                        lsr_stream_t stream) {
     note_hip_error(0);
     if (!in || !opts) return LSR_ENULL;
-    const auto is_K = [](int K) { return K == 1 || K == 4 || K == 9 || K == 16 || K == 25; };
     const int K = opts->sh_coeffs_out;
-    if (n < 0 || !is_K(in->sh_coeffs) || !is_K(K) || K > in->sh_coeffs) return LSR_EINVAL;
+    if (n < 0 || !sh_valid_coeffs(in->sh_coeffs) || !sh_valid_coeffs(K) || K > in->sh_coeffs) return LSR_EINVAL;
     if (opts->sh_convention != LSR_SH_AXES_3DGS && opts->sh_convention != LSR_SH_AXES_REFERENCE) return LSR_EINVAL;
     if ((in->sh_channel_major & ~1) || in->reserved0 || opts->reserved0 || opts->reserved1) return LSR_EINVAL;
     if (in->cov && in->cov_elems != 6 && in->cov_elems != 9) return LSR_EINVAL;
@@ -441,16 +430,8 @@ int lsr_ply_pack_scene(int64_t n, const lsr_ply_scene_inputs *in, const lsr_ply_
     if ((n + kPlyPackRows - 1) / kPlyPackRows > 0x7fffffffLL) return LSR_EUNSUPPORTED;
     const int reference = opts->sh_convention == LSR_SH_AXES_REFERENCE;
     hipStream_t s = (hipStream_t)stream;
-    switch (K) {
-        case 1: launch_ply_pack_scene<1>(n, reference, *in, rows, s); break;
-        case 4: launch_ply_pack_scene<4>(n, reference, *in, rows, s); break;
-        case 9: launch_ply_pack_scene<9>(n, reference, *in, rows, s); break;
-        case 16: launch_ply_pack_scene<16>(n, reference, *in, rows, s); break;
-        default: launch_ply_pack_scene<25>(n, reference, *in, rows, s); break;
-    }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    dispatch_sh_coeffs(K, [&](auto k) { launch_ply_pack_scene<decltype(k)::value>(n, reference, *in, rows, s); });
+    return launch_status();
 }
 
 int lsr_ply_write_host(const char *path, const float *vertices_host, int64_t n) {

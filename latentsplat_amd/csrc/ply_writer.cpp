@@ -6,6 +6,7 @@
 
 #include "lsr_ply.h"
 #include "lsr_sh_axes_table.h"
+#include "lsr_sh_shape.h"
 
 extern "C" {
 
@@ -25,7 +26,7 @@ int lsr_ply_sh_axes_matrix(double *out) {
 int lsr_ply_write_scene_host(const char *path, const float *rows_host, int64_t n, int32_t sh_coeffs) {
     if (!path || (n > 0 && !rows_host)) return LSR_ENULL;
     const int K = sh_coeffs;
-    if (n < 0 || (K != 1 && K != 4 && K != 9 && K != 16 && K != 25)) return LSR_EINVAL;
+    if (n < 0 || !lsr::sh_valid_coeffs(K)) return LSR_EINVAL;
     FILE *f = fopen(path, "wb");
     if (!f) return LSR_EINVAL;
     bool ok = fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %lld\n", (long long)n) > 0;

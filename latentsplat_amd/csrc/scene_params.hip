@@ -26,6 +26,7 @@
 #include <algorithm>
 
 #include "lsr_internal.h"
+#include "lsr_sh_shape.h"
 #include "lsr_scene.h"
 
 namespace lsr {
@@ -285,7 +286,7 @@ __global__ __launch_bounds__(kSceneChunk) void k_scene_bwd(int64_t n, float m, l
 static int scene_check(const lsr_scene_dims *dims, const lsr_scene_params *p) {
     if (!dims || !p) return LSR_ENULL;
     const int K = dims->sh_coeffs;
-    if (dims->n < 0 || (K != 1 && K != 4 && K != 9 && K != 16 && K != 25)) return LSR_EINVAL;
+    if (dims->n < 0 || !sh_valid_coeffs(K)) return LSR_EINVAL;
     if ((K == 1) != (p->features_rest == nullptr)) return LSR_EINVAL;
     if (!std::isfinite(dims->scale_modifier) || !(dims->scale_modifier > 0.0f)) return LSR_EINVAL;
     if (dims->reserved0 || dims->reserved1) return LSR_EINVAL;
@@ -297,34 +298,24 @@ static unsigned scene_blocks(int64_t n) {
 }
 
 // filter3d NULL: the unfiltered instantiation
-#define SCENE_LAUNCH(kernel, K, ...)                                                                              \
-    do {                                                                                                          \
-        if (filter3d) hipLaunchKernelGGL((kernel<K, true>), grid, block, 0, s, __VA_ARGS__, filter3d);            \
-        else hipLaunchKernelGGL((kernel<K, false>), grid, block, 0, s, __VA_ARGS__, (const float *)nullptr);      \
-    } while (0)
-
 static void launch_scene_fwd(const lsr_scene_dims &d, const lsr_scene_params &p, const lsr_scene_outputs &o, const float *filter3d,
                              hipStream_t s) {
     const dim3 grid(scene_blocks(d.n)), block(kSceneChunk);
-    switch (d.sh_coeffs) {
-        case 1: SCENE_LAUNCH(k_scene_fwd, 1, d.n, d.scale_modifier, p, o); break;
-        case 4: SCENE_LAUNCH(k_scene_fwd, 4, d.n, d.scale_modifier, p, o); break;
-        case 9: SCENE_LAUNCH(k_scene_fwd, 9, d.n, d.scale_modifier, p, o); break;
-        case 16: SCENE_LAUNCH(k_scene_fwd, 16, d.n, d.scale_modifier, p, o); break;
-        default: SCENE_LAUNCH(k_scene_fwd, 25, d.n, d.scale_modifier, p, o); break;
-    }
+    dispatch_sh_coeffs(d.sh_coeffs, [&](auto k) {
+        constexpr int K = decltype(k)::value;
+        if (filter3d) hipLaunchKernelGGL((k_scene_fwd<K, true>), grid, block, 0, s, d.n, d.scale_modifier, p, o, filter3d);
+        else hipLaunchKernelGGL((k_scene_fwd<K, false>), grid, block, 0, s, d.n, d.scale_modifier, p, o, (const float *)nullptr);
+    });
 }
 
 static void launch_scene_bwd(const lsr_scene_dims &d, const lsr_scene_params &p, const lsr_scene_out_grads &g,
                              const lsr_scene_in_grads &o, const float *filter3d, hipStream_t s) {
     const dim3 grid(scene_blocks(d.n)), block(kSceneChunk);
-    switch (d.sh_coeffs) {
-        case 1: SCENE_LAUNCH(k_scene_bwd, 1, d.n, d.scale_modifier, p, g, o); break;
-        case 4: SCENE_LAUNCH(k_scene_bwd, 4, d.n, d.scale_modifier, p, g, o); break;
-        case 9: SCENE_LAUNCH(k_scene_bwd, 9, d.n, d.scale_modifier, p, g, o); break;
-        case 16: SCENE_LAUNCH(k_scene_bwd, 16, d.n, d.scale_modifier, p, g, o); break;
-        default: SCENE_LAUNCH(k_scene_bwd, 25, d.n, d.scale_modifier, p, g, o); break;
-    }
+    dispatch_sh_coeffs(d.sh_coeffs, [&](auto k) {
+        constexpr int K = decltype(k)::value;
+        if (filter3d) hipLaunchKernelGGL((k_scene_bwd<K, true>), grid, block, 0, s, d.n, d.scale_modifier, p, g, o, filter3d);
+        else hipLaunchKernelGGL((k_scene_bwd<K, false>), grid, block, 0, s, d.n, d.scale_modifier, p, g, o, (const float *)nullptr);
+    });
 }
 
 }  // namespace lsr
@@ -342,9 +333,7 @@ static int scene_forward(const lsr_scene_dims *dims, const lsr_scene_params *par
     if ((reinterpret_cast<uintptr_t>(params->rotation) | reinterpret_cast<uintptr_t>(out->rotations)) & 15) return LSR_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     launch_scene_fwd(*dims, *params, *out, filtered ? filter3d : nullptr, s);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    return launch_status();
 }
 
 static int scene_backward(const lsr_scene_dims *dims, const lsr_scene_params *params, const float *filter3d, bool filtered,
@@ -358,9 +347,7 @@ static int scene_backward(const lsr_scene_dims *dims, const lsr_scene_params *pa
     if ((reinterpret_cast<uintptr_t>(params->rotation) | reinterpret_cast<uintptr_t>(din->rotation)) & 15) return LSR_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     launch_scene_bwd(*dims, *params, *dout, *din, filtered ? filter3d : nullptr, s);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    return launch_status();
 }
 
 extern "C" {

@@ -31,6 +31,7 @@
 #include <algorithm>
 
 #include "lsr_internal.h"
+#include "lsr_sh_shape.h"
 #include "lsr_pose.h"
 #include "lsr_sh_generator_table.h"
 
@@ -43,10 +44,7 @@ constexpr int kPgTrips = 4;               // ids of a wave reduced by a wave sum
 constexpr int kPgFinishPhases = 32;       // lanes per (transform, component) of k_pose_grad_finish
 
 __host__ __device__ constexpr int pg_chunk(int K) { return K >= 16 ? 64 : 128; }     // Gaussians per chunk = lanes per workgroup
-__host__ __device__ constexpr int pg_degree(int K) { return (K > 16) + (K > 9) + (K > 4) + (K > 1); }
-__host__ __device__ constexpr int pg_row_floats(int K) { return 3 * (K - 1); }
-__host__ __device__ constexpr int pg_row_stride(int K) { return pg_row_floats(K) | 1; }  // odd: no bank conflicts
-__host__ __device__ constexpr int pg_rows_bytes(int K) { return K > 1 ? 2 * pg_chunk(K) * pg_row_stride(K) * 4 : 32; }
+__host__ __device__ constexpr int pg_rows_bytes(int K) { return K > 1 ? 2 * pg_chunk(K) * sh_rest_stride(K) * 4 : 32; }
 __host__ __device__ constexpr int pg_tables_bytes(int K, int T) { return pg_chunk(K) / 64 * T * 7 * 8; }
 static_assert(pg_rows_bytes(25) + pg_tables_bytes(25, LSR_POSE_MAX_TRANSFORMS) <= kPgLdsBytes, "LDS budget, K = 25");
 static_assert(pg_rows_bytes(16) + pg_tables_bytes(16, LSR_POSE_MAX_TRANSFORMS) <= kPgLdsBytes, "LDS budget, K = 16");
@@ -139,8 +137,8 @@ template <int K>
 __global__ __launch_bounds__(pg_chunk(K)) void k_scene_pose_grad(int64_t n, int T, const float *__restrict__ records,
                                                                  const int32_t *__restrict__ idx, lsr_pose_grad_in in,
                                                                  double *__restrict__ partial) {
-    constexpr int G = pg_chunk(K), W = pg_row_floats(K), WP = pg_row_stride(K), PAD = WP - W, WAVES = G / 64;
-    constexpr int RF = LSR_TRANSFORM_RECORD_FLOATS(pg_degree(K));
+    constexpr int G = pg_chunk(K), W = sh_rest_floats(K), WP = sh_rest_stride(K), PAD = WP - W, WAVES = G / 64;
+    constexpr int RF = LSR_TRANSFORM_RECORD_FLOATS(sh_degree_of(K));
     __shared__ float s_c[K > 1 ? G * WP : 4], s_g[K > 1 ? G * WP : 4];
     extern __shared__ double pg_tab[];                   // [WAVES][T][7]
     const int tid = threadIdx.x, lane = tid & 63;
@@ -316,8 +314,6 @@ static void pg_launch(const lsr_transform_dims &d, const float *records, const i
                        d.num_transforms, records, idx, in, partial);
 }
 
-static bool pg_valid_k(int K) { return K == 1 || K == 4 || K == 9 || K == 16 || K == 25; }
-
 }  // namespace lsr
 
 using namespace lsr;
@@ -332,13 +328,11 @@ int lsr_pose_matrices(int32_t T, const float *quaternions, const float *translat
     if (!quaternions || !translations || !matrices) return LSR_ENULL;
     hipLaunchKernelGGL(k_pose_matrices, dim3((unsigned)((T + 63) / 64)), dim3(64), 0, (hipStream_t)stream, (int)T, quaternions,
                        translations, log_scales, matrices);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    return launch_status();
 }
 
 size_t lsr_pose_grad_workspace_bytes(int64_t n, int32_t sh_coeffs, int32_t T) {
-    if (n < 0 || !pg_valid_k(sh_coeffs) || T < 0 || T > LSR_POSE_MAX_TRANSFORMS) return 0;
+    if (n < 0 || !sh_valid_coeffs(sh_coeffs) || T < 0 || T > LSR_POSE_MAX_TRANSFORMS) return 0;
     return (size_t)pg_blocks(n, sh_coeffs) * (size_t)T * 7 * sizeof(double);
 }
 
@@ -348,7 +342,7 @@ int lsr_scene_pose_grad(const lsr_transform_dims *dims, const float *records, co
     note_hip_error(0);
     if (!dims || !in) return LSR_ENULL;
     const int K = dims->sh_coeffs, T = dims->num_transforms;
-    if (dims->n < 0 || !pg_valid_k(K) || T < 0) return LSR_EINVAL;
+    if (dims->n < 0 || !sh_valid_coeffs(K) || T < 0) return LSR_EINVAL;
     if (dims->reserved0 || dims->reserved1) return LSR_EINVAL;
     if (K == 1 && (in->features_rest || in->g_features_rest)) return LSR_EINVAL;
     if ((reinterpret_cast<uintptr_t>(in->rotation) | reinterpret_cast<uintptr_t>(in->g_rotation)) & 15) return LSR_EINVAL;
@@ -363,20 +357,10 @@ int lsr_scene_pose_grad(const lsr_transform_dims *dims, const float *records, co
     }
     hipStream_t s = (hipStream_t)stream;
     double *partial = static_cast<double *>(workspace);
-    if (dims->n > 0) {
-        switch (K) {
-            case 1: pg_launch<1>(*dims, records, idx, *in, partial, s); break;
-            case 4: pg_launch<4>(*dims, records, idx, *in, partial, s); break;
-            case 9: pg_launch<9>(*dims, records, idx, *in, partial, s); break;
-            case 16: pg_launch<16>(*dims, records, idx, *in, partial, s); break;
-            default: pg_launch<25>(*dims, records, idx, *in, partial, s); break;
-        }
-    }
+    if (dims->n > 0) dispatch_sh_coeffs(K, [&](auto k) { pg_launch<decltype(k)::value>(*dims, records, idx, *in, partial, s); });
     hipLaunchKernelGGL(k_pose_grad_finish, dim3((unsigned)T), dim3(7 * kPgFinishPhases), 0, s, (int)T, (int)pg_blocks(dims->n, K), partial, quaternions, grad_quaternion, grad_translation,
                        grad_log_scale);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    return launch_status();
 }
 
 }  // extern "C"

@@ -26,6 +26,7 @@
 #include <algorithm>
 
 #include "lsr_internal.h"
+#include "lsr_sh_shape.h"
 #include "lsr_transform.h"
 #include "lsr_sh_rotate.h"
 #include "lsr_sh_rotate_basis.h"
@@ -42,12 +43,8 @@ constexpr int kXfRounds = 4;              // grid cap in rounds of resident work
 constexpr int kXfBatch = 16;              // dword loads in flight per lane
 enum { kXfUniform = 0, kXfStaged = 1, kXfGather = 2 };
 
-__host__ __device__ constexpr int xf_band_offset(int l) { return l * (4 * l * l - 1) / 3; }            // sum_{m<l} (2m+1)^2
-__host__ __device__ constexpr int xf_record_band(int l) { return LSR_TRANSFORM_HEADER_FLOATS + xf_band_offset(l) - 1; }
-__host__ __device__ constexpr int xf_degree(int K) { return (K > 16) + (K > 9) + (K > 4) + (K > 1); }
-__host__ __device__ constexpr int xf_row_floats(int K) { return 3 * (K - 1); }
-__host__ __device__ constexpr int xf_row_stride(int K) { return xf_row_floats(K) | 1; }                // odd: no bank conflicts
-__host__ __device__ constexpr int xf_rows_bytes(int K) { return K > 1 ? kXfChunk * xf_row_stride(K) * 4 : 16; }
+__host__ __device__ constexpr int xf_record_band(int l) { return LSR_TRANSFORM_HEADER_FLOATS + sh_band_offset(l) - 1; }
+__host__ __device__ constexpr int xf_rows_bytes(int K) { return K > 1 ? kXfChunk * sh_rest_stride(K) * 4 : 16; }
 
 // X <- (X + X^-T) / 2: one Newton step towards the orthogonal factor of X (X^-T = cofactors / det)
 __device__ static void xf_polar_step(double (&X)[9]) {
@@ -121,7 +118,7 @@ __global__ __launch_bounds__(64) void k_transform_records(int num, const float *
 
     int l = 0;
     while (l < LSR_TRANSFORM_MAX_DEGREE && (l + 1) * (l + 1) <= e) ++l;
-    const int idx = e - l * l, n = 2 * l + 1, off = xf_band_offset(l);
+    const int idx = e - l * l, n = 2 * l + 1, off = sh_band_offset(l);
     const bool active = e >= 1 && e < (degree + 1) * (degree + 1);
     if (active) {
         const double *x = kShRotDirs[l * l + idx];
@@ -186,8 +183,8 @@ template <int K, int MODE>
 __global__ __launch_bounds__(kXfChunk) void k_scene_transform(int64_t n, int T, const float *__restrict__ records,
                                                               const int32_t *__restrict__ idx, lsr_transform_in in,
                                                               lsr_transform_out out) {
-    constexpr int G = kXfChunk, W = xf_row_floats(K), WP = xf_row_stride(K), PAD = WP - W;
-    constexpr int RF = LSR_TRANSFORM_RECORD_FLOATS(xf_degree(K));
+    constexpr int G = kXfChunk, W = sh_rest_floats(K), WP = sh_rest_stride(K), PAD = WP - W;
+    constexpr int RF = LSR_TRANSFORM_RECORD_FLOATS(sh_degree_of(K));
     __shared__ float s_rows[K > 1 ? G * WP : 4];
     extern __shared__ float4 xf_dyn[];                   // kXfStaged: the T records
     float *s_rec = reinterpret_cast<float *>(xf_dyn);
@@ -304,7 +301,7 @@ __global__ __launch_bounds__(kXfChunk) void k_scene_transform(int64_t n, int T, 
 
 static int xf_mode(const lsr_transform_dims &d, const int32_t *idx) {
     if (!idx) return kXfUniform;
-    const int64_t bytes = (int64_t)d.num_transforms * LSR_TRANSFORM_RECORD_FLOATS(xf_degree(d.sh_coeffs)) * 4;
+    const int64_t bytes = (int64_t)d.num_transforms * LSR_TRANSFORM_RECORD_FLOATS(sh_degree_of(d.sh_coeffs)) * 4;
     return xf_rows_bytes(d.sh_coeffs) + bytes + 64 <= kXfLdsBytes ? kXfStaged : kXfGather;
 }
 
@@ -312,7 +309,7 @@ template <int K>
 static void xf_launch(const lsr_transform_dims &d, const float *records, const int32_t *idx, const lsr_transform_in &in,
                       const lsr_transform_out &out, hipStream_t s) {
     const int mode = xf_mode(d, idx);
-    const size_t dyn = mode == kXfStaged ? (size_t)d.num_transforms * LSR_TRANSFORM_RECORD_FLOATS(xf_degree(K)) * 4 : 0;
+    const size_t dyn = mode == kXfStaged ? (size_t)d.num_transforms * LSR_TRANSFORM_RECORD_FLOATS(sh_degree_of(K)) * 4 : 0;
     // as many workgroups as are resident (by LDS, at most 16 two-wave workgroups per CU) when each stages the records;
     // otherwise up to kXfRounds times as many, so that a scene of a few rounds is handed out chunk by chunk as workgroups
     // retire instead of two chunks to some workgroups and one to the others
@@ -338,9 +335,7 @@ int lsr_transform_records(int32_t T, const float *matrices, int32_t degree, int3
     if (!matrices || !records) return LSR_ENULL;
     hipLaunchKernelGGL(k_transform_records, dim3((unsigned)T), dim3(64), 0, (hipStream_t)stream, (int)T, matrices, (int)degree,
                        (int)adjoint, records);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    return launch_status();
 }
 
 int lsr_scene_transform(const lsr_transform_dims *dims, const float *records, const int32_t *idx,
@@ -348,7 +343,7 @@ int lsr_scene_transform(const lsr_transform_dims *dims, const float *records, co
     note_hip_error(0);
     if (!dims || !in || !out) return LSR_ENULL;
     const int K = dims->sh_coeffs;
-    if (dims->n < 0 || (K != 1 && K != 4 && K != 9 && K != 16 && K != 25) || dims->num_transforms < 1) return LSR_EINVAL;
+    if (dims->n < 0 || !sh_valid_coeffs(K) || dims->num_transforms < 1) return LSR_EINVAL;
     if (dims->reserved0 || dims->reserved1) return LSR_EINVAL;
     if (K == 1 && (in->features_rest || out->features_rest)) return LSR_EINVAL;
     if (K > 1 && out->features_rest && !in->features_rest) return LSR_EINVAL;
@@ -357,16 +352,8 @@ int lsr_scene_transform(const lsr_transform_dims *dims, const float *records, co
     if (!records || (out->xyz && !in->xyz) || (out->scaling && !in->scaling) || (out->rotation && !in->rotation)) return LSR_ENULL;
     if (!out->xyz && !out->features_rest && !out->scaling && !out->rotation) return LSR_OK;
     hipStream_t s = (hipStream_t)stream;
-    switch (K) {
-        case 1: xf_launch<1>(*dims, records, idx, *in, *out, s); break;
-        case 4: xf_launch<4>(*dims, records, idx, *in, *out, s); break;
-        case 9: xf_launch<9>(*dims, records, idx, *in, *out, s); break;
-        case 16: xf_launch<16>(*dims, records, idx, *in, *out, s); break;
-        default: xf_launch<25>(*dims, records, idx, *in, *out, s); break;
-    }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    dispatch_sh_coeffs(K, [&](auto k) { xf_launch<decltype(k)::value>(*dims, records, idx, *in, *out, s); });
+    return launch_status();
 }
 
 }  // extern "C"

@@ -16,6 +16,7 @@
 //   backward  the two gradient tiles -> LDS, sum over S, transposed mat-vec, mask, LDS image of the dense rows, copy out.
 // HBM traffic per row is the minimum: 4 W bytes in and 4 S W out (forward), the reverse (backward); W = 3 Kc + C Kf.
 #include "lsr_internal.h"
+#include "lsr_sh_shape.h"
 #include "lsr_sh_rotate.h"
 #include "lsr_sh_rotate_basis.h"
 #include "lsr_sh_rotate_tables.h"
@@ -26,8 +27,6 @@ constexpr int kShRotThreads = 256;
 constexpr int kShRotLdsFloats = 12288;    // staging budget of a workgroup: 48 KB, three workgroups per CU
 constexpr int kShRotLdsMaxFloats = 15360; // (with the tables: the 64 KB a workgroup gets without opting in to more)
 constexpr int kShRotLdsSlack = 16;        // alignment shifts of the (up to three) LDS images
-
-__host__ __device__ constexpr int sh_band_offset(int l) { return l * (4 * l * l - 1) / 3; }   // sum_{m<l} (2m+1)^2
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Rotation matrices.  Y_l(R x) = D_l(R) Y_l(x) for all x, so with n = 2l+1 fixed directions x_k and the constant
@@ -342,23 +341,14 @@ __global__ __launch_bounds__(kShRotThreads) void k_sh_rotate_bwd(lsr_sh_rotate_d
 
 using namespace lsr;
 
-static int sh_degree_of(int coeffs) {
-    switch (coeffs) {
-    case 1: return 0;
-    case 4: return 1;
-    case 9: return 2;
-    case 16: return 3;
-    case 25: return 4;
-    default: return -1;
-    }
-}
+static int sh_degree_or_none(int coeffs) { return sh_valid_coeffs(coeffs) ? sh_degree_of(coeffs) : -1; }
 
 // dims validation shared by both directions; fills in the tiling.  LSR_OK with tiles_per_cam == 0: nothing to launch.
 static int sh_rotate_check(const lsr_sh_rotate_dims *d, bool forward, ShRotTiling *tl) {
     if (!d) return LSR_ENULL;
     if (d->num_cameras < 1 || d->rays < 0 || d->samples < 1 || d->reserved0 != 0) return LSR_EINVAL;
-    const int lc = d->color_coeffs == 0 ? -1 : sh_degree_of(d->color_coeffs);
-    const int lf = d->feat_coeffs == 0 ? -1 : sh_degree_of(d->feat_coeffs);
+    const int lc = d->color_coeffs == 0 ? -1 : sh_degree_or_none(d->color_coeffs);
+    const int lf = d->feat_coeffs == 0 ? -1 : sh_degree_or_none(d->feat_coeffs);
     if ((d->color_coeffs != 0 && lc < 0) || (d->feat_coeffs != 0 && lf < 0) || (lc < 0 && lf < 0)) return LSR_EINVAL;
     if (lf >= 0 && (d->feat_channels < 1 || d->feat_channels > LSR_MAX_FEAT_CHANNELS)) return LSR_EINVAL;
     const int lmax = lc > lf ? lc : lf;
@@ -401,9 +391,7 @@ int lsr_sh_rotation_matrices(int32_t num_rot, const float *rotations, int64_t ro
     if (!rotations || !tables) return LSR_ENULL;
     hipLaunchKernelGGL(k_sh_rotation_matrices, dim3((unsigned)((num_rot + kShRotMatPerBlock - 1) / kShRotMatPerBlock)), dim3(64), 0, (hipStream_t)stream,
                        (int)num_rot, rotations, row_stride, mat_stride, (int)degree, tables);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    return launch_status();
 }
 
 int lsr_sh_rotate_forward(const lsr_sh_rotate_dims *d, const float *tables, const float *rows,
@@ -418,9 +406,7 @@ int lsr_sh_rotate_forward(const lsr_sh_rotate_dims *d, const float *tables, cons
     hipLaunchKernelGGL(k_sh_rotate_fwd, dim3((unsigned)(tl.tiles_per_cam * d->num_cameras)), dim3(kShRotThreads),
                        sh_rotate_lds_bytes(*d, tl), (hipStream_t)stream, *d, tl, tables, rows, color_mask, feature_mask,
                        color_out, feature_out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    return launch_status();
 }
 
 int lsr_sh_rotate_backward(const lsr_sh_rotate_dims *d, const float *tables, const float *g_color,
@@ -436,9 +422,7 @@ int lsr_sh_rotate_backward(const lsr_sh_rotate_dims *d, const float *tables, con
                        sh_rotate_lds_bytes(*d, tl), (hipStream_t)stream, *d, tl, tables,
                        d->color_coeffs > 0 ? g_color : nullptr, d->feat_coeffs > 0 ? g_feature : nullptr, color_mask,
                        feature_mask, d_rows);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    return launch_status();
 }
 
 }  // extern "C"

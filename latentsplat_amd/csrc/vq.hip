@@ -375,9 +375,7 @@ int lsr_vq_assign(const lsr_vq_dims *dims, const float *x, const float *codebook
     hipLaunchKernelGGL(k_vq_assign, dim3((unsigned)((n + kRows - 1) / kRows)), dim3(kVqThreads), lds, s, n, k_pad, d, x, packed, bias, idx_out);
     if (dist2_out)
         hipLaunchKernelGGL(k_vq_dist2, dim3((unsigned)((n + kVqThreads - 1) / kVqThreads)), dim3(kVqThreads), 0, s, n, k, d, x, codebook, idx_out, dist2_out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    return launch_status();
 }
 
 int lsr_vq_update(const lsr_vq_dims *dims, const float *x, const int32_t *idx, const float *weights,
@@ -411,9 +409,7 @@ int lsr_vq_update(const lsr_vq_dims *dims, const float *x, const int32_t *idx, c
     hipLaunchKernelGGL(k_vq_partial, dim3((unsigned)vq_blocks(n)), dim3(d <= 64 ? 64 : 128), 0, s, k, d, x, weights, keys_out, order, start,
                        prev_codebook, codebook_out, mass_out, partial);
     hipLaunchKernelGGL(k_vq_finish, dim3((unsigned)k), dim3(kVqThreads), 0, s, k, d, start, partial, prev_codebook, codebook_out, mass_out);
-    e = hipGetLastError();
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    return LSR_OK;
+    return launch_status();
 }
 
 }  // extern "C"

@@ -22,19 +22,12 @@ from typing import NamedTuple, Optional
 import torch
 from torch import Tensor
 
-from .. import _lib
+from .. import _args, _lib
+from .._args import ptr
 from .._lib import LatentDims, LatentInputs, LatentOutGrads, LatentOutputs
 from .decoder import DecoderOutput
 
 LOGVAR_FROM_MASK, LOGVAR_FROM_FEATURES = 0, 1
-
-
-def _ptr(t: Optional[Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream(t: Tensor):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 def _require(*tensors: Optional[Tensor]) -> None:
@@ -50,7 +43,6 @@ class _LatentEpilogue(torch.autograd.Function):
     @staticmethod
     def forward(ctx, features, mask, noise, color, out_size, logvar_mode, want_skip, want_logvar, interval):
         _require(features, mask, noise, color)
-        lib = _lib.load()
         features = features.contiguous()
         mask = None if mask is None else mask.contiguous()
         noise = None if noise is None else noise.contiguous()
@@ -65,10 +57,9 @@ class _LatentEpilogue(torch.autograd.Function):
         z = torch.empty((V, Cc, oh, ow), device=dev) if out_size is not None else None
         lv_ch = Cc if logvar_mode == LOGVAR_FROM_FEATURES else 1
         logvar = torch.empty((V, lv_ch, H, W), device=dev) if want_logvar else None
-        inp = LatentInputs(_ptr(features), _ptr(mask), _ptr(noise), _ptr(color))
-        out = LatentOutputs(_ptr(skip), _ptr(z), _ptr(logvar))
-        _lib.check(lib.lsr_latent_forward(C.byref(dims), C.byref(inp), C.byref(out), _stream(features)),
-                   "lsr_latent_forward")
+        inp = LatentInputs(ptr(features), ptr(mask), ptr(noise), ptr(color))
+        out = LatentOutputs(ptr(skip), ptr(z), ptr(logvar))
+        _lib.call("lsr_latent_forward", C.byref(dims), C.byref(inp), C.byref(out), _args.stream(features))
         ctx.save_for_backward(features, mask, noise)
         ctx.dims = dims
         ctx.set_materialize_grads(False)
@@ -79,16 +70,14 @@ class _LatentEpilogue(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_skip, g_z, _g_logvar):
         features, mask, noise = ctx.saved_tensors
-        lib = _lib.load()
         g_skip = None if g_skip is None else g_skip.contiguous()
         g_z = None if g_z is None else g_z.contiguous()
         d_features = torch.empty_like(features)
         if g_skip is None and g_z is None:
             return d_features.zero_(), None, None, None, None, None, None, None, None
-        inp = LatentInputs(_ptr(features), _ptr(mask), _ptr(noise), None)
-        dout = LatentOutGrads(_ptr(g_skip), _ptr(g_z))
-        _lib.check(lib.lsr_latent_backward(C.byref(ctx.dims), C.byref(inp), C.byref(dout), _ptr(d_features),
-                                           _stream(features)), "lsr_latent_backward")
+        inp = LatentInputs(ptr(features), ptr(mask), ptr(noise), None)
+        dout = LatentOutGrads(ptr(g_skip), ptr(g_z))
+        _lib.call("lsr_latent_backward", C.byref(ctx.dims), C.byref(inp), C.byref(dout), ptr(d_features), _args.stream(features))
         return d_features, None, None, None, None, None, None, None, None
 
 

@@ -13,12 +13,14 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+from functools import partial
 from typing import Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _args, _lib
+from ._args import ptr
 
 RULES = dict(copy=_lib.DENSIFY_COPY, zero_new=_lib.DENSIFY_ZERO_NEW, xyz=_lib.DENSIFY_XYZ, scaling=_lib.DENSIFY_SCALING)
 _FLT_MAX = 3.4028234663852886e38
@@ -26,22 +28,7 @@ _SCENE_PARAMS = ("_xyz", "_features_dc", "_features_rest", "_opacity", "_scaling
 _SCENE_RULES = dict(_xyz="xyz", _features_dc="copy", _features_rest="copy", _opacity="copy", _scaling="scaling", _rotation="copy")
 
 
-def _ptr(t: Optional[Tensor]) -> C.c_void_p:
-    return C.c_void_p(None if t is None or t.numel() == 0 else t.data_ptr())
-
-
-def _f32(name: str, t: Tensor, shape: Optional[tuple] = None, device=None) -> Tensor:
-    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32:
-        raise _lib.LsrError(f"density control needs float32 ROCm tensors (no CPU fallback): {name} is not one")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise _lib.LsrError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
-    if device is not None and t.device != device:
-        raise _lib.LsrError(f"{name} must be on {device}")
-    return t
-
-
-def _stream(dev) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+_f32 = partial(_args.f32, "density control")
 
 
 def accumulate_density_stats(means2D_grad: Tensor, radii: Tensor, grad_accum: Tensor, denom: Tensor, max_radii: Tensor) -> None:
@@ -65,8 +52,8 @@ def accumulate_density_stats(means2D_grad: Tensor, radii: Tensor, grad_accum: Te
         return
     g, radii = g.detach().contiguous(), radii.contiguous()
     with torch.cuda.device(dev):
-        _lib.check(_lib.load().lsr_density_accumulate(V, n, _ptr(g), _ptr(radii), _ptr(grad_accum), _ptr(denom), _ptr(max_radii),
-                                                      _stream(dev)), "lsr_density_accumulate")
+        _lib.call("lsr_density_accumulate", V, n, ptr(g), ptr(radii), ptr(grad_accum), ptr(denom), ptr(max_radii),
+                  _args.stream(dev))
 
 
 def plan_densify(opacity: Tensor, scaling: Tensor, grad_accum: Tensor, denom: Tensor, max_radii: Tensor, *,
@@ -94,11 +81,11 @@ def plan_densify(opacity: Tensor, scaling: Tensor, grad_accum: Tensor, denom: Te
     capacity = n * max(2, int(n_split))
     map_ = torch.empty(capacity, dtype=torch.int32, device=dev)
     counts = torch.zeros(4, dtype=torch.int32, device=dev)
-    ws = torch.empty(lib.lsr_densify_workspace_bytes(n), dtype=torch.uint8, device=dev)
+    ws = _args.workspace(lib.lsr_densify_workspace_bytes(n), dev)
     op, sc = op.detach().contiguous(), sc.detach().contiguous()
     with torch.cuda.device(dev):
-        _lib.check(lib.lsr_densify_plan(n, _ptr(op), _ptr(sc), *map(_ptr, stats), C.byref(params), _ptr(map_), capacity,
-                                        C.c_void_p(counts.data_ptr()), _ptr(ws), _stream(dev)), "lsr_densify_plan")
+        _lib.call("lsr_densify_plan", n, ptr(op), ptr(sc), *map(ptr, stats), C.byref(params), ptr(map_), capacity,
+                  C.c_void_p(counts.data_ptr()), ptr(ws), _args.stream(dev))
     return map_, counts
 
 
@@ -148,8 +135,8 @@ def apply_densify(map_: Tensor, counts: Tensor, n_out: int, tables: Sequence[Tup
             raise _lib.LsrError("eps must be (n_split * split parents, 3)")
         eps_rows = extras[2].shape[0]
     with torch.cuda.device(dev):
-        _lib.check(_lib.load().lsr_densify_apply(n, int(n_out), _ptr(map_), _ptr(counts), int(n_split), desc, num_tables,
-                                                 *map(_ptr, extras), eps_rows, _stream(dev)), "lsr_densify_apply")
+        _lib.call("lsr_densify_apply", n, int(n_out), ptr(map_), ptr(counts), int(n_split), desc, num_tables,
+                  *map(ptr, extras), eps_rows, _args.stream(dev))
     return outs
 
 

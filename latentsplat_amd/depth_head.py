@@ -18,8 +18,9 @@ from typing import Optional
 import torch
 from torch import Tensor, nn
 
-from . import _lib
-from .gaussian_adapter import _ptr, _row_stride, _stream
+from . import _args, _lib
+from ._args import ptr
+from .gaussian_adapter import _row_stride
 
 
 def opacity_exponent(initial: float, final: float, warm_up: int, global_step: int) -> float:
@@ -50,9 +51,8 @@ class _DepthHead(torch.autograd.Function):
         shape = (cams, rays, surfaces, samples)
         depth, opacity = torch.empty(shape, device=dev), torch.empty(shape, device=dev)
         index = torch.empty(shape, device=dev, dtype=torch.int32)
-        _lib.check(_lib.load().lsr_depth_head_forward(C.byref(dims), _ptr(logits), _ptr(near), _ptr(far),
-                                                      _ptr(uniforms), _ptr(depth), _ptr(opacity), _ptr(index),
-                                                      _stream(logits)), "lsr_depth_head_forward")
+        _lib.call("lsr_depth_head_forward", C.byref(dims), ptr(logits), ptr(near), ptr(far), ptr(uniforms), ptr(depth),
+                  ptr(opacity), ptr(index), _args.stream(logits))
         ctx.save_for_backward(logits, near, far, index)
         ctx.dims = dims
         ctx.mark_non_differentiable(index)
@@ -69,9 +69,8 @@ class _DepthHead(torch.autograd.Function):
         g_opacity = None if g_opacity is None else g_opacity.contiguous()
         # dense rows; for a strided view autograd's own view backward supplies the zeros around them
         d_logits = torch.empty((dims.num_cameras, dims.rays, 2 * dims.buckets * dims.surfaces), device=logits.device)
-        _lib.check(_lib.load().lsr_depth_head_backward(C.byref(dims), _ptr(logits), _ptr(near), _ptr(far),
-                                                       _ptr(index), _ptr(g_depth), _ptr(g_opacity), _ptr(d_logits),
-                                                       _stream(logits)), "lsr_depth_head_backward")
+        _lib.call("lsr_depth_head_backward", C.byref(dims), ptr(logits), ptr(near), ptr(far), ptr(index), ptr(g_depth),
+                  ptr(g_opacity), ptr(d_logits), _args.stream(logits))
         return d_logits, None, None, None, None, None, None, None, None
 
 

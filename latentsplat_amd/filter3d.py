@@ -18,18 +18,12 @@ built: it lives inside the projection kernel, behind the rasterizer's ABI.
 float32 ROCm tensors only; there is no CPU fallback."""
 from __future__ import annotations
 
-import ctypes as C
-from typing import Optional
-
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _args, _lib
+from ._args import ptr
 from .scene_model import _ActivateSceneFiltered, _filter, activate_forward
-
-
-def _ptr(t: Optional[Tensor]) -> C.c_void_p:
-    return C.c_void_p(None if t is None or t.numel() == 0 else t.data_ptr())
 
 
 def compute_filter_3d(xyz: Tensor, views: Tensor, width: int, *, margin: float = 0.15, variance: float = 0.2,
@@ -62,16 +56,14 @@ def compute_filter_3d(xyz: Tensor, views: Tensor, width: int, *, margin: float =
     seen = torch.empty(n, dtype=torch.uint8, device=dev) if return_seen else None
     if n > 0:
         pts, table = xyz.detach().contiguous(), views.detach().contiguous()
-        ws = torch.empty(lib.lsr_filter3d_workspace_bytes(n, V), dtype=torch.uint8, device=dev)
+        ws = _args.workspace(lib.lsr_filter3d_workspace_bytes(n, V), dev)
         mode = _lib.FILTER3D_PER_VIEW if per_view else _lib.FILTER3D_PUBLISHED
         with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _lib.check(lib.lsr_filter3d_compute(n, _ptr(pts), V, _ptr(table), int(width), float(margin), float(variance), mode,
-                                                _ptr(filt), _ptr(seen), _ptr(ws), stream), "lsr_filter3d_compute")
+            _lib.call("lsr_filter3d_compute", n, ptr(pts), V, ptr(table), int(width), float(margin), float(variance), mode,
+                      ptr(filt), ptr(seen), ptr(ws), _args.stream(dev))
     else:      # the argument checks of the library, which launches nothing
-        _lib.check(lib.lsr_filter3d_compute(0, None, V, None, int(width), float(margin), float(variance),
-                                            _lib.FILTER3D_PER_VIEW if per_view else _lib.FILTER3D_PUBLISHED, None, None, None, None),
-                   "lsr_filter3d_compute")
+        _lib.call("lsr_filter3d_compute", 0, None, V, None, int(width), float(margin), float(variance),
+                  _lib.FILTER3D_PER_VIEW if per_view else _lib.FILTER3D_PUBLISHED, None, None, None, None)
     return (filt, seen.bool()) if return_seen else filt
 
 

@@ -24,7 +24,8 @@ from typing import Callable, Optional
 import torch
 from torch import Tensor, nn
 
-from . import _lib
+from . import _args, _lib
+from ._args import ptr
 from .sh_rotate import rotate_harmonics
 from ._lib import AdapterDims, AdapterInGrads, AdapterInputs, AdapterOutGrads, AdapterOutputs
 
@@ -46,14 +47,6 @@ class GaussianAdapterCfg:             # gaussian_adapter.py:24-29
     gaussian_scale_max: float
     color_sh_degree: int
     feature_sh_degree: int
-
-
-def _ptr(t: Optional[Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream(t: Tensor):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 def _row_stride(t: Tensor) -> Optional[int]:
@@ -80,7 +73,6 @@ class _AdapterGeometry(torch.autograd.Function):
         for t in (extrinsics, intrinsics, coordinates, depths, raw):
             if not t.is_cuda or t.dtype != torch.float32:
                 raise _lib.LsrError("GaussianAdapter geometry needs float32 ROCm tensors (no CPU fallback)")
-        lib = _lib.load()
         cams, rays, samples = depths.shape
         extrinsics, intrinsics = extrinsics.contiguous(), intrinsics.contiguous()
         coordinates, depths = coordinates.contiguous(), depths.contiguous()
@@ -94,10 +86,9 @@ class _AdapterGeometry(torch.autograd.Function):
         cov = torch.empty((cams, rays, samples) + ((3, 3) if cov_elems == 9 else (6,)), device=dev)
         scales = torch.empty((cams, rays, samples, 3), device=dev)
         rotations = torch.empty((cams, rays, 4), device=dev)
-        inp = AdapterInputs(_ptr(extrinsics), _ptr(intrinsics), _ptr(coordinates), _ptr(depths), _ptr(raw))
-        out = AdapterOutputs(_ptr(means), _ptr(cov), _ptr(scales), _ptr(rotations))
-        _lib.check(lib.lsr_adapter_forward(C.byref(dims), C.byref(inp), C.byref(out), _stream(depths)),
-                   "lsr_adapter_forward")
+        inp = AdapterInputs(ptr(extrinsics), ptr(intrinsics), ptr(coordinates), ptr(depths), ptr(raw))
+        out = AdapterOutputs(ptr(means), ptr(cov), ptr(scales), ptr(rotations))
+        _lib.call("lsr_adapter_forward", C.byref(dims), C.byref(inp), C.byref(out), _args.stream(depths))
         ctx.save_for_backward(extrinsics, intrinsics, coordinates, depths, raw)
         ctx.dims = dims
         ctx.set_materialize_grads(False)
@@ -107,7 +98,6 @@ class _AdapterGeometry(torch.autograd.Function):
     def backward(ctx, g_means, g_cov, g_scales, g_rot):
         extrinsics, intrinsics, coordinates, depths, raw = ctx.saved_tensors
         dims = ctx.dims
-        lib = _lib.load()
         dev = depths.device
         cams, rays, samples = depths.shape
         g_means = torch.zeros((cams, rays, samples, 3), device=dev) if g_means is None else g_means.contiguous()
@@ -118,11 +108,10 @@ class _AdapterGeometry(torch.autograd.Function):
         d_coord = torch.empty((cams, rays, 2), device=dev)
         d_depth = torch.empty((cams, rays, samples), device=dev)
         d_raw = torch.empty((cams, rays, 7), device=dev)
-        inp = AdapterInputs(_ptr(extrinsics), _ptr(intrinsics), _ptr(coordinates), _ptr(depths), _ptr(raw))
-        dout = AdapterOutGrads(_ptr(g_means), _ptr(g_cov), _ptr(g_scales), _ptr(g_rot))
-        din = AdapterInGrads(_ptr(d_coord), _ptr(d_depth), _ptr(d_raw))
-        _lib.check(lib.lsr_adapter_backward(C.byref(dims), C.byref(inp), C.byref(dout), C.byref(din),
-                                            _stream(depths)), "lsr_adapter_backward")
+        inp = AdapterInputs(ptr(extrinsics), ptr(intrinsics), ptr(coordinates), ptr(depths), ptr(raw))
+        dout = AdapterOutGrads(ptr(g_means), ptr(g_cov), ptr(g_scales), ptr(g_rot))
+        din = AdapterInGrads(ptr(d_coord), ptr(d_depth), ptr(d_raw))
+        _lib.call("lsr_adapter_backward", C.byref(dims), C.byref(inp), C.byref(dout), C.byref(din), _args.stream(depths))
         return None, None, d_coord, d_depth, d_raw, None, None, None, None, None, None
 
 

@@ -9,13 +9,13 @@ chunks of the sorted cloud, and a workgroup-wide bound that skips only what cann
 float32 ROCm tensors only; there is no CPU fallback."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Tuple
 
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _args, _lib
+from ._args import ptr
 
 
 def _points(points: Tensor) -> Tensor:
@@ -38,11 +38,9 @@ def _run(points: Tensor, want_mean: bool, want_dist2: bool, want_index: bool):
     if n == 0:
         return mean, dist2, index
     lib = _lib.load()
-    ws = torch.empty(lib.lsr_knn3_workspace_bytes(n), dtype=torch.uint8, device=dev)
-    ptr = lambda t: C.c_void_p(None if t is None else t.data_ptr())
+    ws = _args.workspace(lib.lsr_knn3_workspace_bytes(n), dev)
     with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.lsr_knn3(n, ptr(p), ptr(mean), ptr(dist2), ptr(index), ptr(ws), stream), "lsr_knn3")
+        _lib.call("lsr_knn3", n, ptr(p), ptr(mean), ptr(dist2), ptr(index), ptr(ws), _args.stream(dev))
     return mean, dist2, index
 
 

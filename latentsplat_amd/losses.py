@@ -13,16 +13,12 @@ fallback."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional
 
 import torch
 from torch import Tensor
 
-from . import _lib
-
-
-def _ptr(t: Optional[Tensor]) -> C.c_void_p:
-    return C.c_void_p(None if t is None else t.data_ptr())
+from . import _args, _lib
+from ._args import ptr
 
 
 def _prepare(what: str, image: Tensor, target: Tensor):
@@ -60,11 +56,10 @@ def photometric_forward(image: Tensor, target: Tensor, lambda_dssim: float = 0.2
     lib = _lib.load()
     dims = _dims(x.shape, lambda_dssim, cov_norm, crop)
     out = {k: torch.empty(s, dtype=torch.float32, device=x.device) for k, s in shapes.items() if k in want}
-    workspace = torch.empty(max(lib.lsr_photometric_workspace_bytes(C.byref(dims)), 16), dtype=torch.uint8, device=x.device)
+    workspace = _args.workspace(max(lib.lsr_photometric_workspace_bytes(C.byref(dims)), 16), x.device)
     with torch.cuda.device(x.device):
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        _lib.check(lib.lsr_photometric_forward(C.byref(dims), _ptr(x), _ptr(y), _ptr(workspace), *(_ptr(out.get(k)) for k in shapes),
-                                               stream), "lsr_photometric_forward")
+        _lib.call("lsr_photometric_forward", C.byref(dims), ptr(x), ptr(y), ptr(workspace),
+                  *(ptr(out.get(k)) for k in shapes), _args.stream(x))
     return out
 
 
@@ -76,12 +71,10 @@ def photometric_backward(image: Tensor, target: Tensor, saved: Tensor, grad_loss
         if not torch.is_tensor(t) or t.device != x.device or t.dtype != torch.float32 or t.numel() != n:
             raise _lib.LsrError(f"{name} must be a float32 tensor of {n} elements on the images' device")
     saved, grad_loss = saved.detach().contiguous(), grad_loss.detach().contiguous()
-    lib = _lib.load()
     grad = torch.empty_like(x)
     with torch.cuda.device(x.device):
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        _lib.check(lib.lsr_photometric_backward(C.byref(_dims(x.shape, lambda_dssim)), _ptr(x), _ptr(y), _ptr(saved),
-                                                _ptr(grad_loss), _ptr(grad), stream), "lsr_photometric_backward")
+        _lib.call("lsr_photometric_backward", C.byref(_dims(x.shape, lambda_dssim)), ptr(x), ptr(y), ptr(saved),
+                  ptr(grad_loss), ptr(grad), _args.stream(x))
     return grad
 
 

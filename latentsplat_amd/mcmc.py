@@ -12,15 +12,16 @@ did; :func:`inject_noise` is the per-step noise in one launch.  :class:`MCMCCont
 float32 ROCm tensors only; there is no CPU fallback."""
 from __future__ import annotations
 
-import ctypes as C
 import math
+from functools import partial
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _args, _lib
+from ._args import ptr
 
 ROLES = dict(copy=_lib.MCMC_COPY, opacity=_lib.MCMC_OPACITY, scaling=_lib.MCMC_SCALING, moment=_lib.MCMC_MOMENT)
 _SCENE_PARAMS = ("_xyz", "_features_dc", "_features_rest", "_opacity", "_scaling", "_rotation")
@@ -28,18 +29,7 @@ _SCENE_ROLES = dict(_xyz="copy", _features_dc="copy", _features_rest="copy", _op
 _MOMENTS = ("exp_avg", "exp_avg_sq", "max_exp_avg_sq")
 
 
-def _ptr(t: Optional[Tensor]) -> C.c_void_p:
-    return C.c_void_p(None if t is None or t.numel() == 0 else t.data_ptr())
-
-
-def _f32(name: str, t, shape: Optional[tuple] = None, device=None) -> Tensor:
-    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32:
-        raise _lib.LsrError(f"the MCMC strategy needs float32 ROCm tensors (no CPU fallback): {name} is not one")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise _lib.LsrError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
-    if device is not None and t.device != device:
-        raise _lib.LsrError(f"{name} must be on {device}")
-    return t
+_f32 = partial(_args.f32, "the MCMC strategy")
 
 
 def _i32(name: str, t, numel: int, device) -> Tensor:
@@ -52,14 +42,6 @@ def _rows(n: int) -> int:
     if n >= _lib.MCMC_MAX_ROWS:
         raise _lib.LsrError(f"the MCMC strategy takes fewer than 2^28 rows, got {n}")
     return n
-
-
-def _stream(dev) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _workspace(lib, n: int, m: int, dev) -> Tensor:
-    return torch.empty(lib.lsr_mcmc_workspace_bytes(n, m), dtype=torch.uint8, device=dev)
 
 
 def dead_logit(min_opacity: float) -> float:
@@ -85,14 +67,12 @@ def classify_dead(opacity: Tensor, threshold_logit: float, want_dead: bool = Tru
     weights = torch.empty(n, dtype=torch.float32, device=dev)
     dead = torch.empty(n, dtype=torch.int32, device=dev) if want_dead else None
     counts = torch.zeros(2, dtype=torch.int32, device=dev) if want_dead else None
-    ws = _workspace(lib, n, 0, dev) if want_dead else None
+    ws = _args.workspace(lib.lsr_mcmc_workspace_bytes(n, 0), dev) if want_dead else None
     if n == 0:
         return weights, dead, counts
     with torch.cuda.device(dev):
-        _lib.check(lib.lsr_mcmc_classify(n, _ptr(op), float(threshold_logit), _ptr(weights),
-                                         C.c_void_p(dead.data_ptr() if want_dead else None),
-                                         C.c_void_p(counts.data_ptr() if want_dead else None), _ptr(ws), _stream(dev)),
-                   "lsr_mcmc_classify")
+        _lib.call("lsr_mcmc_classify", n, ptr(op), float(threshold_logit), ptr(weights), ptr(dead), ptr(counts), ptr(ws),
+                  _args.stream(dev))
     return weights, dead, counts
 
 
@@ -118,10 +98,10 @@ def sample_by_weight(weights: Tensor, uniforms: Tensor, return_total: bool = Fal
     idx = torch.empty(m, dtype=torch.int32, device=dev)
     count = torch.zeros(n, dtype=torch.int32, device=dev)
     total = torch.zeros(1, dtype=torch.int64, device=dev)
-    ws = _workspace(lib, n, m, dev)
+    ws = _args.workspace(lib.lsr_mcmc_workspace_bytes(n, m), dev)
     with torch.cuda.device(dev):
-        _lib.check(lib.lsr_mcmc_sample(n, _ptr(w), m, _ptr(u), _ptr(idx), _ptr(count), C.c_void_p(total.data_ptr()), _ptr(ws),
-                                       _stream(dev)), "lsr_mcmc_sample")
+        _lib.call("lsr_mcmc_sample", n, ptr(w), m, ptr(u), ptr(idx), ptr(count), ptr(total), ptr(ws),
+                  _args.stream(dev))
     return (idx, count, total) if return_total else (idx, count)
 
 
@@ -162,11 +142,10 @@ def apply_relocation(tables: Sequence[Tuple[Tensor, str]], n: int, idx: Tensor, 
         return
     lib = _lib.load()
     arr = (_lib.McmcTable * max(len(desc), 1))(*desc)
-    ws = _workspace(lib, n, m, dev)
-    dest_ptr = C.c_void_p(None) if dest is None else C.c_void_p(dest.data_ptr())
+    ws = _args.workspace(lib.lsr_mcmc_workspace_bytes(n, m), dev)
     with torch.cuda.device(dev):
-        _lib.check(lib.lsr_mcmc_apply(n, m, _ptr(idx), _ptr(count), dest_ptr, arr, len(desc), float(min_opacity), _ptr(ws),
-                                      _stream(dev)), "lsr_mcmc_apply")
+        _lib.call("lsr_mcmc_apply", n, m, ptr(idx), ptr(count), ptr(dest), arr, len(desc), float(min_opacity), ptr(ws),
+                  _args.stream(dev))
 
 
 def relocation_values(opacity: Tensor, scaling: Tensor, count: Tensor, min_opacity: float = 0.005) -> Tuple[Tensor, Tensor]:
@@ -206,8 +185,8 @@ def inject_noise(xyz: Tensor, opacity: Tensor, scaling: Tensor, rotation: Tensor
         return
     op, sc, rot, e = (t.detach().contiguous() for t in (op, sc, rot, e))
     with torch.cuda.device(dev):
-        _lib.check(_lib.load().lsr_mcmc_noise(n, _ptr(x.detach()), _ptr(op), _ptr(sc), _ptr(rot), _ptr(e), float(step_scale),
-                                              _stream(dev)), "lsr_mcmc_noise")
+        _lib.call("lsr_mcmc_noise", n, ptr(x.detach()), ptr(op), ptr(sc), ptr(rot), ptr(e), float(step_scale),
+                  _args.stream(dev))
 
 
 def _held_parameters(scene, optimizer, what: str):

@@ -16,12 +16,13 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+from functools import partial
 from typing import Optional, Sequence
 
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _args, _lib
 
 
 def expon_lr(step: int, lr_init: float, lr_final: float, max_steps: int, delay_steps: int = 0, delay_mult: float = 1.0) -> float:
@@ -62,12 +63,7 @@ def adam_scalars(lr: float, betas, step: int, bias_correction: bool = True):
     return float(lr) / (1.0 - float(betas[0]) ** step), 1.0 / math.sqrt(1.0 - float(betas[1]) ** step)
 
 
-def _f32(name: str, t, contiguous: bool) -> Tensor:
-    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32:
-        raise _lib.LsrError(f"adam_step needs float32 ROCm tensors (no CPU fallback): {name} is not one")
-    if contiguous and not t.is_contiguous():
-        raise _lib.LsrError(f"{name} is updated in place and must be contiguous (it is not copied)")
-    return t
+_f32 = partial(_args.f32, "adam_step")
 
 
 def adam_step(tables: Sequence[dict], visible: Optional[Tensor] = None) -> None:
@@ -95,10 +91,10 @@ def adam_step(tables: Sequence[dict], visible: Optional[Tensor] = None) -> None:
         vis = vis.view(torch.uint8) if vis.dtype == torch.bool else vis
         n_vis, dev = vis.shape[0], vis.device
     for i, t in enumerate(tables):
-        p = _f32(f"table {i} param", t["param"], True)
-        m = _f32(f"table {i} exp_avg", t["exp_avg"], True)
-        v = _f32(f"table {i} exp_avg_sq", t["exp_avg_sq"], True)
-        g = _f32(f"table {i} grad", t["grad"], False)
+        p = _f32(f"table {i} param", t["param"], contiguous=True)
+        m = _f32(f"table {i} exp_avg", t["exp_avg"], contiguous=True)
+        v = _f32(f"table {i} exp_avg_sq", t["exp_avg_sq"], contiguous=True)
+        g = _f32(f"table {i} grad", t["grad"])
         dev = p.device if dev is None else dev
         if any(x.device != dev for x in (p, m, v, g)):
             raise _lib.LsrError(f"table {i}: every tensor of a call must be on {dev}")
@@ -126,14 +122,12 @@ def adam_step(tables: Sequence[dict], visible: Optional[Tensor] = None) -> None:
                                    eps=float(t.get("eps", 1e-8)), step_size=step_size, inv_sqrt_bc2=inv_sqrt_bc2, reserved_f=0.0))
     if not desc:
         return
-    lib = _lib.load()
     with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         for at in range(0, len(desc), _lib.ADAM_MAX_TABLES):
             chunk = desc[at:at + _lib.ADAM_MAX_TABLES]
             arr = (_lib.AdamTable * len(chunk))(*chunk)
-            _lib.check(lib.lsr_adam_step(arr, len(chunk), C.c_void_p(None if vis is None or n_vis == 0 else vis.data_ptr()),
-                                         n_vis, stream), "lsr_adam_step")
+            _lib.call("lsr_adam_step", arr, len(chunk), C.c_void_p(None if vis is None or n_vis == 0 else vis.data_ptr()),
+                      n_vis, _args.stream(dev))
 
 
 class SceneAdam(torch.optim.Adam):

@@ -16,7 +16,8 @@ from typing import Optional
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _args, _lib
+from ._args import ptr
 from ._lib import PLY_VERTEX_FLOATS, PlyInputs
 
 
@@ -34,7 +35,6 @@ def pack_vertices(extrinsics: Tensor, means: Tensor, scales: Tensor, rotations: 
     for t in tensors:
         if not t.is_cuda or t.dtype != torch.float32:
             raise _lib.LsrError("export_ply needs float32 ROCm tensors (no CPU fallback)")
-    lib = _lib.load()
     extrinsics, means, scales, rotations, harmonics, opacities = (t.detach().contiguous() for t in tensors)
     n = means.shape[0]
     if harmonics.dim() != 3 or harmonics.shape[1] != 3:
@@ -43,11 +43,9 @@ def pack_vertices(extrinsics: Tensor, means: Tensor, scales: Tensor, rotations: 
     center = means.median(dim=0).values.contiguous()
     scale_factor = (means - center).abs().quantile(0.95, dim=0).max().reshape(1).contiguous()
     out = torch.empty((n, PLY_VERTEX_FLOATS), device=means.device)
-    p = lambda t: C.c_void_p(t.data_ptr())
-    inp = PlyInputs(p(extrinsics), p(means), p(scales), p(rotations), p(harmonics), p(opacities), p(center),
-                    p(scale_factor))
-    stream = C.c_void_p(torch.cuda.current_stream(means.device).cuda_stream)
-    _lib.check(lib.lsr_ply_pack(n, harmonics.shape[2], C.byref(inp), p(out), stream), "lsr_ply_pack")
+    inp = PlyInputs(ptr(extrinsics), ptr(means), ptr(scales), ptr(rotations), ptr(harmonics), ptr(opacities), ptr(center),
+                    ptr(scale_factor))
+    _lib.call("lsr_ply_pack", n, harmonics.shape[2], C.byref(inp), ptr(out), _args.stream(means))
     return out
 
 
@@ -56,8 +54,7 @@ def export_ply(extrinsics: Tensor, means: Tensor, scales: Tensor, rotations: Ten
     vertices = pack_vertices(extrinsics, means, scales, rotations, harmonics, opacities).cpu().contiguous()
     path = Path(path)
     path.parent.mkdir(exist_ok=True, parents=True)
-    _lib.check(_lib.load().lsr_ply_write_host(os.fsencode(str(path)), C.c_void_p(vertices.data_ptr()),
-                                              vertices.shape[0]), "lsr_ply_write_host")
+    _lib.call("lsr_ply_write_host", os.fsencode(str(path)), C.c_void_p(vertices.data_ptr()), vertices.shape[0])
 
 
 # ---- scene export: a standard 3DGS scene file that keeps the scene (every SH band, logit opacities, geometry taken from
@@ -117,15 +114,12 @@ def pack_scene(means: Tensor, opacities: Tensor, shs: Tensor, *, covariances: Op
         raise _lib.LsrError("scales must be (n, 3) and rotations (n, 4)")
     if tuple(means.shape) != (n, 3) or opacities.shape[0] != n or shs.shape[0] != n:
         raise _lib.LsrError("means must be (n, 3), opacities (n,) or (n, 1), shs n Gaussians")
-    lib = _lib.load()
     rows = torch.empty((n, _lib.ply_scene_row_floats(K_out)), dtype=torch.float32, device=dev)
-    p = lambda t: C.c_void_p(None if t is None else t.data_ptr())
-    inp = _lib.PlySceneInputs(p(means), p(opacities), p(shs), p(covariances), p(scales), p(rotations), K_in,
+    inp = _lib.PlySceneInputs(ptr(means), ptr(opacities), ptr(shs), ptr(covariances), ptr(scales), ptr(rotations), K_in,
                               int(bool(channel_major)), cov_elems, 0)
     opts = _lib.PlySceneOpts(_CONVENTIONS[convention], K_out, 0, 0)
     with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.lsr_ply_pack_scene(n, C.byref(inp), C.byref(opts), p(rows), stream), "lsr_ply_pack_scene")
+        _lib.call("lsr_ply_pack_scene", n, C.byref(inp), C.byref(opts), ptr(rows), _args.stream(dev))
     return rows
 
 
@@ -138,8 +132,7 @@ def save_ply(path, means: Tensor, opacities: Tensor, shs: Tensor, **opts) -> Non
     path = Path(path)
     path.parent.mkdir(exist_ok=True, parents=True)
     K = (rows.shape[1] - 14) // 3
-    _lib.check(_lib.load().lsr_ply_write_scene_host(os.fsencode(str(path)), C.c_void_p(host.data_ptr()), rows.shape[0], K),
-               "lsr_ply_write_scene_host")
+    _lib.call("lsr_ply_write_scene_host", os.fsencode(str(path)), C.c_void_p(host.data_ptr()), rows.shape[0], K)
 
 
 def save_gaussians(path, gaussians, scene: int = 0, **opts) -> None:

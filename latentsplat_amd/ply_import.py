@@ -19,7 +19,8 @@ from typing import Optional, Sequence
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _args, _lib
+from ._args import ptr
 from ._lib import PlyLayout, PlyOutputs
 
 _OPACITY_FLAGS = {"logit": 0, "raw": _lib.PLY_OPACITY_RAW}
@@ -74,7 +75,6 @@ def unpack_table(rows: Tensor, layout: PlyLayout, opacity: str = "logit", want: 
         raise _lib.LsrError(f"opacity must be 'logit' or 'raw', got {opacity!r}")
     if not rows.is_cuda or rows.dtype != torch.float32:
         raise _lib.LsrError("ply import needs a float32 ROCm row table (no CPU fallback)")
-    lib = _lib.load()
     rows = rows.detach().contiguous()
     n, K, dev = layout.n, layout.sh_coeffs, rows.device
     if rows.dim() != 2 or tuple(rows.shape) != (n, layout.stride):
@@ -86,9 +86,8 @@ def unpack_table(rows: Tensor, layout: PlyLayout, opacity: str = "logit", want: 
     out = {k: torch.empty(s, dtype=torch.float32, device=dev) for k, s in shapes.items() if want is None or k in want}
     ptrs = PlyOutputs(**{k: C.c_void_p(t.data_ptr()) for k, t in out.items()})
     with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.lsr_ply_unpack(C.byref(layout), C.c_void_p(rows.data_ptr()), _OPACITY_FLAGS[opacity],
-                                      C.byref(ptrs), stream), "lsr_ply_unpack")
+        _lib.call("lsr_ply_unpack", C.byref(layout), C.c_void_p(rows.data_ptr()), _OPACITY_FLAGS[opacity], C.byref(ptrs),
+                  _args.stream(dev))
     return out
 
 
@@ -106,7 +105,7 @@ def unpack_vertices(rows: Tensor, names: Sequence[str], *, opacity: str = "logit
 def read_header(path) -> PlyLayout:
     """The layout ``lsr_ply_read_header`` parses from the file (host only)."""
     layout = PlyLayout()
-    _lib.check(_lib.load().lsr_ply_read_header(os.fsencode(str(path)), C.byref(layout)), "lsr_ply_read_header")
+    _lib.call("lsr_ply_read_header", os.fsencode(str(path)), C.byref(layout))
     return layout
 
 
@@ -118,11 +117,9 @@ def load_ply(path, device, *, opacity: str = "logit") -> Scene3DGS:
                             "there is no CPU fallback")
     if opacity not in _OPACITY_FLAGS:
         raise _lib.LsrError(f"opacity must be 'logit' or 'raw', got {opacity!r}")
-    lib = _lib.load()
     layout = read_header(path)
     host = torch.empty((layout.n, layout.stride), dtype=torch.float32, pin_memory=True)
-    _lib.check(lib.lsr_ply_read_rows(os.fsencode(str(path)), C.c_void_p(host.data_ptr()), host.numel()),
-               "lsr_ply_read_rows")
+    _lib.call("lsr_ply_read_rows", os.fsencode(str(path)), C.c_void_p(host.data_ptr()), host.numel())
     return _scene(unpack_table(host.to(device, non_blocking=True), layout, opacity), layout.sh_coeffs)
 
 
@@ -132,13 +129,11 @@ def load_points_ply(path, device):
     float32 on ``device``.  The library's host reader (``lsr_ply_read_points``); what
     :meth:`latentsplat_amd.scene_model.GaussianScene.from_point_cloud` starts from."""
     device = torch.device(device)
-    lib = _lib.load()
     n, has_colors = C.c_int64(0), C.c_int32(0)
     name = os.fsencode(str(path))
-    _lib.check(lib.lsr_ply_read_points_header(name, C.byref(n), C.byref(has_colors)), "lsr_ply_read_points_header")
+    _lib.call("lsr_ply_read_points_header", name, C.byref(n), C.byref(has_colors))
     pin = device.type == "cuda"
     xyz = torch.empty((n.value, 3), dtype=torch.float32, pin_memory=pin)
     rgb = torch.empty((n.value, 3), dtype=torch.float32, pin_memory=pin) if has_colors.value else None
-    ptr = lambda t: C.c_void_p(None if t is None or t.numel() == 0 else t.data_ptr())
-    _lib.check(lib.lsr_ply_read_points(name, ptr(xyz), ptr(rgb), n.value), "lsr_ply_read_points")
+    _lib.call("lsr_ply_read_points", name, ptr(xyz), ptr(rgb), n.value)
     return xyz.to(device), None if rgb is None else rgb.to(device)

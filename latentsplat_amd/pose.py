@@ -25,8 +25,9 @@ from typing import Optional
 import torch
 from torch import Tensor, nn
 
-from . import _lib
-from .transform import _NAMES, _check_scene, _index, _ptr, _quad, _split, apply_records, transform_records
+from . import _args, _lib
+from ._args import ptr
+from .transform import _NAMES, _check_scene, _index, _split, apply_records, transform_records
 
 MAX_TRANSFORMS = _lib.POSE_MAX_TRANSFORMS
 
@@ -53,8 +54,7 @@ def _pose_matrices(q: Tensor, t: Tensor, ls: Optional[Tensor]) -> Tensor:
     T = q.shape[0]
     out = torch.empty((T, 4, 4), dtype=torch.float32, device=q.device)
     with torch.cuda.device(q.device):
-        stream = C.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
-        _lib.check(_lib.load().lsr_pose_matrices(T, _ptr(q), _ptr(t), _ptr(ls), _ptr(out), stream), "lsr_pose_matrices")
+        _lib.call("lsr_pose_matrices", T, ptr(q), ptr(t), ptr(ls), ptr(out), _args.stream(q))
     return out
 
 
@@ -77,7 +77,7 @@ class _PoseScene(torch.autograd.Function):
                                   None if log_scales is None else log_scales.detach().contiguous())
         records = transform_records(matrices, isqrt(K) - 1, check=False)
         ins = dict(xyz=xyz.detach().contiguous(), features_rest=features_rest.detach().contiguous(),
-                   scaling=scaling.detach().contiguous(), rotation=_quad(rotation.detach().contiguous()))
+                   scaling=scaling.detach().contiguous(), rotation=_args.quad(rotation.detach().contiguous()))
         outs = {k: torch.empty_like(t) for k, t in ins.items()}
         apply_records(records, idx, ins, outs, n, K)
         adjoint = transform_records(matrices, isqrt(K) - 1, adjoint=True, check=False) if any(ctx.needs_input_grad[:4]) else None
@@ -94,7 +94,7 @@ class _PoseScene(torch.autograd.Function):
         for k, need, g in zip(_NAMES, ctx.needs_input_grad, grads):
             if need and g is not None:
                 g = g.detach().contiguous()
-                ins[k] = _quad(g) if k == "rotation" else g
+                ins[k] = _args.quad(g) if k == "rotation" else g
                 outs[k] = torch.empty_like(g)
         if outs:
             apply_records(adjoint, idx, ins, outs, n, K)
@@ -104,21 +104,19 @@ class _PoseScene(torch.autograd.Function):
             dev = q.device
             g = {k: (None if v is None else v.detach().contiguous()) for k, v in zip(_NAMES, grads)}
             if g["rotation"] is not None:
-                g["rotation"] = _quad(g["rotation"])
+                g["rotation"] = _args.quad(g["rotation"])
             shapes = ((T, 4), (T, 3), (T,))
             pose = [torch.empty(s, dtype=torch.float32, device=dev) if need else None
                     for s, need in zip(shapes, ctx.needs_input_grad[4:7])]
             lib = _lib.load()
-            ws = torch.empty(max(int(lib.lsr_pose_grad_workspace_bytes(n, K, T)), 8), dtype=torch.uint8, device=dev)
+            ws = _args.workspace(max(int(lib.lsr_pose_grad_workspace_bytes(n, K, T)), 8), dev)
             dims = _lib.TransformDims(n=n, sh_coeffs=K, num_transforms=T, reserved0=0, reserved1=0)
-            gin = _lib.PoseGradIn(xyz=_ptr(xyz), rotation=_ptr(rot), features_rest=_ptr(rest), g_xyz=_ptr(g["xyz"]),
-                                  g_features_rest=_ptr(g["features_rest"]), g_scaling=_ptr(g["scaling"]),
-                                  g_rotation=_ptr(g["rotation"]))
+            gin = _lib.PoseGradIn(xyz=ptr(xyz), rotation=ptr(rot), features_rest=ptr(rest), g_xyz=ptr(g["xyz"]),
+                                  g_features_rest=ptr(g["features_rest"]), g_scaling=ptr(g["scaling"]),
+                                  g_rotation=ptr(g["rotation"]))
             with torch.cuda.device(dev):
-                stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-                _lib.check(lib.lsr_scene_pose_grad(C.byref(dims), _ptr(records), _ptr(idx), _ptr(q), C.byref(gin), _ptr(ws),
-                                                   ws.numel(), _ptr(pose[0]), _ptr(pose[1]), _ptr(pose[2]), stream),
-                           "lsr_scene_pose_grad")
+                _lib.call("lsr_scene_pose_grad", C.byref(dims), ptr(records), ptr(idx), ptr(q), C.byref(gin), ptr(ws),
+                          ws.numel(), ptr(pose[0]), ptr(pose[1]), ptr(pose[2]), _args.stream(dev))
         return tuple(outs.get(k) for k in _NAMES) + tuple(pose) + (None,)
 
 

@@ -19,7 +19,8 @@ from typing import NamedTuple, Optional
 import torch
 from torch import Tensor, nn
 
-from . import _lib
+from . import _args, _lib
+from ._args import ptr
 from ._lib import Dims, InGrads, Inputs, LsrError, OutGrads, Outputs
 
 
@@ -154,7 +155,6 @@ def _straight_through(values: Tensor, carrier: Tensor) -> Tensor:
 
 def _build_view_table(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor, background: Tensor,
                       scale_invariant: bool, depth_mode: int = _lib.DEPTH_NATIVE) -> Tensor:
-    lib = _lib.load()
     dev = extrinsics.device
     if dev.type != "cuda":
         raise LsrError("build_view_table runs on the MI355X; use make_view_table for host tensors")
@@ -162,21 +162,15 @@ def _build_view_table(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far:
     f = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
     ext, intr, nr, fr, bg = f(extrinsics), f(intrinsics), f(near), f(far), f(background)
     out = torch.empty((V, _lib.VIEW_FLOATS), dtype=torch.float32, device=dev)
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    stream = _args.stream(dev)
     with torch.cuda.device(dev):
         if depth_mode == _lib.DEPTH_NATIVE:
-            _lib.check(lib.lsr_build_views(V, _ptr(ext), _ptr(intr), _ptr(nr), _ptr(fr), _ptr(bg),
-                                           0 if bg.dim() == 1 else 3, 1 if scale_invariant else 0, _ptr(out), stream),
-                       "lsr_build_views")
+            _lib.call("lsr_build_views", V, ptr(ext), ptr(intr), ptr(nr), ptr(fr), ptr(bg), 0 if bg.dim() == 1 else 3,
+                      1 if scale_invariant else 0, ptr(out), stream)
         else:
-            _lib.check(lib.lsr_build_views_depth(V, _ptr(ext), _ptr(intr), _ptr(nr), _ptr(fr), _ptr(bg),
-                                                 0 if bg.dim() == 1 else 3, 1 if scale_invariant else 0, depth_mode,
-                                                 _ptr(out), stream), "lsr_build_views_depth")
+            _lib.call("lsr_build_views_depth", V, ptr(ext), ptr(intr), ptr(nr), ptr(fr), ptr(bg),
+                      0 if bg.dim() == 1 else 3, 1 if scale_invariant else 0, depth_mode, ptr(out), stream)
     return out
-
-
-def _ptr(t: Optional[Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def _prep(t: Optional[Tensor], name: str, dev) -> Optional[Tensor]:
@@ -369,8 +363,8 @@ class _RasterizeViews(torch.autograd.Function):
                  # (never below the sort-tier hint of the speculative forward: a launch structure chosen for lists of up to `hint`
                  # keys would otherwise include the fallback scatter for segments shorter than that)
                  min(max(int(1.3 * est[1]) + 64, _tier_hint(est[1])), 2 ** 31 - 1) if (est is not None and est[1] > 0) else 0)
-        inp = Inputs(_ptr(views), _ptr(means3D), _ptr(cov3D), _ptr(opacities), _ptr(color), _ptr(features))
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        inp = Inputs(ptr(views), ptr(means3D), ptr(cov3D), ptr(opacities), ptr(color), ptr(features))
+        stream = _args.stream(dev)
         u8 = dict(dtype=torch.uint8, device=dev)
         geom_bytes = lib.lsr_geom_workspace_bytes(C.byref(d))
         if geom_bytes == 0:
@@ -390,7 +384,8 @@ class _RasterizeViews(torch.autograd.Function):
             radii = torch.empty((V, G), dtype=torch.int32, device=dev)
             if _EARLY_FRONT and G > 0 and 0 < front_cap < 2 ** 32:
                 d.forward_flags |= _lib.FWD_FRONT_DONE
-                _lib.check(lib.lsr_forward_front(C.byref(d), C.byref(inp), _ptr(geom), _ptr(radii), front_cap, stream), "lsr_forward_front")
+                _lib.check(lib.lsr_forward_front(C.byref(d), C.byref(inp), ptr(geom), ptr(radii), front_cap, stream),
+                           "lsr_forward_front")
             img = torch.empty(lib.lsr_image_workspace_bytes(C.byref(d)), **u8)
             # everything that does not depend on the pair count is allocated BEFORE prepare(): the GPU
             # idles between prepare's synchronisation and the launches of render(), so that window
@@ -402,24 +397,23 @@ class _RasterizeViews(torch.autograd.Function):
             out_depth = torch.empty((V, H, W), **f32)
             gradws = (torch.empty(lib.lsr_grad_workspace_bytes(C.byref(d)), **u8)
                       if d.forward_flags & _lib.FWD_CLEARS_GRAD else None)
-            outs = Outputs(_ptr(out_color), _ptr(out_feat), _ptr(out_mask), _ptr(out_depth), _ptr(radii), _ptr(gradws))
+            outs = Outputs(ptr(out_color), ptr(out_feat), ptr(out_mask), ptr(out_depth), ptr(radii), ptr(gradws))
             if pair_capacity > 0:
                 # latency mode: no host synchronisation; the pair count stays on the device
                 # (last_forward_status() reads it back when the caller wants to check for overflow)
                 npairs.value, maxtile.value = int(pair_capacity), int(max_tile_hint)
                 layout_pairs = npairs.value
                 binws = torch.empty(lib.lsr_binning_workspace_bytes(C.byref(d), npairs.value, 2 ** 31 - 1), **u8)
-                _lib.check(lib.lsr_forward_nosync(C.byref(d), C.byref(inp), _ptr(geom), _ptr(binws), _ptr(img),
-                                                  npairs.value, maxtile.value, C.byref(outs), stream),
-                           "lsr_forward_nosync")
+                _lib.check(lib.lsr_forward_nosync(C.byref(d), C.byref(inp), ptr(geom), ptr(binws), ptr(img), npairs.value,
+                                                  maxtile.value, C.byref(outs), stream), "lsr_forward_nosync")
             else:
                 done = False
                 if speculate:
                     binws = torch.empty(lib.lsr_binning_workspace_bytes(C.byref(d), cap, hint), **u8)
                     ov = C.c_int32(0)
-                    _lib.check(lib.lsr_forward_speculative(C.byref(d), C.byref(inp), _ptr(geom), _ptr(binws), _ptr(img), cap, hint,
-                                                           C.byref(outs), C.byref(npairs), C.byref(maxtile), C.byref(ov), stream),
-                               "lsr_forward_speculative")
+                    _lib.check(lib.lsr_forward_speculative(C.byref(d), C.byref(inp), ptr(geom), ptr(binws), ptr(img), cap,
+                                                           hint, C.byref(outs), C.byref(npairs), C.byref(maxtile),
+                                                           C.byref(ov), stream), "lsr_forward_speculative")
                     done = not ov.value
                     SPECULATION_STATS["speculative" if done else "reruns"] += 1
                     if done:
@@ -427,12 +421,11 @@ class _RasterizeViews(torch.autograd.Function):
                 if not done:
                     SPECULATION_STATS["exact"] += 1
                     d.forward_flags &= ~_lib.FWD_FRONT_DONE      # (a speculative forward that fell short is run again from the start)
-                    _lib.check(lib.lsr_forward_prepare(C.byref(d), C.byref(inp), _ptr(geom), _ptr(radii),
-                                                       C.byref(npairs), C.byref(maxtile), stream),
-                               "lsr_forward_prepare")
+                    _lib.check(lib.lsr_forward_prepare(C.byref(d), C.byref(inp), ptr(geom), ptr(radii), C.byref(npairs),
+                                                       C.byref(maxtile), stream), "lsr_forward_prepare")
                     # the largest pair-count dependent allocation (the likeliest out-of-memory site of a forward)
                     binws = torch.empty(lib.lsr_binning_workspace_bytes(C.byref(d), npairs.value, maxtile.value), **u8)
-                    _lib.check(lib.lsr_forward_render(C.byref(d), C.byref(inp), _ptr(geom), _ptr(binws), _ptr(img),
+                    _lib.check(lib.lsr_forward_render(C.byref(d), C.byref(inp), ptr(geom), ptr(binws), ptr(img),
                                                       npairs.value, maxtile.value, C.byref(outs), stream),
                                "lsr_forward_render")
                     layout_pairs = npairs.value
@@ -445,7 +438,7 @@ class _RasterizeViews(torch.autograd.Function):
                     # workspace with the host's pair count; the device flags a list that did not fit (it cannot
                     # happen unless the two counts disagree) — surface it instead of rendering a tile short
                     n, mt, ov = C.c_int64(0), C.c_int32(0), C.c_int32(0)
-                    _lib.check(lib.lsr_forward_status(C.byref(d), _ptr(geom), C.byref(n), C.byref(mt), C.byref(ov), stream),
+                    _lib.check(lib.lsr_forward_status(C.byref(d), ptr(geom), C.byref(n), C.byref(mt), C.byref(ov), stream),
                                "lsr_forward_status")
                     if ov.value or n.value != npairs.value:
                         raise LsrError(f"synchronous forward: device pair count {n.value} / overflow {ov.value} disagrees "
@@ -499,8 +492,8 @@ class _RasterizeViews(torch.autograd.Function):
         g_color = g_in(g_color) if (has_shs or has_cp) else None
         g_feat = g_in(g_feat) if has_f else None
         g_mask, g_depth = g_in(g_mask), g_in(g_depth)
-        inp = Inputs(_ptr(views), _ptr(means3D), _ptr(cov3D), _ptr(opacities),
-                     _ptr(color) if (has_shs or has_cp) else None, _ptr(features) if has_f else None)
+        inp = Inputs(ptr(views), ptr(means3D), ptr(cov3D), ptr(opacities),
+                     ptr(color) if (has_shs or has_cp) else None, ptr(features) if has_f else None)
         d_means = torch.empty_like(means3D)
         d_cov = torch.empty_like(cov3D)
         d_opac = torch.empty_like(opacities)
@@ -516,11 +509,11 @@ class _RasterizeViews(torch.autograd.Function):
                 d = Dims.from_buffer_copy(d)
                 d.forward_flags &= ~_lib.FWD_CLEARS_GRAD
             gradws = torch.empty(lib.lsr_grad_workspace_bytes(C.byref(d)), dtype=torch.uint8, device=dev)
-        gout = OutGrads(_ptr(g_color), _ptr(g_feat), _ptr(g_mask), _ptr(g_depth))
-        fwd = Outputs(_ptr(f_color) if f_color.numel() else None, _ptr(f_feat) if f_feat.numel() else None,
-                      None, _ptr(f_depth), None)
-        gin = InGrads(_ptr(d_means), _ptr(d_cov), _ptr(d_opac), _ptr(d_color), _ptr(d_feat), _ptr(d_m2d))
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        gout = OutGrads(ptr(g_color), ptr(g_feat), ptr(g_mask), ptr(g_depth))
+        fwd = Outputs(ptr(f_color) if f_color.numel() else None, ptr(f_feat) if f_feat.numel() else None,
+                      None, ptr(f_depth), None)
+        gin = InGrads(ptr(d_means), ptr(d_cov), ptr(d_opac), ptr(d_color), ptr(d_feat), ptr(d_m2d))
+        stream = _args.stream(dev)
         d_views = None
         with torch.cuda.device(dev):
             if ctx.needs_input_grad[0]:
@@ -528,14 +521,13 @@ class _RasterizeViews(torch.autograd.Function):
                 # fixed-order reduction of their partial records
                 d_views = torch.empty((V, _lib.VIEW_FLOATS), **f32)
                 vgws = torch.empty(lib.lsr_view_grad_workspace_bytes(C.byref(d)), dtype=torch.uint8, device=dev)
-                _lib.check(lib.lsr_backward_views(C.byref(d), C.byref(inp), _ptr(plan.geom), _ptr(plan.bin),
-                                                  _ptr(plan.img), plan.num_pairs, _ptr(plan.radii), C.byref(fwd),
-                                                  C.byref(gout), _ptr(gradws), C.byref(gin), _ptr(d_views), _ptr(vgws),
-                                                  stream), "lsr_backward_views")
+                _lib.check(lib.lsr_backward_views(C.byref(d), C.byref(inp), ptr(plan.geom), ptr(plan.bin), ptr(plan.img),
+                                                  plan.num_pairs, ptr(plan.radii), C.byref(fwd), C.byref(gout), ptr(gradws),
+                                                  C.byref(gin), ptr(d_views), ptr(vgws), stream), "lsr_backward_views")
             else:
-                _lib.check(lib.lsr_backward(C.byref(d), C.byref(inp), _ptr(plan.geom), _ptr(plan.bin),
-                                            _ptr(plan.img), plan.num_pairs, _ptr(plan.radii), C.byref(fwd),
-                                            C.byref(gout), _ptr(gradws), C.byref(gin), stream), "lsr_backward")
+                _lib.check(lib.lsr_backward(C.byref(d), C.byref(inp), ptr(plan.geom), ptr(plan.bin), ptr(plan.img),
+                                            plan.num_pairs, ptr(plan.radii), C.byref(fwd), C.byref(gout), ptr(gradws),
+                                            C.byref(gin), stream), "lsr_backward")
             if ctx.debug:
                 torch.cuda.synchronize(dev)
         if not want_m2d:
@@ -603,13 +595,12 @@ def last_forward_status() -> dict:
         return dict(_LAST_STATUS)
     if _LAST_PLAN is None:
         raise LsrError("no forward has run yet")
-    lib = _lib.load()
     plan = _LAST_PLAN
     dev = plan.geom.device
     n, mt, ov = C.c_int64(0), C.c_int32(0), C.c_int32(0)
     with torch.cuda.device(dev):
-        _lib.check(lib.lsr_forward_status(C.byref(plan.dims), _ptr(plan.geom), C.byref(n), C.byref(mt), C.byref(ov),
-                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "lsr_forward_status")
+        _lib.call("lsr_forward_status", C.byref(plan.dims), ptr(plan.geom), C.byref(n), C.byref(mt), C.byref(ov),
+                  _args.stream(dev))
     return dict(num_pairs=n.value, max_tile_pairs=mt.value, overflow=bool(ov.value))
 
 
@@ -654,7 +645,6 @@ def _pack_view_dev(rs: GaussianRasterizationSettings, dev) -> Tensor:
     if dev.type != "cuda":
         raise LsrError("latentsplat_amd rasterizer runs on MI355X only: tensors must be on a ROCm ('cuda') device; "
                        "there is no CPU fallback")
-    lib = _lib.load()
     f = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
     vm, pm, cp, bg = f(rs.viewmatrix), f(rs.projmatrix), f(rs.campos), f(rs.bg)
     tx, ty = rs.tanfovx, rs.tanfovy
@@ -662,9 +652,8 @@ def _pack_view_dev(rs: GaussianRasterizationSettings, dev) -> Tensor:
     tyd = f(ty).reshape(-1) if torch.is_tensor(ty) else None
     out = torch.empty((1, _lib.VIEW_FLOATS), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(lib.lsr_pack_view(_ptr(vm), _ptr(pm), _ptr(cp), _ptr(bg), 0.0 if txd is not None else float(tx),
-                                     0.0 if tyd is not None else float(ty), _ptr(txd), _ptr(tyd), _ptr(out),
-                                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "lsr_pack_view")
+        _lib.call("lsr_pack_view", ptr(vm), ptr(pm), ptr(cp), ptr(bg), 0.0 if txd is not None else float(tx),
+                  0.0 if tyd is not None else float(ty), ptr(txd), ptr(tyd), ptr(out), _args.stream(dev))
     return out
 
 

@@ -22,20 +22,12 @@ from typing import Optional, Sequence
 import torch
 from torch import Tensor, nn
 
-from . import _lib
+from . import _args, _lib
+from ._args import ptr
 from .ply_import import Scene3DGS, read_header
 
 _FORWARD_OUTPUTS = ("shs", "opacities", "cov3D", "scales", "rotations")
 _PARAMS = ("features_dc", "features_rest", "opacity", "scaling", "rotation")
-
-
-def _ptr(t: Optional[Tensor]) -> C.c_void_p:
-    return C.c_void_p(None if t is None or t.numel() == 0 else t.data_ptr())
-
-
-def _quad(t: Tensor) -> Tensor:
-    """(the kernels move a quaternion as one 16-byte quad)"""
-    return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
 def _prepare(features_dc: Tensor, features_rest: Tensor, opacity: Tensor, scaling: Tensor, rotation: Tensor):
@@ -56,7 +48,7 @@ def _prepare(features_dc: Tensor, features_rest: Tensor, opacity: Tensor, scalin
     if len({t.device for t in given}) != 1:
         raise _lib.LsrError("the scene's tensors must be on one device")
     dc, rest, op, sc, rot = (t.detach().contiguous() for t in given)
-    return (dc, rest, op, sc, _quad(rot)), n, K
+    return (dc, rest, op, sc, _args.quad(rot)), n, K
 
 
 def _filter(filter_3d, n: int, dev) -> Optional[Tensor]:
@@ -89,22 +81,19 @@ def activate_forward(features_dc: Tensor, features_rest: Tensor, opacity: Tensor
     unknown = [k for k in (want or ()) if k not in shapes]
     if unknown:
         raise _lib.LsrError(f"unknown outputs {unknown}; expected some of {list(shapes)}")
-    lib = _lib.load()
     dev = params[0].device
     out = {k: torch.empty(s, dtype=torch.float32, device=dev) for k, s in shapes.items() if want is None or k in want}
     if n == 0:
         return out
-    ptrs = _lib.SceneOutputs(**{k: _ptr(t) for k, t in out.items()})
+    ptrs = _lib.SceneOutputs(**{k: ptr(t) for k, t in out.items()})
     with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _args.stream(dev)
         if filt is None:
-            _lib.check(lib.lsr_scene_activate_forward(C.byref(_dims(n, K, scale_modifier)),
-                                                      C.byref(_lib.SceneParams(*map(_ptr, params))), C.byref(ptrs), stream),
-                       "lsr_scene_activate_forward")
+            _lib.call("lsr_scene_activate_forward", C.byref(_dims(n, K, scale_modifier)),
+                      C.byref(_lib.SceneParams(*map(ptr, params))), C.byref(ptrs), stream)
         else:
-            _lib.check(lib.lsr_scene_activate_filtered_forward(C.byref(_dims(n, K, scale_modifier)),
-                                                               C.byref(_lib.SceneParams(*map(_ptr, params))), _ptr(filt),
-                                                               C.byref(ptrs), stream), "lsr_scene_activate_filtered_forward")
+            _lib.call("lsr_scene_activate_filtered_forward", C.byref(_dims(n, K, scale_modifier)),
+                      C.byref(_lib.SceneParams(*map(ptr, params))), ptr(filt), C.byref(ptrs), stream)
     return out
 
 
@@ -128,23 +117,20 @@ def activate_backward(features_dc: Tensor, features_rest: Tensor, opacity: Tenso
                 raise _lib.LsrError(f"the gradient of {name} must be a float32 ROCm tensor of shape {shape} on the scene's device")
             g = g.detach().contiguous()
         ups.append(g)
-    lib = _lib.load()
     out = {k: torch.empty_like(t) for k, t in zip(_PARAMS, params) if want is None or k in want}
     if n == 0:
         return out
-    grads = _lib.SceneInGrads(**{k: _ptr(t) for k, t in out.items()})
+    grads = _lib.SceneInGrads(**{k: ptr(t) for k, t in out.items()})
     with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _args.stream(dev)
         if filt is None:
-            _lib.check(lib.lsr_scene_activate_backward(C.byref(_dims(n, K, scale_modifier)),
-                                                       C.byref(_lib.SceneParams(*map(_ptr, params))),
-                                                       C.byref(_lib.SceneOutGrads(*map(_ptr, ups))), C.byref(grads), stream),
-                       "lsr_scene_activate_backward")
+            _lib.call("lsr_scene_activate_backward", C.byref(_dims(n, K, scale_modifier)),
+                      C.byref(_lib.SceneParams(*map(ptr, params))), C.byref(_lib.SceneOutGrads(*map(ptr, ups))),
+                      C.byref(grads), stream)
         else:
-            _lib.check(lib.lsr_scene_activate_filtered_backward(C.byref(_dims(n, K, scale_modifier)),
-                                                                C.byref(_lib.SceneParams(*map(_ptr, params))), _ptr(filt),
-                                                                C.byref(_lib.SceneOutGrads(*map(_ptr, ups))), C.byref(grads),
-                                                                stream), "lsr_scene_activate_filtered_backward")
+            _lib.call("lsr_scene_activate_filtered_backward", C.byref(_dims(n, K, scale_modifier)),
+                      C.byref(_lib.SceneParams(*map(ptr, params))), ptr(filt),
+                      C.byref(_lib.SceneOutGrads(*map(ptr, ups))), C.byref(grads), stream)
     return out
 
 
@@ -276,11 +262,9 @@ class GaussianScene(nn.Module):
         lie in [0, 1] stores probabilities, as this project's viewer export ``export_ply`` writes them, and is refused
         (``check_opacity=False`` takes the values as logits regardless)."""
         device = torch.device(device)
-        lib = _lib.load()
         layout = read_header(path)
         host = torch.empty((layout.n, layout.stride), dtype=torch.float32, pin_memory=device.type == "cuda")
-        _lib.check(lib.lsr_ply_read_rows(os.fsencode(str(path)), C.c_void_p(host.data_ptr()), host.numel()),
-                   "lsr_ply_read_rows")
+        _lib.call("lsr_ply_read_rows", os.fsencode(str(path)), C.c_void_p(host.data_ptr()), host.numel())
         if check_opacity and layout.n > 0:
             o = host[:, layout.opacity]
             if float(o.min()) >= 0.0 and float(o.max()) <= 1.0:
@@ -527,5 +511,5 @@ class GaussianScene(nn.Module):
             rows = parameters_to_rows(self._xyz, self._features_dc, self._features_rest, opacity, scaling, self._rotation).cpu()
         path = Path(path)
         path.parent.mkdir(exist_ok=True, parents=True)
-        _lib.check(_lib.load().lsr_ply_write_scene_host(os.fsencode(str(path)), C.c_void_p(rows.data_ptr()), rows.shape[0],
-                                                        (self.max_sh_degree + 1) ** 2), "lsr_ply_write_scene_host")
+        _lib.call("lsr_ply_write_scene_host", os.fsencode(str(path)), C.c_void_p(rows.data_ptr()), rows.shape[0],
+                  (self.max_sh_degree + 1) ** 2)

@@ -16,17 +16,10 @@ from typing import Optional
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _args, _lib
+from ._args import ptr
 
 _COEFFS = (1, 4, 9, 16, 25)
-
-
-def _ptr(t: Optional[Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream(t: Tensor):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 def _need_rocm(*tensors: Optional[Tensor]):
@@ -50,8 +43,7 @@ def sh_rotation_matrices(rotations: Tensor, degree: int) -> Tensor:
     rotations = rotations.detach().contiguous()
     num, side = rotations.shape[0], rotations.shape[1]
     tables = torch.empty((num, _lib.sh_rotate_table_floats(degree)), device=rotations.device)
-    _lib.check(_lib.load().lsr_sh_rotation_matrices(num, _ptr(rotations), side, side * side, degree, _ptr(tables),
-                                                    _stream(rotations)), "lsr_sh_rotation_matrices")
+    _lib.call("lsr_sh_rotation_matrices", num, ptr(rotations), side, side * side, degree, ptr(tables), _args.stream(rotations))
     return tables
 
 
@@ -87,9 +79,8 @@ class _ShRotate(torch.autograd.Function):
         dev = rows.device
         color = torch.empty((cams, rays, samples, 3, color_coeffs), device=dev) if color_coeffs else None
         feature = torch.empty((cams, rays, samples, feat_channels, feat_coeffs), device=dev) if feat_coeffs else None
-        _lib.check(_lib.load().lsr_sh_rotate_forward(C.byref(dims), _ptr(tables), _ptr(rows), _ptr(color_mask),
-                                                     _ptr(feature_mask), _ptr(color), _ptr(feature), _stream(rows)),
-                   "lsr_sh_rotate_forward")
+        _lib.call("lsr_sh_rotate_forward", C.byref(dims), ptr(tables), ptr(rows), ptr(color_mask), ptr(feature_mask),
+                  ptr(color), ptr(feature), _args.stream(rows))
         ctx.save_for_backward(tables, color_mask, feature_mask)
         ctx.dims = dims
         ctx.set_materialize_grads(False)
@@ -105,9 +96,8 @@ class _ShRotate(torch.autograd.Function):
         g_color = None if g_color is None else g_color.contiguous()
         g_feature = None if g_feature is None else g_feature.contiguous()
         d_rows = torch.empty((dims.num_cameras, dims.rays, width), device=tables.device)
-        _lib.check(_lib.load().lsr_sh_rotate_backward(C.byref(dims), _ptr(tables), _ptr(g_color), _ptr(g_feature),
-                                                      _ptr(color_mask), _ptr(feature_mask), _ptr(d_rows),
-                                                      _stream(tables)), "lsr_sh_rotate_backward")
+        _lib.call("lsr_sh_rotate_backward", C.byref(dims), ptr(tables), ptr(g_color), ptr(g_feature), ptr(color_mask),
+                  ptr(feature_mask), ptr(d_rows), _args.stream(tables))
         return d_rows, None, None, None, None, None, None, None
 
 

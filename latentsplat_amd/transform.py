@@ -27,7 +27,8 @@ from typing import Optional
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _args, _lib
+from ._args import ptr
 
 _NAMES = ("xyz", "features_rest", "scaling", "rotation")
 SIMILARITY_TOLERANCE = 1e-5
@@ -124,10 +125,6 @@ def _matrices(M, check: bool) -> Tensor:
     return M
 
 
-def _ptr(t: Optional[Tensor]) -> C.c_void_p:
-    return C.c_void_p(None if t is None or t.numel() == 0 else t.data_ptr())
-
-
 def transform_records(M: Tensor, degree: int, adjoint: bool = False, check: bool = True) -> Tensor:
     """``lsr_transform_records``: the per-transform constants ``(T, LSR_TRANSFORM_RECORD_FLOATS(degree))`` the kernel reads,
     from similarities ``M (4, 4)`` or ``(T, 4, 4)`` on a ROCm device (any float dtype; the kernel reads float32).  A record
@@ -145,11 +142,8 @@ def transform_records(M: Tensor, degree: int, adjoint: bool = False, check: bool
     M = M.to(torch.float32).contiguous()
     T = M.shape[0]
     out = torch.empty((T, _lib.transform_record_floats(int(degree))), dtype=torch.float32, device=M.device)
-    lib = _lib.load()
     with torch.cuda.device(M.device):
-        stream = C.c_void_p(torch.cuda.current_stream(M.device).cuda_stream)
-        _lib.check(lib.lsr_transform_records(T, _ptr(M), int(degree), 1 if adjoint else 0, _ptr(out), stream),
-                   "lsr_transform_records")
+        _lib.call("lsr_transform_records", T, ptr(M), int(degree), 1 if adjoint else 0, ptr(out), _args.stream(M))
     return out
 
 
@@ -167,13 +161,12 @@ def apply_records(records: Tensor, idx: Optional[Tensor], inputs: dict, outputs:
     if n == 0:
         return
     dims = _lib.TransformDims(n=n, sh_coeffs=K, num_transforms=records.shape[0], reserved0=0, reserved1=0)
-    tin = _lib.TransformIn(**{k: _ptr(inputs.get(k)) for k in _NAMES})
-    tout = _lib.TransformOut(**{k: _ptr(outputs.get(k)) for k in _NAMES})
+    tin = _lib.TransformIn(**{k: ptr(inputs.get(k)) for k in _NAMES})
+    tout = _lib.TransformOut(**{k: ptr(outputs.get(k)) for k in _NAMES})
     dev = records.device
     with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(_lib.load().lsr_scene_transform(C.byref(dims), _ptr(records), _ptr(idx), C.byref(tin), C.byref(tout), stream),
-                   "lsr_scene_transform")
+        stream = _args.stream(dev)
+        _lib.call("lsr_scene_transform", C.byref(dims), ptr(records), ptr(idx), C.byref(tin), C.byref(tout), stream)
 
 
 def _check_scene(xyz: Tensor, features_rest: Tensor, scaling: Tensor, rotation: Tensor):
@@ -194,11 +187,6 @@ def _check_scene(xyz: Tensor, features_rest: Tensor, scaling: Tensor, rotation: 
     return n, K
 
 
-def _quad(t: Tensor) -> Tensor:
-    """(the kernel moves a quaternion as one 16-byte quad)"""
-    return t if t.data_ptr() % 16 == 0 else t.clone()
-
-
 class _TransformScene(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, features_rest, scaling, rotation, matrices, idx):
@@ -206,7 +194,7 @@ class _TransformScene(torch.autograd.Function):
         n, K = xyz.shape[0], features_rest.shape[1] + 1
         records = transform_records(matrices, isqrt(K) - 1, check=False)
         ins = dict(xyz=xyz.detach().contiguous(), features_rest=features_rest.detach().contiguous(),
-                   scaling=scaling.detach().contiguous(), rotation=_quad(rotation.detach().contiguous()))
+                   scaling=scaling.detach().contiguous(), rotation=_args.quad(rotation.detach().contiguous()))
         outs = {k: torch.empty_like(t) for k, t in ins.items()}
         apply_records(records, idx, ins, outs, n, K)
         # the backward's constants are fixed here, from the matrices the forward used (one more small launch, none later)
@@ -222,7 +210,7 @@ class _TransformScene(torch.autograd.Function):
         for k, need, g in zip(_NAMES, ctx.needs_input_grad, grads):
             if need and g is not None:
                 g = g.detach().contiguous()
-                ins[k] = _quad(g) if k == "rotation" else g
+                ins[k] = _args.quad(g) if k == "rotation" else g
                 outs[k] = torch.empty_like(g)
         if outs:
             records, idx = ctx.saved_tensors

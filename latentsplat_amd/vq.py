@@ -22,7 +22,8 @@ from typing import Optional, Tuple
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _args, _lib
+from ._args import ptr
 
 MAX_DIM, MAX_CODES, MAX_ROWS = _lib.VQ_MAX_DIM, _lib.VQ_MAX_CODES, _lib.VQ_MAX_ROWS
 
@@ -50,22 +51,13 @@ def _vector(t: Tensor, x: Tensor, dtype, what: str) -> Tensor:
     return t.detach().contiguous()
 
 
-def _ptr(t: Optional[Tensor]) -> C.c_void_p:
-    return C.c_void_p(None if t is None else t.data_ptr())
-
-
-def _workspace(n: int, k: int, d: int, dev) -> Tensor:
-    return torch.empty(_lib.load().lsr_vq_workspace_bytes(n, k, d), dtype=torch.uint8, device=dev)
-
-
 def _assign(x: Tensor, c: Tensor, idx: Tensor, dist2: Optional[Tensor], ws: Tensor) -> None:
     n, d = x.shape
     if n == 0:
         return
     dims = _lib.VqDims(n=n, k=c.shape[0], d=d)
     with torch.cuda.device(x.device):
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        _lib.check(_lib.load().lsr_vq_assign(C.byref(dims), _ptr(x), _ptr(c), _ptr(idx), _ptr(dist2), _ptr(ws), stream), "lsr_vq_assign")
+        _lib.call("lsr_vq_assign", C.byref(dims), ptr(x), ptr(c), ptr(idx), ptr(dist2), ptr(ws), _args.stream(x))
 
 
 def _update(x: Tensor, idx: Tensor, w: Optional[Tensor], prev: Tensor, out: Tensor, mass: Tensor, ws: Tensor) -> None:
@@ -76,9 +68,8 @@ def _update(x: Tensor, idx: Tensor, w: Optional[Tensor], prev: Tensor, out: Tens
         return
     dims = _lib.VqDims(n=n, k=prev.shape[0], d=d)
     with torch.cuda.device(x.device):
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        _lib.check(_lib.load().lsr_vq_update(C.byref(dims), _ptr(x), _ptr(idx), _ptr(w), _ptr(prev), _ptr(out), _ptr(mass), _ptr(ws), stream),
-                   "lsr_vq_update")
+        _lib.call("lsr_vq_update", C.byref(dims), ptr(x), ptr(idx), ptr(w), ptr(prev), ptr(out), ptr(mass), ptr(ws),
+                  _args.stream(x))
 
 
 def vq_assign(x: Tensor, codebook: Tensor, want_dist: bool = False):
@@ -91,7 +82,7 @@ def vq_assign(x: Tensor, codebook: Tensor, want_dist: bool = False):
     n, dev = x.shape[0], x.device
     idx = torch.empty((n,), dtype=torch.int32, device=dev)
     dist2 = torch.empty((n,), dtype=torch.float32, device=dev) if want_dist else None
-    _assign(x, c, idx, dist2, _workspace(n, c.shape[0], x.shape[1], dev))
+    _assign(x, c, idx, dist2, _args.workspace(_lib.load().lsr_vq_workspace_bytes(n, c.shape[0], x.shape[1]), dev))
     return (idx, dist2) if want_dist else idx
 
 
@@ -105,7 +96,8 @@ def vq_update(x: Tensor, idx: Tensor, prev_codebook: Tensor, weights: Optional[T
     idx = _vector(idx, x, torch.int32, "idx")
     w = None if weights is None else _vector(weights, x, torch.float32, "weights")
     out, mass = torch.empty_like(prev), torch.empty((prev.shape[0],), dtype=torch.float32, device=x.device)
-    _update(x, idx, w, prev, out, mass, _workspace(x.shape[0], prev.shape[0], x.shape[1], x.device))
+    ws = _args.workspace(_lib.load().lsr_vq_workspace_bytes(x.shape[0], prev.shape[0], x.shape[1]), x.device)
+    _update(x, idx, w, prev, out, mass, ws)
     return out, mass
 
 
@@ -133,7 +125,7 @@ def kmeans(x: Tensor, k: int, iters: int = 10, weights: Optional[Tensor] = None,
         perm = torch.randperm(n, generator=generator, device=generator.device if generator is not None else "cpu")
         code = x.index_select(0, perm.to(dev)[torch.arange(k, device=dev) % n])
     idx = torch.empty((n,), dtype=torch.int32, device=dev)
-    ws = _workspace(n, k, d, dev)
+    ws = _args.workspace(_lib.load().lsr_vq_workspace_bytes(n, k, d), dev)
     other, mass = torch.empty_like(code), torch.empty((k,), dtype=torch.float32, device=dev)
     for _ in range(int(iters)):
         _assign(x, code, idx, None, ws)

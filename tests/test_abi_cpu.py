@@ -30,6 +30,21 @@ def test_header_symbols_are_exported():
     assert lib.lsr_abi_version() == 10
 
 
+def test_every_export_has_a_prototype():
+    """One table (``_lib.PROTOTYPES``) binds the library: every declared name is in it with an explicit restype, ``load()``
+    binds exactly that, and the sizing functions return ``size_t`` (ctypes' default ``int`` would truncate them)."""
+    lib = _lib.load()
+    assert set(_declared()) <= set(_lib.PROTOTYPES)
+    for name, (restype, argtypes) in _lib.PROTOTYPES.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype, name
+        assert (fn.argtypes is None) if argtypes is None else (list(fn.argtypes) == list(argtypes)), name
+        if name.endswith("_workspace_bytes"):
+            assert restype is C.c_size_t, name
+    assert sum(name.endswith("_workspace_bytes") for name in _lib.PROTOTYPES) >= 12
+    assert _lib.PROTOTYPES["lsr_profile_enable"][0] is None           # void in C
+
+
 def _dims(**kw):
     base = dict(num_views=2, num_gaussians=1000, height=64, width=64, feat_channels=4, color_mode=0,
                 sh_degree=0, sh_coeffs=0, vs_means=0, vs_cov=0, vs_opac=0, vs_color=0, vs_feat=0,

@@ -646,3 +646,20 @@ def test_more_than_2_to_24_gaussians_run_without_footprint_culling(hip_device):
     util.assert_grad_close_except_fragile(feats.grad.cpu().numpy(), b["features"], direct, behind_px, 1e-4, "dL/dfeatures (> 2^24 Gaussians)", clean_tol=2e-5)
     util.assert_grad_close_except_fragile(opac.grad.cpu().numpy(), b["opacities"][:, None], direct, behind_px, 1e-4, "dL/dopacities (> 2^24 Gaussians)", clean_tol=2e-5)
     assert float(means.grad[:pad].abs().max()) == 0.0
+
+
+def test_argument_helpers_on_a_rocm_device(hip_device):
+    """What latentsplat_amd/_args.py relies on: torch reports address 0 for a ROCm tensor without elements (so ``ptr`` hands
+    the library NULL for it either way), and ``stream`` is the handle of the stream that is current when it is called."""
+    from latentsplat_amd import _args
+    dev = hip_device
+    full = torch.zeros(8, device=dev)
+    for empty in (torch.empty(0, device=dev), full[8:], torch.zeros((3, 0), device=dev)):
+        assert empty.data_ptr() == 0 and _args.ptr(empty).value is None
+    assert _args.ptr(full).value == full.data_ptr() != 0
+    handle = lambda s: s.value or 0                                      # (ctypes reads a NULL handle, the default stream's, back as None)
+    side = torch.cuda.Stream(device=dev)
+    assert handle(_args.stream(dev)) == handle(_args.stream(full)) == torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.stream(side):
+        assert handle(_args.stream(dev)) == handle(_args.stream(full)) == side.cuda_stream != 0
+    assert handle(_args.stream(dev)) == torch.cuda.current_stream(dev).cuda_stream

@@ -8,14 +8,14 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "latentsplat_amd", "csrc")
-FLAGS = {"preprocess": ["-ffp-contract=off"], "sh": ["-ffp-contract=off"]}   # per-unit flags of csrc/Makefile (COMMON is spelled out below)
 
 
 def main():
     unit = sys.argv[1]
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I../../include", "-I.", "-fno-fast-math", "-fno-slp-vectorize",
-           "-Rpass-analysis=kernel-resource-usage", "-c", unit + ".hip", "-o", "/dev/null"] + FLAGS.get(unit, []) + sys.argv[2:]
-    err = subprocess.run(cmd, cwd=CSRC, stderr=subprocess.PIPE, text=True).stderr
+    # csrc/Makefile knows the unit's flags: its device-assembly rule with the remark switched on (writes UNIT.device.s there)
+    extra = " ".join(["-Rpass-analysis=kernel-resource-usage"] + sys.argv[2:])
+    err = subprocess.run(["make", "-B", unit + ".device.s", "EXTRA=" + extra], cwd=CSRC, stdout=subprocess.DEVNULL,
+                         stderr=subprocess.PIPE, text=True).stderr
     rows, cur = [], None
     for line in err.splitlines():
         m = re.search(r"remark: [^:]*:\d+:\d+:\s+(.*?) \[-Rpass", line) or re.search(r"remark:\s+(.*?) \[-Rpass", line)
