@@ -172,7 +172,19 @@ typedef struct lsr_dims {
                                (ABI v10) bit 3, LSR_FWD_FRONT_DONE: lsr_forward_front has already launched the front half of
                                this forward (below); only lsr_forward_nosync / lsr_forward_speculative read it, every other
                                call ignores it.
-                               Other bits must be 0 (LSR_EINVAL). */
+                               Bit 5, LSR_FWD_ANTIALIAS: opacity compensation for the 0.3 low-pass (the screen-space half of
+                               Mip-Splatting; `antialiasing` of the published rasterizer).  With a0, b, c0 the projected 2D
+                               covariance before the low-pass and det the determinant after it, the opacity every stage
+                               behind the projection sees — slot 5 of the screen record, the alpha >= 1/255 footprint,
+                               the compositing — is o' = o * sqrt(max(0.000025, (a0 c0 - b^2) / det)), so the dilated splat
+                               emits the light of the undilated one (at least 0.005 of it).  Conic, radii, tile rectangles,
+                               depth keys and the canonical lists are those of the classic mode bit for bit; with
+                               LSR_FWD_REACHED_ONLY the reduced lists follow the smaller footprints.  lsr_backward /
+                               lsr_backward_views handed the bit return dL/do = rho dL/do' and add rho's dependence on the
+                               covariance, the mean and the view record (none where the floor holds).  Accepted with
+                               every dims the classic mode accepts; no layout changes (the ABI version stays 10).  Hand the
+                               same value to every call of a forward and to its backward.
+                               Bit 4 is reserved; it and all other bits must be 0 (LSR_EINVAL). */
     int32_t seg_cap_hint;   /* (ABI v9) 0, or the longest tile list (in (Gaussian, tile) pairs) the caller expects — e.g. the
                                `max_tile_pairs` of an earlier call of the same shape plus a margin.  Sizes the per-(view, tile)
                                key segments of the single-pass binning, which are REAL device memory at the end of geom_ws
@@ -185,6 +197,7 @@ typedef struct lsr_dims {
 #define LSR_FWD_CLEARS_GRAD 2
 #define LSR_FWD_REACHED_ONLY 4
 #define LSR_FWD_FRONT_DONE 8
+#define LSR_FWD_ANTIALIAS 32
 
 typedef struct lsr_inputs {
     const float *views;      /* [V][LSR_VIEW_FLOATS] */

@@ -24,6 +24,7 @@ FWD_FOR_BACKWARD = 1                      # lsr_dims.forward_flags
 FWD_CLEARS_GRAD = 2
 FWD_REACHED_ONLY = 4
 FWD_FRONT_DONE = 8      # (ABI v10) lsr_forward_front has launched the front half of this forward
+FWD_ANTIALIAS = 32      # opacity compensation for the 0.3 low-pass (bit 4 is reserved)
 MAX_SH_GROUP_FLOATS = 120   # C*Kf the fused latent-SH path supports (LDS budget of sh.hip)
 MAX_FEAT_CHANNELS = 32
 

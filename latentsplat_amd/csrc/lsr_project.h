@@ -60,6 +60,7 @@ struct Projected {
     float tz;                             // view-space depth (the sort key's bits)
     float radius;                         // ceil(3 sigma_max), pixels
     int rminx, rminy, rmaxx, rmaxy;       // tile rectangle [min, max)
+    float rho;                            // AA instances only: the opacity compensation of the low-pass (below)
 };
 
 // vm / pm: the view and projection matrices of the camera table (memory = transposed matrices); (p0, p1, p2): the mean
@@ -67,7 +68,13 @@ struct Projected {
 // ONE visibility predicate instead of nested early exits (each exit level made the compiler re-materialise the zeroed
 // outputs): culled lanes run the arithmetic on whatever they hold (IEEE special values are harmless here) and are
 // masked where results leave the thread.
-template <bool FMA>
+// AA (LSR_FWD_ANTIALIAS): also rho = sqrt(max(0.000025, det0 / det)), det0 the determinant of the covariance BEFORE the
+// low-pass: what the dilation by 0.3 takes from the splat's peak so that its integral stays the undilated one (the
+// screen-space half of Mip-Splatting; the published rasterizer's `antialiasing`, floor included: rho >= 0.005).  det0 is
+// formed from the undilated diagonal itself — det - 0.3 (a + c) + 0.09 cancels to percents for the sub-pixel splats the mode
+// is for — in the FMA convention of det.  Nothing else of the projection depends on AA: the instances without it are the
+// code they were, and the instances with it produce the same conic, radius, rectangle and depth bits.
+template <bool FMA, bool AA = false>
 __device__ __forceinline__ Projected project_gaussian(const float (&vm)[16], const float (&pm)[16], float limx, float limy,
                                                       float focal_x, float focal_y, float p0, float p1, float p2,
                                                       float s0, float s1, float s2, float s3, float s4, float s5,
@@ -101,10 +108,16 @@ __device__ __forceinline__ Projected project_gaussian(const float (&vm)[16], con
     const float v10 = dot3<FMA>(s0, m10, s1, m11, s2, m12);
     const float v11 = dot3<FMA>(s1, m10, s3, m11, s4, m12);
     const float v12 = dot3<FMA>(s2, m10, s4, m11, s5, m12);
-    const float ca = dot3<FMA>(m00, v00, m01, v01, m02, v02) + LSR_LOWPASS;
+    const float ca0 = dot3<FMA>(m00, v00, m01, v01, m02, v02);
     const float cb = dot3<FMA>(m00, v10, m01, v11, m02, v12);
-    const float cc = dot3<FMA>(m10, v10, m11, v11, m12, v12) + LSR_LOWPASS;
+    const float cc0 = dot3<FMA>(m10, v10, m11, v11, m12, v12);
+    const float ca = ca0 + LSR_LOWPASS, cc = cc0 + LSR_LOWPASS;
     const float det = FMA ? __builtin_fmaf(ca, cc, -(cb * cb)) : ca * cc - cb * cb;
+    if constexpr (AA) {
+        const float det0 = FMA ? __builtin_fmaf(ca0, cc0, -(cb * cb)) : ca0 * cc0 - cb * cb;
+        const float q = det0 / det;
+        r.rho = sqrtf(q > 0.000025f ? q : 0.000025f);   // (a NaN ratio takes the floor)
+    } else r.rho = 1.0f;
     ok = ok && !(det == 0.0f);
     const float det_inv = 1.0f / det;
     r.conic_a = cc * det_inv; r.conic_b = -cb * det_inv; r.conic_c = ca * det_inv;

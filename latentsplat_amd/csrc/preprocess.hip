@@ -36,7 +36,9 @@ constexpr int kPreItems = 8;  // (Gaussian, view) items per thread: 2048 per blo
 // k_scatter's body without its launch, without the machine-wide re-read of the records from HBM and without the wait
 // for the tile scan in front of it; the order of the keys inside a segment is whatever the atomics produce, as before
 // (k_sort_tiles sorts distinct 64-bit keys).
-template <int COLOR_MODE, bool LDS_HIST, int VB, bool FMA, bool SEG>
+// AA (LSR_FWD_ANTIALIAS): the opacity of the screen record and of the footprint is opacity * rho (lsr_project.h); instances
+// of their own, so the ones without it keep their code and their 80 registers.
+template <int COLOR_MODE, bool LDS_HIST, int VB, bool FMA, bool SEG, bool AA = false>
 __global__ void __launch_bounds__(kPreThreads, 6)   // six waves per SIMD (80 VGPRs): the kernel streams, occupancy hides its latencies
 k_preprocess(lsr_dims d, lsr_inputs in, float *__restrict__ rec, int RF, char *__restrict__ binrec, int narrow,
              int32_t *__restrict__ radii, uint32_t *__restrict__ tile_count, uint32_t *header, FoldedScan fs, int kItems, SegOut seg) {
@@ -132,11 +134,12 @@ k_preprocess(lsr_dims d, lsr_inputs in, float *__restrict__ rec, int RF, char *_
             const float p0 = q0 * scale, p1 = q1 * scale, p2 = q2 * scale;
             const float s0 = r0 * scale2, s1 = r1 * scale2, s2 = r2 * scale2;
             const float s3 = r3 * scale2, s4 = r4 * scale2, s5 = r5 * scale2;
-            const Projected pj = project_gaussian<FMA>(vm, pm, limx, limy, focal_x, focal_y, p0, p1, p2, s0, s1, s2, s3, s4, s5,
+            const Projected pj = project_gaussian<FMA, AA>(vm, pm, limx, limy, focal_x, focal_y, p0, p1, p2, s0, s1, s2, s3, s4, s5,
                                                        d.width, d.height, gx, gy, in_range);
             const bool ok = pj.ok;
             const float px = pj.px, py = pj.py, conic_a = pj.conic_a, conic_b = pj.conic_b, conic_c = pj.conic_c, tz = pj.tz;
             const float my_radius = pj.radius;
+            const float rec_opacity = AA ? opacity * pj.rho : opacity;   // what the compositing kernels and the footprint see
             const TileRect rect{pj.rminx, pj.rminy, pj.rmaxx, pj.rmaxy};
 
             // slot 6, what the compositing kernels blend into the depth image: the view z, or the view's depth mode applied
@@ -145,9 +148,9 @@ k_preprocess(lsr_dims d, lsr_inputs in, float *__restrict__ rec, int RF, char *_
             float zpay = tz;
             if (vw[41] != 0.0f) zpay = depth_mode_payload((int)vw[41], tz, scale, vw[42], vw[43]);
             const float4 rr0 = make_float4(px, py, conic_a, conic_b);
-            const float4 rr1 = make_float4(conic_c, opacity, ok ? zpay : -1.0f, 0.0f);   // a negative slot 6 marks a culled record (staging only)
+            const float4 rr1 = make_float4(conic_c, rec_opacity, ok ? zpay : -1.0f, 0.0f);   // a negative slot 6 marks a culled record (staging only)
             // footprint span for the half-tile render lists (k_scatter / k_sort_tiles); not part of the bit-exact contract
-            const uint32_t span = ok ? footprint_cells(px, py, conic_a, conic_b, conic_c, opacity, rect.x0, rect.y0) : kSpanNone;
+            const uint32_t span = ok ? footprint_cells(px, py, conic_a, conic_b, conic_c, rec_opacity, rect.x0, rect.y0) : kSpanNone;
             if (ok) {
                 if (!staged) {
                     float4 *R = (float4 *)(rec + o * (size_t)RF);
@@ -268,7 +271,9 @@ hipError_t launch_preprocess(const lsr_dims &d, const lsr_inputs &in, char *geom
         if (!lds || !narrow || L.seg_cap == 0) return hipErrorInvalidValue;
         so.keys = (uint64_t *)(geom + L.seg_keys); so.cap = L.seg_cap;
     }
-#define LSR_PRE4(CM, LH, VBV, FM, SG) hipLaunchKernelGGL((k_preprocess<CM, LH, VBV, FM, SG>), grid, dim3(kPreThreads), shm, s, d, in, rec, RF, binrec, narrow, radii, tc, (uint32_t *)(geom + L.header), fs, items, so)
+    const bool aa = (d.forward_flags & LSR_FWD_ANTIALIAS) != 0;
+#define LSR_PRE5(CM, LH, VBV, FM, SG, AAV) hipLaunchKernelGGL((k_preprocess<CM, LH, VBV, FM, SG, AAV>), grid, dim3(kPreThreads), shm, s, d, in, rec, RF, binrec, narrow, radii, tc, (uint32_t *)(geom + L.header), fs, items, so)
+#define LSR_PRE4(CM, LH, VBV, FM, SG) do { if (aa) LSR_PRE5(CM, LH, VBV, FM, SG, true); else LSR_PRE5(CM, LH, VBV, FM, SG, false); } while (0)
 #define LSR_PRE3(CM, LH, VBV, FM) do { if (LH && seg_mode) LSR_PRE4(CM, LH, VBV, FM, LH); else LSR_PRE4(CM, LH, VBV, FM, false); } while (0)
 #define LSR_PRE2(CM, LH, VBV) do { if (fma) LSR_PRE3(CM, LH, VBV, true); else LSR_PRE3(CM, LH, VBV, false); } while (0)
 #define LSR_PRE(CM)                                                                              \
@@ -284,6 +289,7 @@ hipError_t launch_preprocess(const lsr_dims &d, const lsr_inputs &in, char *geom
 #undef LSR_PRE2
 #undef LSR_PRE3
 #undef LSR_PRE4
+#undef LSR_PRE5
     prof_end(kStPreprocess, s);
     return hipGetLastError();
 }

@@ -53,7 +53,10 @@ constexpr int kPreBwdShared = 3 + 6 + 1 + kPreBwdFeat + 3;   // register accumul
 // stored as one partial record (lsr_internal.h kCam*); it stores nothing else.  (Folded into the plain instance, the extra
 // uses changed how the compiler contracted the Gaussian gradients — no longer bit for bit those of lsr_backward — and the
 // 32 live partial sums spilled inside the view loop.)  The plain instances are the code they were.
-template <int PARTS, bool FMA, bool CAM = false>
+// AA (forwards run with LSR_FWD_ANTIALIAS): the record's opacity was o' = o rho, rho^2 = det0 / det (lsr_project.h), so the
+// moment m0 = sum o' G dL/dalpha is also rho dL/drho, and rho's dependence on the 2D covariance joins dL/d(a, b, c) below.
+// Instances of their own again: the ones without it are the code they were.
+template <int PARTS, bool FMA, bool CAM = false, bool AA = false>
 __global__ void __launch_bounds__(kPreBwdThreads, 4)
 k_preprocess_bwd(PreBwdParams pk) {
     // view groups: blockIdx.y = group; its inputs, gradient outputs and workspace slices (uniform: scalar arithmetic)
@@ -103,6 +106,8 @@ k_preprocess_bwd(PreBwdParams pk) {
         if (pay16) { q0 = *(const float4 *)(rc + 8); q1 = *(const float4 *)(rc + 12); }
         // opacity: the record holds m0 = sum opacity * G * dL/dalpha; dL/dopacity = m0 / opacity
         // (m0 != 0 implies opacity >= 1/255)
+        // AA: m0 is taken with the record's o' = o rho, and dL/do = rho dL/do' = rho m0 / o' = m0 / o: the division by the
+        // INPUT opacity below, and the shared-opacity sum, are right as they stand.
         if constexpr (!CAM) {   // (the camera-gradient instance stores nothing but its partial records)
         if (d.vs_opac != 0) {
             const float o_in = p.in.opacities[(size_t)v * d.vs_opac + i];
@@ -205,9 +210,26 @@ k_preprocess_bwd(PreBwdParams pk) {
         const float gpy = -(cB * r0.x + cC * r0.y);
         const float d2 = det_inv * det_inv;
         // conic = (c, -b, a) / det
-        const float dL_da = d2 * (gcon.x * (-c * c) + gcon.y * (b * c) + gcon.z * (det - a * c));
-        const float dL_dc = d2 * (gcon.x * (det - a * c) + gcon.y * (a * b) + gcon.z * (-a * a));
-        const float dL_db = d2 * (gcon.x * (2.0f * b * c) - gcon.y * (det + 2.0f * b * b) + gcon.z * (2.0f * a * b));
+        float dL_da = d2 * (gcon.x * (-c * c) + gcon.y * (b * c) + gcon.z * (det - a * c));
+        float dL_dc = d2 * (gcon.x * (det - a * c) + gcon.y * (a * b) + gcon.z * (-a * a));
+        float dL_db = d2 * (gcon.x * (2.0f * b * c) - gcon.y * (det + 2.0f * b * b) + gcon.z * (2.0f * a * b));
+        if constexpr (AA) {
+            // rho^2 = det0 / det with det0 = a0 c0 - b^2 of the undilated diagonal (formed from it, as the forward does):
+            // dL/drho = m0 / rho, so dL/d(ln rho) = m0 and d(ln rho) = (d det0 / det0 - d det / det) / 2; a0, c0 have the
+            // derivatives of a, c.  Where the forward took the floor (det0 / det <= 0.000025, also det0 <= 0 or NaN) rho is a
+            // constant: nothing is added, and nothing of 1 / det0 is formed.  The decision is RECOMPUTED here (this unit's
+            // contracted det0, det0 * rcp(det)), not the forward's (its FMA convention, an IEEE division): within an ulp of the
+            // threshold the two can differ — a floored forward gets a term of its finite size, or the reverse.  Unlike the clamp
+            // of the Jacobian the term is continuous in the inputs there, only its derivative jumps, so no bits are kept for it.
+            const float a0 = MS[0][0] * M[0][0] + MS[0][1] * M[0][1] + MS[0][2] * M[0][2];
+            const float c0 = MS[1][0] * M[1][0] + MS[1][1] * M[1][1] + MS[1][2] * M[1][2];
+            const float det0 = a0 * c0 - b * b;
+            const bool rho_live = det_inv != 0.0f && det0 * det_inv > 0.000025f;   // (det_inv = 0: culled or singular)
+            const float i0 = rcp(rho_live ? det0 : 1.0f), m0 = r1.y;
+            dL_da += rho_live ? 0.5f * m0 * (c0 * i0 - c * det_inv) : 0.0f;
+            dL_dc += rho_live ? 0.5f * m0 * (a0 * i0 - a * det_inv) : 0.0f;
+            dL_db += rho_live ? m0 * b * (det_inv - i0) : 0.0f;
+        }
         // packed Sigma gradient: diagonal once, off-diagonals twice (stored once)
         float gm[3], gc[6];
         gc[0] = dL_da * M[0][0] * M[0][0] + dL_db * M[0][0] * M[1][0] + dL_dc * M[1][0] * M[1][0];
@@ -399,23 +421,18 @@ hipError_t launch_preprocess_backward(const lsr_dims &d_all, const lsr_inputs &i
     const int per_block = kPreBwdThreads / parts;   // Gaussians per block
     const dim3 grid((unsigned)((d.num_gaussians + per_block - 1) / per_block), (unsigned)num_view_groups(d_all));
     // the projection convention of the forward (lsr_set_projection_contraction): the clamp decision must be its own
+    const bool aa = (d.forward_flags & LSR_FWD_ANTIALIAS) != 0;   // the forward's flag word: its projection scaled the opacities
+#define LSR_PREBWD3(PT, FM, CM, AAV) hipLaunchKernelGGL((k_preprocess_bwd<PT, FM, CM, AAV>), grid, dim3(kPreBwdThreads), 0, s, p)
+#define LSR_PREBWD2(PT, FM, CM) do { if (aa) LSR_PREBWD3(PT, FM, CM, true); else LSR_PREBWD3(PT, FM, CM, false); } while (0)
+#define LSR_PREBWD(FM, CM) do { \
+        if (parts == 4) LSR_PREBWD2(4, FM, CM); else if (parts == 2) LSR_PREBWD2(2, FM, CM); else LSR_PREBWD2(1, FM, CM); } while (0)
     if (cam.part) {   // the camera gradient: a second launch over the same records (the plain instance follows below)
-#define LSR_PREBWD_CAM(FM) do { \
-            if (parts == 4) hipLaunchKernelGGL((k_preprocess_bwd<4, FM, true>), grid, dim3(kPreBwdThreads), 0, s, p); \
-            else if (parts == 2) hipLaunchKernelGGL((k_preprocess_bwd<2, FM, true>), grid, dim3(kPreBwdThreads), 0, s, p); \
-            else hipLaunchKernelGGL((k_preprocess_bwd<1, FM, true>), grid, dim3(kPreBwdThreads), 0, s, p); } while (0)
-        if (projection_contraction()) LSR_PREBWD_CAM(true); else LSR_PREBWD_CAM(false);
-#undef LSR_PREBWD_CAM
+        if (projection_contraction()) LSR_PREBWD(true, true); else LSR_PREBWD(false, true);
     }
-    if (projection_contraction()) {
-        if (parts == 4) hipLaunchKernelGGL((k_preprocess_bwd<4, true>), grid, dim3(kPreBwdThreads), 0, s, p);
-        else if (parts == 2) hipLaunchKernelGGL((k_preprocess_bwd<2, true>), grid, dim3(kPreBwdThreads), 0, s, p);
-        else hipLaunchKernelGGL((k_preprocess_bwd<1, true>), grid, dim3(kPreBwdThreads), 0, s, p);
-    } else {
-        if (parts == 4) hipLaunchKernelGGL((k_preprocess_bwd<4, false>), grid, dim3(kPreBwdThreads), 0, s, p);
-        else if (parts == 2) hipLaunchKernelGGL((k_preprocess_bwd<2, false>), grid, dim3(kPreBwdThreads), 0, s, p);
-        else hipLaunchKernelGGL((k_preprocess_bwd<1, false>), grid, dim3(kPreBwdThreads), 0, s, p);
-    }
+    if (projection_contraction()) LSR_PREBWD(true, false); else LSR_PREBWD(false, false);
+#undef LSR_PREBWD
+#undef LSR_PREBWD2
+#undef LSR_PREBWD3
     prof_end(kStPreprocessBwd, s);
     return hipGetLastError();
 }

@@ -288,7 +288,8 @@ struct PreShArgs {
 #ifndef LSR_PSH_WAVES
 #define LSR_PSH_WAVES 1
 #endif
-template <int DEGC, int COFF, bool FMA, bool SEG>
+// AA (LSR_FWD_ANTIALIAS): record and footprint opacity = opacity * rho, as in k_preprocess; instances of their own.
+template <int DEGC, int COFF, bool FMA, bool SEG, bool AA = false>
 __global__ void __launch_bounds__(kShThreads, LSR_PSH_WAVES)
 k_preprocess_sh(ShParams pk, PreShArgs a) {
     const ShParams p = group_params(pk);
@@ -349,11 +350,12 @@ k_preprocess_sh(ShParams pk, PreShArgs a) {
             const float focal_x = v < 64 ? focal.x : d.width / (2.0f * vw[35]), focal_y = v < 64 ? focal.y : d.height / (2.0f * vw[36]);
             const float scale = vw[40], scale2 = scale * scale;
             const float p0 = q0 * scale, p1 = q1 * scale, p2 = q2 * scale;
-            const Projected pj = project_gaussian<FMA>(vm, pm, limx, limy, focal_x, focal_y, p0, p1, p2, r0 * scale2, r1 * scale2, r2 * scale2,
+            const Projected pj = project_gaussian<FMA, AA>(vm, pm, limx, limy, focal_x, focal_y, p0, p1, p2, r0 * scale2, r1 * scale2, r2 * scale2,
                                                        r3 * scale2, r4 * scale2, r5 * scale2, d.width, d.height, gx, gy, active);
             const bool ok = pj.ok;
             const size_t o = (size_t)v * G + ii;
-            const uint32_t span = ok ? footprint_cells(pj.px, pj.py, pj.conic_a, pj.conic_b, pj.conic_c, opacity, pj.rminx, pj.rminy) : kSpanNone;
+            const float rec_opacity = AA ? opacity * pj.rho : opacity;
+            const uint32_t span = ok ? footprint_cells(pj.px, pj.py, pj.conic_a, pj.conic_b, pj.conic_c, rec_opacity, pj.rminx, pj.rminy) : kSpanNone;
             const TileRect rect{pj.rminx, pj.rminy, pj.rmaxx, pj.rmaxy};
             if (ok) count_pairs(a.lds_hist ? s_hist + v * T : tile_count + (size_t)v * T, gx, rect, span, skip_none);
             if (active) {
@@ -399,7 +401,7 @@ k_preprocess_sh(ShParams pk, PreShArgs a) {
             }
             float4 *R = (float4 *)(p.rec + o * (size_t)RF);
             R[0] = make_float4(pj.px, pj.py, pj.conic_a, pj.conic_b);
-            R[1] = make_float4(pj.conic_c, opacity, zpay, 0.0f);
+            R[1] = make_float4(pj.conic_c, rec_opacity, zpay, 0.0f);
             // payload slots 8.. : rgb (COFF = 3) then the feature channels, zero padded to the record
             auto slot = [&](int ch) -> float { return ch < COFF ? col[ch < 3 ? ch : 0] : (hasF ? feat(ch - COFF) : 0.0f); };
 #pragma unroll 1
@@ -853,13 +855,16 @@ hipError_t launch_preprocess_sh(const lsr_dims &d, const lsr_inputs &in, char *g
     const dim3 grid((unsigned)((nchunks + a.chunks - 1) / a.chunks), groups), block(kShThreads);
     const bool fma = projection_contraction();
     prof_begin(kStPreprocess, s);
-#define LSR_PSH2(DC, CO, FM) do { if (seg_mode) hipLaunchKernelGGL((k_preprocess_sh<DC, CO, FM, true>), grid, block, shm, s, p, a); \
-                                  else hipLaunchKernelGGL((k_preprocess_sh<DC, CO, FM, false>), grid, block, shm, s, p, a); } while (0)
+    const bool aa = (d.forward_flags & LSR_FWD_ANTIALIAS) != 0;
+#define LSR_PSH3(DC, CO, FM, AAV) do { if (seg_mode) hipLaunchKernelGGL((k_preprocess_sh<DC, CO, FM, true, AAV>), grid, block, shm, s, p, a); \
+                                       else hipLaunchKernelGGL((k_preprocess_sh<DC, CO, FM, false, AAV>), grid, block, shm, s, p, a); } while (0)
+#define LSR_PSH2(DC, CO, FM) do { if (aa) LSR_PSH3(DC, CO, FM, true); else LSR_PSH3(DC, CO, FM, false); } while (0)
 #define LSR_PSH(DC, CO) do { if (fma) LSR_PSH2(DC, CO, true); else LSR_PSH2(DC, CO, false); } while (0)
     if (degc == 4) LSR_PSH(4, 3); else if (degc == 3) LSR_PSH(3, 3); else if (degc == 2) LSR_PSH(2, 3);
     else if (degc == 1) LSR_PSH(1, 3); else if (degc == 0) LSR_PSH(0, 3); else LSR_PSH(-1, 0);
 #undef LSR_PSH
 #undef LSR_PSH2
+#undef LSR_PSH3
     prof_end(kStPreprocess, s);
     return hipGetLastError();
 }

@@ -125,12 +125,14 @@ def _view_table(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tenso
 
 
 def _render_views(views: Tensor, image_shape, means: Tensor, covariances: Tensor, opacities: Tensor,
-                  color_sh, feature_sh, use_sh: bool) -> RenderOutput:
+                  color_sh, feature_sh, use_sh: bool, antialiasing: bool = False) -> RenderOutput:
     """``views`` (B,44); UNSCALED means (S,G,3) / covariances (S,G,3,3); opacities (S,G);
     *_sh (S,G,.,.) with S = 1 (shared), B (one slice per view) or a divisor of B (scenes of B/S
     consecutive views each)."""
     h, w = image_shape
     degree, kw = 0, {}
+    if antialiasing:   # (only when asked for: the call without it is the call it always was)
+        kw.update(antialiasing=True)
     if use_sh:
         if color_sh is not None:
             degree = isqrt(color_sh.shape[-1]) - 1
@@ -190,15 +192,17 @@ def render_cuda(
     scale_invariant: bool = True,
     use_sh: bool = True,
     depth_mode: Optional[str] = None,
+    antialiasing: bool = False,
 ) -> RenderOutput:
     """``depth_mode`` (None: today's call exactly): "depth", "disparity", "relative_disparity" or "log" make
     ``RenderOutput.depth`` what ``render_depth_cuda(..., mode=depth_mode)`` renders with a second pass — here from the
-    same pass (the view table carries the mode; :func:`latentsplat_amd.rasterizer.depth_mode_payload`)."""
+    same pass (the view table carries the mode; :func:`latentsplat_amd.rasterizer.depth_mode_payload`).
+    ``antialiasing``: opacity compensation for the 0.3 low-pass (:func:`latentsplat_amd.rasterizer.rasterize_views`)."""
     assert gaussian_color_sh_coefficients is not None or gaussian_feature_sh_coefficients is not None
     assert use_sh or gaussian_color_sh_coefficients.shape[-1] == 1
     views = _view_table(extrinsics, intrinsics, near, far, background_color, scale_invariant, depth_mode)
     return _render_views(views, image_shape, gaussian_means, gaussian_covariances, gaussian_opacities,
-                         gaussian_color_sh_coefficients, gaussian_feature_sh_coefficients, use_sh)
+                         gaussian_color_sh_coefficients, gaussian_feature_sh_coefficients, use_sh, antialiasing)
 
 
 def render_scenes(
@@ -216,10 +220,11 @@ def render_scenes(
     scale_invariant: bool = True,
     use_sh: bool = True,
     depth_mode: Optional[str] = None,
+    antialiasing: bool = False,
 ) -> RenderOutput:
     """Scene-major entry point: identical results to ``render_cuda`` on the v-fold replicated
     inputs, but colour SH / opacities of a scene are read once for all of its views.
-    Returns tensors flattened over (b v) like ``render_cuda``.  ``depth_mode``: as in ``render_cuda``."""
+    Returns tensors flattened over (b v) like ``render_cuda``.  ``depth_mode``, ``antialiasing``: as in ``render_cuda``."""
     assert gaussian_color_sh_coefficients is not None or gaussian_feature_sh_coefficients is not None
     b, v = extrinsics.shape[:2]
     outs = []
@@ -231,12 +236,12 @@ def render_scenes(
         # ONE call for all b*v views: the b scenes are view groups of v views each (inputs keep their
         # leading scene dimension, nothing is replicated or concatenated)
         return _render_views(views, image_shape, gaussian_means, gaussian_covariances, gaussian_opacities,
-                             gaussian_color_sh_coefficients, fsh_all, use_sh)
+                             gaussian_color_sh_coefficients, fsh_all, use_sh, antialiasing)
     for s in range(b):   # latent SH evaluated on the host (degree > 2 / too many coefficients): per scene
         csh = None if gaussian_color_sh_coefficients is None else gaussian_color_sh_coefficients[s][None]
         fsh = fsh_all[s][None]
         outs.append(_render_views(views[s * v:(s + 1) * v], image_shape, gaussian_means[s][None],
-                                  gaussian_covariances[s][None], gaussian_opacities[s][None], csh, fsh, use_sh))
+                                  gaussian_covariances[s][None], gaussian_opacities[s][None], csh, fsh, use_sh, antialiasing))
     cat = lambda xs: None if xs[0] is None else torch.cat(xs, dim=0)
     return RenderOutput(cat([o.color for o in outs]), cat([o.feature for o in outs]),
                         cat([o.mask for o in outs]), cat([o.depth for o in outs]))

@@ -37,6 +37,7 @@ class GaussianRasterizationSettings(NamedTuple):
     campos: Tensor
     prefiltered: bool
     debug: bool
+    antialiasing: bool = False   # the published field and place: opacity compensation for the 0.3 low-pass (LSR_FWD_ANTIALIAS)
 
 
 # Depth modes of the view table (slot 41; include/lsr_rasterizer.h LSR_DEPTH_*).  The names are the reference's
@@ -290,7 +291,8 @@ class _RasterizeViews(torch.autograd.Function):
     @staticmethod
     def forward(ctx, views, means3D, means2D, cov3D, opacities, shs, colors_precomp, features,
                 H: int, W: int, sh_degree: int, debug: bool, feat_sh_degree: int = -1,
-                shs_channel_major: bool = False, pair_capacity: int = 0, max_tile_hint: int = 0, grad_mode: bool = True):
+                shs_channel_major: bool = False, pair_capacity: int = 0, max_tile_hint: int = 0, grad_mode: bool = True,
+                antialiasing: bool = False):
         lib = _lib.load()
         ctx.set_materialize_grads(False)  # unused outputs (mask / depth ...) arrive as None, not zeros
         dev = means3D.device
@@ -349,7 +351,7 @@ class _RasterizeViews(torch.autograd.Function):
                            "carry the scene dimension")
         # what earlier calls of this shape needed (speculative workspace sizes; the capacity of the key segments: real
         # device memory, lsr_dims.seg_cap_hint — 1.3 x the longest recent tile list instead of the default 8192 keys)
-        shape_key = (dev.index, V, G, H, W, Cf, color_mode, K, Kf, vpg, cov_elems, strides, _REACHED_ONLY)
+        shape_key = (dev.index, V, G, H, W, Cf, color_mode, K, Kf, vpg, cov_elems, strides, _REACHED_ONLY, bool(antialiasing))
         est = _estimate_get(shape_key) if (_SPECULATE and G > 0) else None
         d = Dims(V, G, H, W, Cf, color_mode, int(sh_degree), K, *strides,
                  cov_elems, _lib.FEAT_SH if feat_sh else _lib.FEAT_DIRECT, max(int(feat_sh_degree), 0), Kf,
@@ -359,7 +361,9 @@ class _RasterizeViews(torch.autograd.Function):
                  # zeroes the backward's gradient workspace on the side (ABI v9: lsr_backward then skips its clear)
                  # (grad_mode: torch.is_grad_enabled() of the CALLER — inside Function.forward it is always off)
                  ((_lib.FWD_FOR_BACKWARD | (_lib.FWD_CLEARS_GRAD if _FWD_CLEARS_GRAD else 0)) if (grad_mode and any(ctx.needs_input_grad) and G > 0) else 0)
-                 | (_lib.FWD_REACHED_ONLY if _REACHED_ONLY else 0),
+                 | (_lib.FWD_REACHED_ONLY if _REACHED_ONLY else 0)
+                 # opacity compensation for the low-pass; the backward reads the bit from the same dims
+                 | (_lib.FWD_ANTIALIAS if antialiasing else 0),
                  # (never below the sort-tier hint of the speculative forward: a launch structure chosen for lists of up to `hint`
                  # keys would otherwise include the fallback scatter for segments shorter than that)
                  min(max(int(1.3 * est[1]) + 64, _tier_hint(est[1])), 2 ** 31 - 1) if (est is not None and est[1] > 0) else 0)
@@ -535,9 +539,9 @@ class _RasterizeViews(torch.autograd.Function):
         elif len(ctx.m2d_shape) == 2:  # one (G,3) tensor shared by the views
             d_m2d = d_m2d.sum(0) if V > 1 else d_m2d[0]
         # order: views, means3D, means2D, cov3D, opacities, shs, colors_precomp, features, H, W, deg,
-        #        debug, feat_sh_degree, shs_channel_major
+        #        debug, feat_sh_degree, shs_channel_major, pair_capacity, max_tile_hint, grad_mode, antialiasing
         return (d_views, d_means, d_m2d, d_cov, d_opac, d_color if has_shs else None,
-                d_color if has_cp else None, d_feat, None, None, None, None, None, None, None, None, None)
+                d_color if has_cp else None, d_feat, None, None, None, None, None, None, None, None, None, None)
 
 
 def rasterize_views(views: Tensor, image_height: int, image_width: int, sh_degree: int, means3D: Tensor,
@@ -545,7 +549,7 @@ def rasterize_views(views: Tensor, image_height: int, image_width: int, sh_degre
                     colors_precomp: Optional[Tensor] = None, features: Optional[Tensor] = None,
                     means2D: Optional[Tensor] = None, debug: bool = False,
                     feature_sh: Optional[Tensor] = None, shs_channel_major: bool = False,
-                    pair_capacity: Optional[int] = None, max_tile_hint: int = 4096):
+                    pair_capacity: Optional[int] = None, max_tile_hint: int = 4096, antialiasing: bool = False):
     """Render V views in one call.  ``views`` is the (V,44) table of :func:`make_view_table`; every
     per-Gaussian tensor is either shared ``(G,...)`` or per view ``(V,G,...)``.
     Returns ``(color (V,3,H,W)|None, feature (V,C,H,W)|None, mask (V,H,W), depth (V,H,W), radii (V,G))``.
@@ -566,7 +570,13 @@ def rasterize_views(views: Tensor, image_height: int, image_width: int, sh_degre
     forward never waits for the device (``lsr_forward_nosync``) and can be captured in a
     ``torch.cuda.graph``.  A scene that needs more pairs renders truncated lists and raises the
     overflow flag reported by :func:`last_forward_status` — check it at a synchronisation point of
-    your choice."""
+    your choice.
+
+    ``antialiasing=True`` (``LSR_FWD_ANTIALIAS``; the published rasterizer's ``antialiasing``, gsplat's
+    ``rasterize_mode="antialiased"``): every splat's opacity is multiplied by ``sqrt(max(0.000025, det0 / det))``, the
+    determinants of its projected covariance before and after the 0.3 low-pass, so that a sub-pixel splat emits the light of
+    its true extent instead of that of the dilated blob.  Radii and tile lists are those of the classic mode; the gradients of
+    means, covariances and the view table include the factor's."""
     V = views.shape[0]
     feat_sh_degree = -1
     if feature_sh is not None:
@@ -578,7 +588,7 @@ def rasterize_views(views: Tensor, image_height: int, image_width: int, sh_degre
     color, feat, mask, depth, radii = _RasterizeViews.apply(
         views, means3D, means2D, cov3D_precomp, opacities, shs, colors_precomp, features,
         int(image_height), int(image_width), int(sh_degree), bool(debug), int(feat_sh_degree),
-        bool(shs_channel_major), int(pair_capacity or 0), int(max_tile_hint), torch.is_grad_enabled())
+        bool(shs_channel_major), int(pair_capacity or 0), int(max_tile_hint), torch.is_grad_enabled(), bool(antialiasing))
     return (color if color.numel() else None, feat if feat.numel() else None, mask, depth, radii)
 
 
@@ -689,6 +699,7 @@ class GaussianRasterizer(nn.Module):
         views = _pack_view(rs, means3D.device)
         color, feat, mask, depth, radii = _RasterizeViews.apply(
             views, means3D, means2D, cov3D_precomp, opacities, shs, colors_precomp, features,
-            int(rs.image_height), int(rs.image_width), int(rs.sh_degree), bool(rs.debug), -1, False, 0, 0, torch.is_grad_enabled())
+            int(rs.image_height), int(rs.image_width), int(rs.sh_degree), bool(rs.debug), -1, False, 0, 0, torch.is_grad_enabled(),
+            bool(rs.antialiasing))
         return (color[0] if color.numel() else None, feat[0] if feat.numel() else None,
                 mask, depth, radii[0])

@@ -405,11 +405,13 @@ class GaussianScene(nn.Module):
 
     def render(self, views: Tensor, height: int, width: int, scale_modifier: float = 1.0, filter_3d: Optional[Tensor] = None,
                transforms: Optional[Tensor] = None, transform_idx: Optional[Tensor] = None, check_transforms: bool = True,
-               poses=None, **kw):
+               poses=None, antialiasing: bool = False, **kw):
         """``rasterize_views`` of the activated scene: ``(color, feature, mask, depth, radii)``.  ``views`` is a table
         of ``build_view_table`` / ``make_view_table`` (one that requires grad receives the camera gradient); ``kw``
         goes to ``rasterize_views``.  All stored SH coefficients are passed with ``sh_degree=active_sh_degree``.
         ``filter_3d`` (:meth:`compute_filter_3d`): render the scene with the 3D smoothing filter inside the activation.
+        ``antialiasing=True``: the rasterizer compensates every splat's opacity for its 0.3 screen-space low-pass
+        (``rasterize_views``); with ``filter_3d`` the two halves of Mip-Splatting, and independent of it.
 
         ``transforms`` (``(4, 4)`` or ``(T, 4, 4)`` similarities on the scene's device) with ``transform_idx`` (integer
         ``(n,)``: the transform of each Gaussian; ``None``: transform 0 for all; out of range: not moved) render the POSED
@@ -425,6 +427,8 @@ class GaussianScene(nn.Module):
         :func:`latentsplat_amd.pose.pose_scene`, and the poses receive their gradient too.  It excludes ``transforms`` and,
         like it, ``filter_3d``; ``poses=None`` leaves every other path as it is."""
         from .rasterizer import rasterize_views
+        if antialiasing:   # (only when asked for: the call without it is the call it always was)
+            kw["antialiasing"] = True
         if transforms is not None or poses is not None:
             xyz, (shs, opacities, cov, _, _) = self._posed(transforms, transform_idx, filter_3d, scale_modifier, False,
                                                            check_transforms, poses)

@@ -57,6 +57,9 @@ targets do not.  Besides the raw `point_cloud.ply`, `point_cloud_fused.ply` hold
 opacities and scales, which any viewer shows filtered.  `fit.json` then holds `filter_3d`, `filter_3d_interval`,
 `filter_3d_events` (`step, reason, gaussians` of every computation) and `fused_ply`.
 
+`--antialiasing` renders the targets and every step of the fit with the rasterizer's opacity compensation for its 0.3
+screen-space low-pass (the published trainer's `--antialiasing`); `fit.json` holds `antialiasing`.
+
 `--bilateral-grid X Y L` trains with bilateral-grid appearance compensation (`latentsplat_amd.BilateralGrid`):
 every fitted render goes through one X x Y x L grid of colour affines per view before the loss (`1 1 1`: one affine per view,
 the published trainer's exposure compensation; `16 16 8`: the published grid), `--tv-weight` (default 10, the published one)
@@ -73,7 +76,7 @@ usage: python tools/fit_ply.py scene.ply --out DIR [--views 8] [--size 256] [--s
                                [--optimizer torch|fused|sparse] [--lr-position-final F] [--lr-position-max-steps S]
                                [--from-points] [--sh-degree-interval 0]
                                [--strategy adc|mcmc] [--cap-max N] [--noise-lr 5e5] [--opacity-reg 0.01] [--scale-reg 0.01]
-                               [--filter-3d] [--filter-3d-interval 100]
+                               [--filter-3d] [--filter-3d-interval 100] [--antialiasing]
                                [--bilateral-grid X Y L] [--bilateral-grid-lr 2e-3] [--tv-weight 10] [--target-jitter 0]"""
 from __future__ import annotations
 
@@ -143,6 +146,8 @@ def main(argv=None) -> dict:
     ap.add_argument("--scale-reg", type=float, default=0.01, help="mcmc: weight of mean(exp(scaling)) in the loss")
     ap.add_argument("--filter-3d", action="store_true",
                     help="train with the 3D smoothing filter of Mip-Splatting and also write point_cloud_fused.ply")
+    ap.add_argument("--antialiasing", action="store_true",
+                    help="render with opacity compensation for the 0.3 screen-space low-pass (default: the classic mode)")
     ap.add_argument("--filter-3d-interval", type=int, default=100, help="recompute the 3D filter every this many steps (the published cadence)")
     ap.add_argument("--bilateral-grid", type=int, nargs=3, default=None, metavar=("X", "Y", "L"),
                     help="one X x Y x L bilateral grid of colour affines per view between render and loss (default: none; "
@@ -181,7 +186,7 @@ def main(argv=None) -> dict:
         centre, extent = scene_extent(scene._xyz)
         ext, intr, near, far = circle_cameras(centre, extent, a.views, a.distance)
         views = build_view_table(ext, intr, near, far, torch.zeros(3, device=dev))
-        target = scene.render(views, a.size, a.size)[0]
+        target = scene.render(views, a.size, a.size, antialiasing=a.antialiasing)[0]
         if a.target_jitter > 0.0:       # a generator of its own: the perturbation below draws what it always drew
             gen_jitter = torch.Generator().manual_seed(a.seed + 0x5eed)
             gain = 1.0 + a.target_jitter * (2.0 * torch.rand(a.views, 3, generator=gen_jitter) - 1.0)
@@ -248,10 +253,11 @@ def main(argv=None) -> dict:
         opt.zero_grad(set_to_none=True)
         if densify and step < until:
             means2D = torch.zeros((a.views, scene.num_gaussians, 3), device=dev, requires_grad=True)
-            render, _, _, _, radii = scene.render(views, a.size, a.size, filter_3d=filter_3d, means2D=means2D)
+            render, _, _, _, radii = scene.render(views, a.size, a.size, filter_3d=filter_3d, means2D=means2D,
+                                                    antialiasing=a.antialiasing)
         else:
             means2D = None
-            render, _, _, _, radii = scene.render(views, a.size, a.size, filter_3d=filter_3d)
+            render, _, _, _, radii = scene.render(views, a.size, a.size, filter_3d=filter_3d, antialiasing=a.antialiasing)
         if grids is not None:
             grid_opt.zero_grad(set_to_none=True)
             render = grids(render, view_idx)
@@ -299,7 +305,8 @@ def main(argv=None) -> dict:
     res = dict(loss_first=float(losses[0]), loss_last=float(losses[-1]), steps=a.steps, ms_per_step=1e3 * per_step,
                timed_steps=a.steps - warm, gaussians=scene.num_gaussians, sh_degree=scene.max_sh_degree, views=a.views,
                size=a.size, noise=a.noise, seed=a.seed, extent=float(extent), lambda_dssim=a.lambda_dssim, optimizer=a.optimizer,
-               from_points=bool(a.from_points), active_sh_degree_last=scene.active_sh_degree)
+               from_points=bool(a.from_points), active_sh_degree_last=scene.active_sh_degree,
+               antialiasing=bool(a.antialiasing))
     if densify:
         res.update(gaussians_first=gaussians_first, gaussians_last=scene.num_gaussians, densify_events=events)
     if mcmc is not None:

@@ -10,8 +10,11 @@
      `last_forward_status()` and the scene's size) in `--out`.
 
 Files written by this project's own `export_ply` store the opacity as it is: pass `--opacity raw` for those.
+`--antialiasing` renders with the rasterizer's opacity compensation for its 0.3 screen-space low-pass (INTEGRATION.md §21);
+`status.json` holds `antialiasing`.
 
-usage: python tools/render_ply.py scene.ply --out renders [--views 8] [--size 256] [--distance 2.5] [--opacity logit]"""
+usage: python tools/render_ply.py scene.ply --out renders [--views 8] [--size 256] [--distance 2.5] [--opacity logit]
+                                  [--antialiasing]"""
 from __future__ import annotations
 
 import argparse
@@ -67,6 +70,8 @@ def main(argv=None) -> dict:
     ap.add_argument("--distance", type=float, default=2.5, help="circle radius in scene extents")
     ap.add_argument("--opacity", choices=("logit", "raw"), default="logit")
     ap.add_argument("--background", type=float, nargs=3, default=(0.0, 0.0, 0.0))
+    ap.add_argument("--antialiasing", action="store_true",
+                    help="opacity compensation for the 0.3 screen-space low-pass (default: the classic mode)")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         sys.exit("render_ply needs an MI355X: no ROCm device is visible (there is no CPU fallback)")
@@ -83,7 +88,7 @@ def main(argv=None) -> dict:
             ext, intr, near, far = circle_cameras(centre, extent, a.views, a.distance)
             views = build_view_table(ext, intr, near, far, torch.tensor(a.background, device=dev))
             color, _, mask, depth, radii = rasterize_views(views, a.size, a.size, s.sh_degree, s.means, s.covariances,
-                                                           s.opacities, shs=s.shs)
+                                                           s.opacities, shs=s.shs, antialiasing=a.antialiasing)
             status = last_forward_status()
             depth = depth * near[:, None, None]        # (the table rescales the scene so that near == 1)
     finally:
@@ -94,7 +99,7 @@ def main(argv=None) -> dict:
     np.save(os.path.join(a.out, "depth.npy"), depth.cpu().numpy())
     status = dict(status, gaussians=int(s.means.shape[0]), sh_degree=int(s.sh_degree), views=a.views, size=a.size,
                   visible=[int(v) for v in (radii > 0).sum(dim=1).tolist()], centre=[float(c) for c in centre.tolist()],
-                  extent=float(extent))
+                  extent=float(extent), antialiasing=bool(a.antialiasing))
     with open(os.path.join(a.out, "status.json"), "w") as f:
         json.dump(status, f, indent=1)
     print(json.dumps(status))
