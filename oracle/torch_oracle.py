@@ -60,22 +60,15 @@ def _clamp_mask(vm, means3D, tanfovx, tanfovy):
         return (rx >= -limx) & (rx <= limx), (ry >= -limy) & (ry <= limy)
 
 
-def rasterize(H, W, tanfovx, tanfovy, bg, viewmatrix, projmatrix, campos, sh_degree, means3D, cov3D,
-              opacities, shs=None, colors_precomp=None, features=None):
-    """Returns (color|None, feature|None, mask(1,H,W), depth(1,H,W), radii). All torch CPU."""
-    dt = means3D.dtype
+def _project(dt, H, W, tanfovx, tanfovy, vm, means3D, cov3D, inx, iny):
+    """(t (G,3), cov2 (G,2,2)): view-space means and the EWA projection M S M^T (no low-pass) in dtype ``dt``; ``vm`` (4,4)
+    as memory has it; (inx, iny) the forward's clamp decision."""
     G = means3D.shape[0]
-    vm = viewmatrix.reshape(4, 4).to(dt)  # memory [4*col+row] => vm[col,row]
-    pm = projmatrix.reshape(4, 4).to(dt)
     ones = torch.ones(G, 1, dtype=dt)
-    ph = torch.cat([means3D, ones], 1) @ pm  # (G,4): row-vector convention == transposed matrix
     t = (torch.cat([means3D, ones], 1) @ vm)[:, :3]
-    p_w = 1.0 / (ph[:, 3] + 0.0000001)
-    ndc = ph[:, :2] * p_w[:, None]
     tz = t[:, 2]
     limx, limy = 1.3 * tanfovx, 1.3 * tanfovy
     txtz, tytz = t[:, 0] / tz, t[:, 1] / tz
-    inx, iny = _clamp_mask(vm, means3D, tanfovx, tanfovy)
     tx = torch.where(inx, t[:, 0], (txtz.clamp(-limx, limx) * tz).detach())
     ty = torch.where(iny, t[:, 1], (tytz.clamp(-limy, limy) * tz).detach())
     fx, fy = W / (2.0 * tanfovx), H / (2.0 * tanfovy)
@@ -86,9 +79,63 @@ def rasterize(H, W, tanfovx, tanfovy, bg, viewmatrix, projmatrix, campos, sh_deg
     M = J @ Wr
     S = torch.stack([cov3D[:, 0], cov3D[:, 1], cov3D[:, 2], cov3D[:, 1], cov3D[:, 3], cov3D[:, 4],
                      cov3D[:, 2], cov3D[:, 4], cov3D[:, 5]], -1).reshape(G, 3, 3)
-    cov2 = M @ S @ M.transpose(1, 2)
+    return t, M @ S @ M.transpose(1, 2)
+
+
+LOWPASS = 0.3
+RHO_FLOOR = 0.000025
+
+
+def _factor(cov2):
+    """sqrt(max(0.000025, det0 / det)) of the undilated (G,2,2) covariance; 1 where det == 0 (culled anyway)."""
+    a0, b, c0 = cov2[:, 0, 0], cov2[:, 0, 1], cov2[:, 1, 1]
+    det0 = a0 * c0 - b * b
+    det = (a0 + LOWPASS) * (c0 + LOWPASS) - b * b
+    det_s = torch.where(det != 0, det, torch.ones_like(det))
+    return torch.sqrt(torch.clamp_min(det0 / det_s, RHO_FLOOR))
+
+
+def opacity_factor(H, W, tanfovx, tanfovy, viewmatrix, means3D, cov3D, dtype=None):
+    """(G,) antialiasing factor rho = sqrt(max(0.000025, det0 / det)) of every Gaussian, det0 / det the determinants of the
+    projected covariance before / after the 0.3 low-pass.  Computed in ``dtype`` from casts of the inputs (default: that of
+    ``means3D``) and returned in it; differentiable in the view matrix, tan(fov), means and covariances.  The clamp decision
+    is the forward's float32 one in every dtype."""
+    dt = means3D.dtype if dtype is None else dtype
+    c = lambda x: torch.as_tensor(x).to(dt)
+    vm = viewmatrix.reshape(4, 4)
+    inx, iny = _clamp_mask(vm, means3D, tanfovx, tanfovy)
+    return _factor(_project(dt, H, W, c(tanfovx), c(tanfovy), c(vm), c(means3D), c(cov3D), inx, iny)[1])
+
+
+def rasterize(H, W, tanfovx, tanfovy, bg, viewmatrix, projmatrix, campos, sh_degree, means3D, cov3D,
+              opacities, shs=None, colors_precomp=None, features=None, antialiasing: bool = False, rho_dtype=None):
+    """Returns (color|None, feature|None, mask(1,H,W), depth(1,H,W), radii). All torch CPU.
+
+    ``antialiasing``: the opacities composited are ``o * sqrt(clamp_min(det0 / det, 0.000025))`` (LSR_FWD_ANTIALIAS), det0
+    of the undilated ``cov2`` below and det its own: differentiable.  ``rho_dtype``: None — the factor in the call's dtype;
+    ``torch.float32`` — only the factor from float32 casts of the inputs, the rest in the call's dtype (the "stock"
+    statement of the 4 x rule, tests/antialias_ref.py); ``"constant"`` — the factor detached: what a backward without its
+    term returns."""
+    dt = means3D.dtype
+    G = means3D.shape[0]
+    vm = viewmatrix.reshape(4, 4).to(dt)  # memory [4*col+row] => vm[col,row]
+    pm = projmatrix.reshape(4, 4).to(dt)
+    ones = torch.ones(G, 1, dtype=dt)
+    ph = torch.cat([means3D, ones], 1) @ pm  # (G,4): row-vector convention == transposed matrix
+    p_w = 1.0 / (ph[:, 3] + 0.0000001)
+    ndc = ph[:, :2] * p_w[:, None]
+    inx, iny = _clamp_mask(vm, means3D, tanfovx, tanfovy)
+    t, cov2 = _project(dt, H, W, tanfovx, tanfovy, vm, means3D, cov3D, inx, iny)
+    tz = t[:, 2]
     a, b, c = cov2[:, 0, 0] + 0.3, cov2[:, 0, 1], cov2[:, 1, 1] + 0.3
     det = a * c - b * b
+    if antialiasing:
+        if rho_dtype is None or rho_dtype == "constant" or rho_dtype == dt:
+            rho = _factor(cov2)
+            rho = rho.detach() if rho_dtype == "constant" else rho
+        else:
+            rho = opacity_factor(H, W, tanfovx, tanfovy, viewmatrix, means3D, cov3D, dtype=rho_dtype).to(dt)
+        opacities = opacities.reshape(-1) * rho
     ok = (tz > 0.2) & (det != 0)
     det_s = torch.where(det != 0, det, torch.ones_like(det))
     conA, conB, conC = c / det_s, -b / det_s, a / det_s

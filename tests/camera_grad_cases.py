@@ -76,8 +76,10 @@ def with_depth_channel(pl, rec, m):
     return pl
 
 
-def oracle_forwards(views32, H, W, means, cov, opac, payload, scenes=None):
-    """Per view: the C oracle's forward (float32, the kernels' decisions bit for bit): ``radii``, ``fragile`` ..."""
+def oracle_forwards(views32, H, W, means, cov, opac, payload, scenes=None, antialiasing=False):
+    """Per view: the C oracle's forward (float32, the kernels' decisions bit for bit): ``radii``, ``fragile`` ...
+    ``antialiasing``: the C oracle has no such mode and needs none: it is fed the per-view opacities o rho, rho from the
+    float32 statement of the factor (oracle.torch_oracle.opacity_factor), which is what the mode composites."""
     out = []
     for v in range(views32.shape[0]):
         sidx, m, c6, o = view_inputs(views32, v, means, cov, opac, scenes)
@@ -87,6 +89,9 @@ def oracle_forwards(views32, H, W, means, cov, opac, payload, scenes=None):
             pl = with_depth_channel(payload(m * s, rec[32:35], sidx), rec, m)
         deg = pl.pop("sh_degree", 0)
         n = lambda k: None if pl.get(k) is None else pl[k].float().contiguous().numpy()
+        if antialiasing:
+            with torch.no_grad():
+                o = o.float() * TO.opacity_factor(H, W, rec[35], rec[36], rec[0:16], m * s, c6 * s * s, dtype=torch.float32)[:, None]
         view = orc.View(H, W, float(views32[v, 35]), float(views32[v, 36]), views32[v, 37:40].numpy(),
                         views32[v, 0:16].reshape(4, 4).numpy(), views32[v, 16:32].reshape(4, 4).numpy(),
                         views32[v, 32:35].numpy(), deg)
@@ -95,9 +100,9 @@ def oracle_forwards(views32, H, W, means, cov, opac, payload, scenes=None):
     return out
 
 
-def fragile_counts(views32, H, W, means, cov, opac, payload, scenes=None, forwards=None):
+def fragile_counts(views32, H, W, means, cov, opac, payload, scenes=None, forwards=None, antialiasing=False):
     """Per view: evaluations the C oracle's forward flags as fragile (a decision within rounding of a threshold)."""
-    fw = forwards if forwards is not None else oracle_forwards(views32, H, W, means, cov, opac, payload, scenes)
+    fw = forwards if forwards is not None else oracle_forwards(views32, H, W, means, cov, opac, payload, scenes, antialiasing)
     return [len(f["fragile"]) + (1 << 20 if f["fragile_overflow"] else 0) for f in fw]
 
 
@@ -218,15 +223,19 @@ def _colour_case(sc, deg, H, W, mode=None, placed=None):
                 dict(shs=shs, sh_degree=deg), sh_payload(deg, shs), 0, mode=mode, placed=placed)
 
 
-def _a1():
-    """V = 4, shared scene, colour SH degree 2: parts == 4 exactly, one full SH view chunk (nv = 4)"""
-    return _colour_case(make_scene(160, image_size=32, views=4, seed=SEEDS["A1"], color_sh_degree=2, feature_channels=None), 2, 32, 32)
+def _a1(seed=None, **scene):
+    """V = 4, shared scene, colour SH degree 2: parts == 4 exactly, one full SH view chunk (nv = 4).  (``seed`` / ``scene``,
+    here and below: another seed than SEEDS' and further make_scene keywords, for the callers that keep a seed table of
+    their own — tests/antialias_grad_cases.py.)"""
+    return _colour_case(make_scene(160, image_size=32, views=4, seed=SEEDS["A1"] if seed is None else seed, color_sh_degree=2,
+                                   feature_channels=None, **scene), 2, 32, 32)
 
 
-def _a2(contraction=False, mode=None):
+def _a2(contraction=False, mode=None, seed=None, **scene):
     """V = 5, shared scene, colour degree 1 + 4 latent channels of degree 2, 3 x 3 covariances: parts == 4 with views split
     2 / 1 / 1 / 1 over the parts, SH view chunks nv = 4, 1"""
-    sc = make_scene(160, image_size=32, views=5, seed=SEEDS["A2"], color_sh_degree=1, feature_channels=4, feature_sh_degree=2)
+    sc = make_scene(160, image_size=32, views=5, seed=SEEDS["A2"] if seed is None else seed, color_sh_degree=1, feature_channels=4,
+                    feature_sh_degree=2, **scene)
     shs, fsh = sc.color_sh.transpose(1, 2).contiguous(), sc.feature_sh.contiguous()
     return Case(cams32(sc, mode=mode), 32, 32, sc.means, sc.covariances.contiguous(), sc.opacities[:, None],
                 dict(shs=shs, sh_degree=1, feature_sh=fsh), latent_sh_payload(1, shs, 2, fsh), 4, contraction=contraction, mode=mode)
@@ -241,20 +250,23 @@ def _a3():
                 dict(colors_precomp=cp, features=feats), lambda ms, cpos, s: dict(colors_precomp=cp.double(), features=feats.double()), 13)
 
 
-def _a4(mode=None):
+def _a4(mode=None, seed=None, **scene):
     """b = 2 scenes x v = 5 views, colour SH degree 2: blockIdx.y = 1 with parts == 4, the vg offset in both kernels"""
-    scs = [make_scene(160, image_size=32, views=5, seed=s, color_sh_degree=2, feature_channels=None) for s in SEEDS["A4"]]
+    scs = [make_scene(160, image_size=32, views=5, seed=s, color_sh_degree=2, feature_channels=None, **scene)
+           for s in (SEEDS["A4"] if seed is None else seed)]
     st = lambda f: torch.stack([f(s) for s in scs]).contiguous()
     shs = st(lambda s: s.color_sh.transpose(1, 2))
     return Case(torch.cat([cams32(s, mode=mode) for s in scs]), 32, 32, st(lambda s: s.means), st(lambda s: cs._pack_covariances(s.covariances)),
                 st(lambda s: s.opacities[:, None]), dict(shs=shs, sh_degree=2), sh_payload(2, shs), 0, scenes=2, mode=mode)
 
 
-def _a5():
+def _a5(seed=None, **scene):
     """V = 5 with per-view (V, G, ...) means / covariances / opacities / harmonics (a different scene per view): the
     chunk = 1 path of k_sh_bwd, non-zero view strides in the camera instances"""
-    cam = make_scene(1, image_size=32, views=5, seed=SEEDS["A5"])
-    scs = [make_scene(160, image_size=32, views=1, seed=SEEDS["A5"] + 1000 * (k + 1), color_sh_degree=2, feature_channels=None) for k in range(5)]
+    seed = SEEDS["A5"] if seed is None else seed
+    cam = make_scene(1, image_size=32, views=5, seed=seed)
+    scs = [make_scene(160, image_size=32, views=1, seed=seed + 1000 * (k + 1), color_sh_degree=2, feature_channels=None, **scene)
+           for k in range(5)]
     st = lambda f: torch.stack([f(s) for s in scs]).contiguous()
     shs = st(lambda s: s.color_sh.transpose(1, 2))
     return Case(cams32(cam), 32, 32, st(lambda s: s.means), st(lambda s: cs._pack_covariances(s.covariances)),

@@ -141,3 +141,163 @@ def test_replay_of_one_isolated_gaussian():
     off = np.array([ref.isolated_mask_sum(d, 0.9, False) for d in draws]) / want
     print(f"classic / expected: {off.min():.4f} .. {off.max():.4f}")
     assert (off >= 1.1).all()
+
+
+# ---- the float64 oracle's statement of the mode (oracle/torch_oracle.py) against tests/antialias_ref.py --------------------
+def _oracle_scene():
+    """32 x 32, two views with scale slots 1 / 0.6 and 1 / 0.8 over the unscaled means of util.make_edge_scene("outside")
+    (visible Gaussians beyond 1.3 tan(fov): clamped Jacobians), ten of the filler rows with a zero and ten with a rank-1
+    covariance (det0 = 0: the floor).  float64 (views (2, 44), means, packed covariances)."""
+    from latentsplat_amd.decoder import cuda_splatting as cs
+    from tests import camera_grad_cases as cases
+    from tests import util
+    sc, lab = util.make_edge_scene("outside", 32, 32, views=2, seed=3, feature_channels=4)
+    sc.near = torch.tensor([0.6, 0.8])
+    views = cases.cams32(sc).double()
+    means, cov = sc.means.double(), cs._pack_covariances(sc.covariances).double().clone()
+    fill = np.nonzero(lab["kind"] == 0)[0][:20]
+    cov[fill[:10]] = 0.0
+    u = torch.randn(10, 3, generator=torch.Generator().manual_seed(2), dtype=torch.float64)
+    r1 = 1e-3 * u[:, :, None] * u[:, None, :]
+    cov[fill[10:]] = torch.stack([r1[:, 0, 0], r1[:, 0, 1], r1[:, 0, 2], r1[:, 1, 1], r1[:, 1, 2], r1[:, 2, 2]], -1)
+    return views, means, cov, torch.from_numpy(fill)
+
+
+def _oracle_rho(rec, means, cov, H=32, W=32, dtype=None):
+    """The oracle's factor of one view as the harness of tests/test_camera_grads_gpu.py calls it: scaled means and covariances"""
+    from oracle import torch_oracle as TO
+    s = rec[40]
+    return TO.opacity_factor(H, W, rec[35], rec[36], rec[0:16], means * s, cov * s * s, dtype=dtype)
+
+
+def test_oracle_factor_and_its_derivatives_equal_the_reference():
+    """Two independent torch statements of one formula (oracle.torch_oracle.opacity_factor through the scaled scene, as the
+    gradient harness composes it; tests/antialias_ref.rho from the table): the factor and its autograd derivatives w.r.t.
+    means, packed covariances and the view record agree in float64 to 1e-10 of each tensor's maximum."""
+    from oracle import torch_oracle as TO
+    views, means, cov, floor_rows = _oracle_scene()
+    G = means.shape[0]
+    w = torch.randn(2, G, generator=torch.Generator().manual_seed(5), dtype=torch.float64)
+    assert float((views[:, 40] - 1.0).abs().min()) > 0.2
+    leaves = lambda: [t.clone().requires_grad_(True) for t in (views, means, cov)]
+    a, b = leaves(), leaves()
+    got = torch.stack([_oracle_rho(a[0][v], a[1], a[2]) for v in range(2)])
+    want_g = ref.rho(b[0], b[1], b[2], 32, 32)
+    want, got_g, got = want_g.detach(), got, got.detach()
+    clamped = 0
+    for v in range(2):
+        inx, iny = TO._clamp_mask(views[v, :16].reshape(4, 4), means * views[v, 40], float(views[v, 35]), float(views[v, 36]))
+        z = (torch.cat([means * views[v, 40], torch.ones(G, 1, dtype=torch.float64)], 1) @ views[v, :16].reshape(4, 4))[:, 2]
+        clamped += int((~(inx & iny) & (z > 0.2)).sum())
+    assert clamped >= 8, clamped
+    assert bool((want[:, floor_rows] == 0.005).all()) and float(want.max()) > 0.5 and float(want.min()) == 0.005
+    assert float((got - want).abs().max()) <= 1e-10 * float(want.max())
+    (got_g * w).sum().backward()
+    (want_g * w).sum().backward()
+    for name, x, y in zip(("views", "means", "cov"), a, b):
+        err, top = float((x.grad - y.grad).abs().max()), float(y.grad.abs().max())
+        print(f"d rho / d{name}: max {top:.3e}, difference {err:.3e}")
+        assert top > 0 and err <= 1e-10 * top, (name, err, top)
+    assert float(a[1].grad[floor_rows].abs().max()) == 0.0 and float(a[2].grad[floor_rows].abs().max()) == 0.0
+    # the record: rho depends on the rotation part of the view matrix, its translation, tan(fov) and the scale, nothing else
+    used = torch.zeros(44, dtype=torch.bool)
+    used[[4 * c + r for c in range(4) for r in range(3)] + [35, 36, 40]] = True
+    assert float(a[0].grad[:, ~used].abs().max()) == 0.0 and bool((a[0].grad[:, used].abs() > 0).all())
+    # the float32 statement: the same function to float32 rounding, and differentiable through the casts
+    c = leaves()
+    r32 = torch.stack([_oracle_rho(c[0][v], c[1], c[2], dtype=torch.float32) for v in range(2)])
+    assert r32.dtype == torch.float32 and torch.equal(r32[:, floor_rows], torch.full((2, 20), 0.000025).sqrt())
+    live = want > 0.0051
+    assert float((r32.double() / want - 1.0)[live].abs().max()) < 1e-3
+    (r32.double() * w).sum().backward()
+    assert c[0].grad.dtype == torch.float64 and float((c[2].grad - b[2].grad).abs().max()) <= 1e-2 * float(b[2].grad.abs().max())
+
+
+def test_oracle_rasterize_keywords():
+    """rasterize(antialiasing=True) composites o rho: the same images as the classic call fed o rho, in every rho_dtype; the
+    default is the function it was; "constant" has the values of the mode and the gradients of the classic call."""
+    from oracle import torch_oracle as TO
+    views, means, cov, _ = _oracle_scene()
+    G = means.shape[0]
+    gen = torch.Generator().manual_seed(1)
+    o = 0.1 + 0.8 * torch.rand(G, 1, generator=gen, dtype=torch.float64)
+    col = torch.rand(G, 3, generator=gen, dtype=torch.float64)
+    rec = views[0]
+    s = rec[40]
+
+    def run(ms, cv, op, **kw):
+        return TO.rasterize(32, 32, rec[35], rec[36], rec[37:40], rec[0:16], rec[16:32], rec[32:35], 0, ms, cv, op,
+                            colors_precomp=col, **kw)
+
+    ms, cv = means * s, cov * s * s
+    plain, off = run(ms, cv, o), run(ms, cv, o, antialiasing=False, rho_dtype=torch.float32)
+    assert all(torch.equal(x, y) for x, y in zip(plain[:1] + plain[2:], off[:1] + off[2:]))
+    for dtype in (None, torch.float64, torch.float32, "constant"):
+        rho = _oracle_rho(rec, means, cov, dtype=torch.float32 if dtype == torch.float32 else None).double()
+        on, fed = run(ms, cv, o, antialiasing=True, rho_dtype=dtype), run(ms, cv, o * rho[:, None])
+        assert all(torch.equal(x, y) for x, y in zip(on[:1] + on[2:], fed[:1] + fed[2:])), dtype
+        assert not torch.equal(on[2], plain[2]) and torch.equal(on[4], plain[4])
+    g = torch.Generator().manual_seed(3)
+    wc = torch.randn(3, 32, 32, generator=g, dtype=torch.float64)
+    grads = {}
+    for dtype in (None, "constant"):
+        cl = cv.clone().requires_grad_(True)
+        (run(ms, cl, o, antialiasing=True, rho_dtype=dtype)[0] * wc).sum().backward()
+        grads[dtype] = cl.grad
+    cl = cv.clone().requires_grad_(True)
+    with torch.no_grad():
+        rho = _oracle_rho(rec, means, cov)
+    (run(ms, cl, o * rho[:, None])[0] * wc).sum().backward()
+    assert torch.allclose(grads["constant"], cl.grad, rtol=1e-12, atol=0)
+    assert float((grads[None] - cl.grad).abs().max()) > 1e-3 * float(cl.grad.abs().max())
+
+
+def test_oracle_factor_against_central_differences():
+    """d (sum w rho) / dx of the oracle's float64 autograd against central differences, for the record slots rho depends on
+    (the 12 view-matrix entries, both tan(fov), the scale) and for the means and covariances of twenty Gaussian rows.  The
+    weights are zero on the rows with a clamped Jacobian: there the derivative is a convention (the clamped t.x / t.z is a
+    constant), which no difference quotient sees.  Per coordinate, with D(h) = (f(x + h) - f(x - h)) / 2h:
+    D(h) = f' + h^2 f''' / 6 + O(h^4), so (D(2h) - D(h)) / 3 estimates the truncation error of D(h); the rounding error of
+    D(h) is at most 2 eps |f| / 2h with eps = 2^-53 per evaluation, taken 64-fold for the sums inside f.  The bar is twice the
+    truncation estimate plus that rounding bound; h = 1e-4 of the coordinate's scale keeps both near 1e-8 of the derivative."""
+    from oracle import torch_oracle as TO
+    views, means, cov, floor_rows = _oracle_scene()
+    G = means.shape[0]
+    w = torch.randn(2, G, generator=torch.Generator().manual_seed(5), dtype=torch.float64)
+    for v in range(2):
+        inx, iny = TO._clamp_mask(views[v, :16].reshape(4, 4), means * views[v, 40], float(views[v, 35]), float(views[v, 36]))
+        w[v][~(inx & iny)] = 0.0
+
+    def f(vw, m, c):
+        return float(sum((_oracle_rho(vw[v], m, c) * w[v]).sum() for v in range(2)))
+
+    a = [t.clone().requires_grad_(True) for t in (views, means, cov)]
+    sum((_oracle_rho(a[0][v], a[1], a[2]) * w[v]).sum() for v in range(2)).backward()
+    f0 = abs(f(views, means, cov))
+    with torch.no_grad():
+        rho = torch.stack([_oracle_rho(views[v], means, cov) for v in range(2)])
+    # twenty rows away from the floor and unclamped in a view, five of them the smallest factors there are
+    ok = ((rho > 0.0051) & (w != 0)).any(0).nonzero()[:, 0]
+    rows = torch.cat([ok[torch.argsort(rho[:, ok].min(0).values)[:5]], ok[5::max(1, len(ok) // 15)][:15]])
+    assert len(rows) == 20
+    slots = [4 * c + r for c in range(4) for r in range(3)] + [35, 36, 40]
+    coords = [(0, (v, k), float(views[v, k].abs().clamp_min(0.1))) for v in range(2) for k in slots]
+    coords += [(1, (int(g), k), float(means[g].abs().max())) for g in rows for k in range(3)]
+    coords += [(2, (int(g), k), float(cov[g].abs().max())) for g in rows for k in range(6)]
+    worst = 0.0
+    for which, idx, scale in coords:
+        h = 1e-4 * scale
+
+        def D(step):
+            hi, lo = [t.clone() for t in (views, means, cov)], [t.clone() for t in (views, means, cov)]
+            hi[which][idx] += step
+            lo[which][idx] -= step
+            return (f(*hi) - f(*lo)) / (2.0 * step)
+
+        d1, d2 = D(h), D(2.0 * h)
+        bar = 2.0 * abs(d2 - d1) / 3.0 + 64.0 * 2.0 ** -53 * f0 / h
+        got = float(a[which].grad[idx])
+        worst = max(worst, abs(got - d1) / max(abs(d1), 1e-6 * float(a[which].grad.abs().max())))
+        assert abs(got - d1) <= bar, (which, idx, got, d1, d2, bar)
+        assert bar <= 1e-5 * max(abs(d1), float(a[which].grad.abs().max()) * 1e-3), (which, idx, d1, bar)
+    print(f"{len(coords)} coordinates, worst |autograd - difference| / max(|difference|, 1e-6 of the tensor's largest) {worst:.2e}")

@@ -9,6 +9,8 @@ Reference: tests/antialias_ref.py — rho per (view, Gaussian) in float64 torch 
     tests/test_parity_gpu.py, the project's bar for gradient rows without a fragile evaluation nearby); dL/dopacities, which
     differs from the reference's by the float rounding of rho alone, without CLEAN_TOL: 4 x the stock error or 8 float32 ulps;
   * one isolated Gaussian: summed mask within 5 % of 2 pi o sqrt(det0).
+  * the speculative and the pair_capacity forward (SEG = true projection instances), eager: bit identity with the exact call.
+Gradients against the float64 oracle on every backward instance and layout: tests/test_antialias_grads_gpu.py.
 The measured ratios are printed (-s) and quoted in DESIGN.md §2.21.
 """
 import ctypes as C
@@ -207,6 +209,62 @@ def test_captured_nosync_forward(hip_device):
             assert torch.equal(a, b)
         classic = rasterize_views(c["views"], H, W, 0, c["means"], c["cov"], c["opac"], features=c["features"])
         assert not torch.equal(classic[2], eager[2])
+
+
+def _call_of(c):
+    """rasterize_views of case ``c`` with the mode on; keywords pass through"""
+    from latentsplat_amd.rasterizer import rasterize_views
+    pay = dict(shs=c["color"], feature_sh=c["features"]) if c["color_mode"] == _lib.COLOR_SH else \
+        dict(colors_precomp=c["color"], features=c["features"])
+    return lambda **kw: rasterize_views(c["views"], c["H"], c["W"], c["sh_degree"], c["means"], c["cov"], c["opac"],
+                                        antialiasing=True, **pay, **kw)
+
+
+def _assert_same_outputs(a, b, what):
+    for x, y, k in zip(a, b, ("colour", "features", "mask", "depth", "radii")):
+        assert (x is None and y is None) or torch.equal(x, y), f"{what}: {k}"
+
+
+@pytest.mark.parametrize("name", ["sh", "one_view"])
+def test_speculative_forward_equals_the_exact_one(hip_device, name):
+    """The SEG = true projection instances with the mode on, outside a captured graph: the first call of a shape takes the
+    exact path (prepare + render), the second the speculative one (SPECULATION_STATS); all outputs and radii bit for bit."""
+    from latentsplat_amd import rasterizer as R
+    c = _case(name, hip_device)
+    assert (c["color_mode"] == _lib.COLOR_SH) == (name == "sh")
+    call = _call_of(c)
+    with R._ESTIMATES_LOCK:
+        R._ESTIMATES.clear()        # whatever ran before in this process: this shape has not been seen
+    with torch.no_grad():
+        s0 = dict(R.SPECULATION_STATS)
+        exact = call()
+        s1 = dict(R.SPECULATION_STATS)
+        second = call()
+        s2 = dict(R.SPECULATION_STATS)
+    assert (s1["exact"], s1["speculative"], s1["reruns"]) == (s0["exact"] + 1, s0["speculative"], s0["reruns"])
+    assert (s2["exact"], s2["speculative"], s2["reruns"]) == (s1["exact"], s1["speculative"] + 1, s1["reruns"])
+    _assert_same_outputs(second, exact, name)
+    assert int((exact[4] > 0).sum()) > 0.3 * exact[4].numel()
+
+
+@pytest.mark.parametrize("name", ["sh", "one_view"])
+def test_pair_capacity_forward_equals_the_exact_one(hip_device, name):
+    """lsr_forward_nosync with the mode on, eager: every output and the radii of the exact call bit for bit, no overflow."""
+    from latentsplat_amd import rasterizer as R
+    c = _case(name, hip_device)
+    call = _call_of(c)
+    with R._ESTIMATES_LOCK:
+        R._ESTIMATES.clear()
+    with torch.no_grad():
+        s0 = dict(R.SPECULATION_STATS)
+        exact = call()
+        assert R.SPECULATION_STATS["exact"] == s0["exact"] + 1
+        st = R.last_forward_status()
+        nosync = call(pair_capacity=2 * st["num_pairs"] + 64, max_tile_hint=max(4096, 2 * st["max_tile_pairs"]))
+        torch.cuda.synchronize(hip_device)
+        after = R.last_forward_status()
+    assert not after["overflow"] and after["num_pairs"] == st["num_pairs"]
+    _assert_same_outputs(nosync, exact, name)
 
 
 # ---- gradients ---------------------------------------------------------------------------------------------------------

@@ -34,13 +34,13 @@ BLOCKS = dict(vm=slice(0, 16), pm=slice(16, 32), campos=slice(32, 35), tanfov=sl
 SEEDS = dict(colour=11, precomp=6, latent=21, groups=40, edge=0, depth=3, ortho=7, decoder=50)
 
 
-def _oracle_view(v, vm, pm, cp, tx, ty, bg, s, H, W, means, cov6, opac, payload):
+def _oracle_view(v, vm, pm, cp, tx, ty, bg, s, H, W, means, cov6, opac, payload, **mode):
     """One view through the float64 oracle; ``payload(ms, campos)`` -> dict(shs=.., colors_precomp=.., features=..,
-    sh_degree=..) given the SCALED means."""
+    sh_degree=..) given the SCALED means.  ``mode``: the oracle's ``antialiasing`` / ``rho_dtype``."""
     ms, cv = means * s, cov6 * s * s
     pl = payload(ms, cp)
     deg = pl.pop("sh_degree", 0)
-    col, feat, mask, depth, _ = TO.rasterize(H, W, tx, ty, bg, vm, pm, cp, deg, ms, cv, opac, **pl)
+    col, feat, mask, depth, _ = TO.rasterize(H, W, tx, ty, bg, vm, pm, cp, deg, ms, cv, opac, **pl, **mode)
     return col, feat, mask, depth
 
 
@@ -76,8 +76,10 @@ def _poison_view_grad_workspace(V, G, dev):
     torch.full((n,), 0xFF, dtype=torch.uint8, device=dev)
 
 
-def _op_grad(views32, H, W, means, cov, opac, kw, C, contraction=False, poison=False):
-    """(views.grad, radii) of the HIP op under the loss of ``_weights(V, H, W, C)``, on the host"""
+def _op_grad(views32, H, W, means, cov, opac, kw, C, contraction=False, poison=False, antialiasing=False, leaves=None):
+    """(views.grad, radii) of the HIP op under the loss of ``_weights(V, H, W, C)``, on the host.  ``antialiasing``: the op's
+    keyword (omitted when off).  ``leaves``: a dict — means, cov, opac and the payload tensors of ``kw`` require grad as well
+    (the plain backward instances run next to the camera ones) and their gradients are left in it, on the host."""
     dev = torch.device("cuda:0")
     V = views32.shape[0]
     w = _weights(V, H, W, C)
@@ -85,9 +87,14 @@ def _op_grad(views32, H, W, means, cov, opac, kw, C, contraction=False, poison=F
     lib.lsr_set_projection_contraction(1 if contraction else 0)
     try:
         views = views32.to(dev).requires_grad_(True)
-        dk = {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in kw.items()}
+        leaf = (lambda t: t.to(dev).requires_grad_(True)) if leaves is not None else (lambda t: t.to(dev))
+        dk = {k: (leaf(v) if torch.is_tensor(v) else v) for k, v in kw.items()}
+        geo = dict(means=leaf(means), cov=leaf(cov), opac=leaf(opac))
+        held = dict(geo, **{k: v for k, v in dk.items() if torch.is_tensor(v)})
         deg = dk.pop("sh_degree", 0)
-        col, feat, mask, depth, radii = R.rasterize_views(views, H, W, deg, means.to(dev), cov.to(dev), opac.to(dev), **dk)
+        if antialiasing:
+            dk["antialiasing"] = True
+        col, feat, mask, depth, radii = R.rasterize_views(views, H, W, deg, geo["means"], geo["cov"], geo["opac"], **dk)
         loss = 0.0
         for v in range(V):
             loss = loss + _loss(None if col is None else col[v].double(), None if feat is None else feat[v].double(),
@@ -95,25 +102,29 @@ def _op_grad(views32, H, W, means, cov, opac, kw, C, contraction=False, poison=F
         if poison:
             _poison_view_grad_workspace(V, means.shape[-2], dev)
         loss.backward()
+        if leaves is not None:
+            leaves.update({k: t.grad.cpu() for k, t in held.items()})
     finally:
         lib.lsr_set_projection_contraction(0)
     return views.grad.cpu(), radii.cpu()
 
 
 def _kernel_vs_oracle(views32, H, W, means, cov, opac, kw, payload, C, scenes=None, contraction=False, tol=1e-3, placed=None,
-                      info=None):
+                      info=None, antialiasing=False):
     """dL/dviews of the HIP op vs autograd through the float64 oracle, per view and per block, on a scene whose C-oracle
     forward has no fragile evaluations (a gradient there may flip between two equally right answers).  A table with a
     depth mode (slot 41): the oracle blends the mode's payload d as one more feature channel, and near / far (slots 42, 43)
-    are two more blocks.  ``placed`` (a B case of camera_grad_cases: positions of the scene's Gaussians among padding): also
+    are two more blocks.  ``antialiasing``: the op's and the oracle's mode; the C oracle (the gate, the radii) is fed o rho per
+    view.  ``placed`` (a B case of camera_grad_cases: positions of the scene's Gaussians among padding): also
     the radii — 0 on the padding in every view, the C oracle's everywhere — and the reduction workspace is poisoned before
     the backward.  ``info`` receives what the caller asserts on."""
     V = views32.shape[0]
-    fwds = oracle_forwards(views32, H, W, means, cov, opac, payload, scenes)
+    fwds = oracle_forwards(views32, H, W, means, cov, opac, payload, scenes, antialiasing=antialiasing)
     assert fragile_counts(None, H, W, None, None, None, None, forwards=fwds) == [0] * V
     moded = bool((views32[:, 41] != 0).all())
     w = _weights(V, H, W, C)
-    got32, radii = _op_grad(views32, H, W, means, cov, opac, kw, C, contraction, poison=placed is not None)
+    got32, radii = _op_grad(views32, H, W, means, cov, opac, kw, C, contraction, poison=placed is not None,
+                            antialiasing=antialiasing)
     if placed is not None:
         want_radii = torch.from_numpy(np.stack([f["radii"] for f in fwds])).to(radii.dtype)
         pad = torch.ones(means.shape[-2], dtype=torch.bool)
@@ -129,7 +140,8 @@ def _kernel_vs_oracle(views32, H, W, means, cov, opac, kw, payload, C, scenes=No
         tx, ty, bg, s = rec[35], rec[36], rec[37:40], rec[40]
         sidx, m, c6, o = _view_inputs(views32, v, means, cov, opac, scenes)
         col, feat, mask, depth = _oracle_view(v, vm, pm, cp, tx, ty, bg, s, H, W, m, c6, o,
-                                              lambda ms, cpos: with_depth_channel(payload(ms, cpos, sidx), rec, m))
+                                              lambda ms, cpos: with_depth_channel(payload(ms, cpos, sidx), rec, m),
+                                              **(dict(antialiasing=True) if antialiasing else {}))
         if moded:
             depth, feat = feat[-1:], (feat[:-1] if feat.shape[0] > 1 else None)
         _loss(col, feat, mask, depth, w[v]).backward()
@@ -150,6 +162,66 @@ def _kernel_vs_oracle(views32, H, W, means, cov, opac, kw, payload, C, scenes=No
     if info is not None:
         info.update(got=got, want=torch.stack(wants), radii=radii, masks=masks, forwards=fwds)
     return worst
+
+
+def _payload_of(kw):
+    """The oracle's payload function from the op's keywords (``shs`` + ``sh_degree`` in the 3DGS axes, ``colors_precomp``,
+    ``features``, ``feature_sh``; shared, per scene or per view), differentiable in the tensors of ``kw``."""
+    deg, shs, fsh = kw.get("sh_degree", 0), kw.get("shs"), kw.get("feature_sh")
+    pick = lambda t, base, sidx: t if t.dim() == base else t[sidx]
+
+    def f(ms, cp, sidx):
+        if fsh is not None:
+            return cases.latent_sh_payload(deg, shs, math.isqrt(fsh.shape[-1]) - 1, fsh)(ms, cp, sidx)
+        out = _sh_payload(deg, shs)(ms, cp, sidx) if shs is not None else {}
+        for k in ("colors_precomp", "features"):
+            if kw.get(k) is not None:
+                out[k] = pick(kw[k], 2, sidx).double()
+        return out
+    return f
+
+
+def _oracle_grads(views32, H, W, means, cov, opac, kw, C, scenes=None, **mode):
+    """Autograd through the float64 oracle under the loss of ``_weights(V, H, W, C)`` with the record, means, cov, opac and
+    the payload tensors of ``kw`` as leaves in the shapes the op takes them: dict of gradients (``views`` (V, 44); an input
+    shared by the views holds the sum over them, a per-scene one the sum over its group, a per-view one each view's — what
+    one leaf of that shape collects).  ``mode``: the oracle's ``antialiasing`` / ``rho_dtype``."""
+    V = views32.shape[0]
+    w = _weights(V, H, W, C)
+    leaf = lambda t: t.detach().double().clone().requires_grad_(True)
+    rec_all = leaf(views32)
+    geo = dict(means=leaf(means), cov=leaf(cov), opac=leaf(opac))
+    kw64 = {k: (leaf(v) if torch.is_tensor(v) else v) for k, v in kw.items()}
+    payload = _payload_of(kw64)
+    moded = bool((views32[:, 41] != 0).all())
+    for v in range(V):
+        rec = rec_all[v]
+        sidx, m, c6, o = _view_inputs(views32, v, geo["means"], geo["cov"], geo["opac"], scenes)
+        col, feat, mask, depth = _oracle_view(v, rec[0:16], rec[16:32], rec[32:35], rec[35], rec[36], rec[37:40], rec[40], H, W,
+                                              m, c6, o, lambda ms, cpos: with_depth_channel(payload(ms, cpos, sidx), rec, m), **mode)
+        if moded:
+            depth, feat = feat[-1:], (feat[:-1] if feat.shape[0] > 1 else None)
+        _loss(col, feat, mask, depth, w[v]).backward()
+    out = dict(views=rec_all.grad, **{k: t.grad for k, t in geo.items()})
+    out.update({k: t.grad for k, t in kw64.items() if torch.is_tensor(t)})
+    return out
+
+
+def _kernel_and_oracle_grads(views32, H, W, means, cov, opac, kw, C, scenes=None, contraction=False, antialiasing=False,
+                             rho_dtypes=(None,)):
+    """One forward and backward of the HIP op with EVERY input a leaf (the plain instances of the projection backward and,
+    for the record, the camera instances) and the float64 oracle's gradients of the same leaves, once per entry of
+    ``rho_dtypes``: (got, [want, ...], radii), dicts keyed views / means / cov / opac / the tensors of ``kw``.  Gated like
+    ``_kernel_vs_oracle`` on a C-oracle forward without fragile evaluations."""
+    V = views32.shape[0]
+    payload = _payload_of({k: (v.double() if torch.is_tensor(v) else v) for k, v in kw.items()})
+    fwds = oracle_forwards(views32, H, W, means, cov, opac, payload, scenes, antialiasing=antialiasing)
+    assert fragile_counts(None, H, W, None, None, None, None, forwards=fwds) == [0] * V
+    got = {}
+    got["views"], radii = _op_grad(views32, H, W, means, cov, opac, kw, C, contraction, antialiasing=antialiasing, leaves=got)
+    mode = lambda rd: dict(antialiasing=True, rho_dtype=rd) if antialiasing else {}
+    wants = [_oracle_grads(views32, H, W, means, cov, opac, kw, C, scenes, **mode(rd)) for rd in rho_dtypes]
+    return {k: t.double() for k, t in got.items()}, wants, radii
 
 
 @pytest.mark.parametrize("axes", ["3dgs", "reference"])
