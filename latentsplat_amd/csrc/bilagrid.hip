@@ -12,7 +12,7 @@
 // nodes, and one LDS float atomic per contribution (96 per pixel) made forward + backward of 16 x 3 x 256 x 256 take 0.65 ms,
 // and still 0.54 ms with up to 64 accumulators per entry so that no two lanes of an instruction named one address: the
 // LDS atomic unit's own rate.  So a wave takes its pixels one distinct lower node at a time, sums the 96 products of the lanes that
-// share it with the transposing exchange of wave_sum32 (lsr_internal.h), and adds each non-zero sum with one LDS atomic.
+// share it with the transposing exchange of wave_sum32 (lsr_wave.h), and adds each non-zero sum with one LDS atomic.
 // bg_path picks T: the largest of 32 and 16 whose worst-case footprint is at most kBgMaxNodes; when neither fits (a grid much
 // finer than the image), path 0 runs the same per-pixel code on 16 x 16 tiles against the parameter in global memory, one
 // global float atomic per contribution.  The bound behind the LDS sizes: a coordinate is the correctly rounded
@@ -28,7 +28,7 @@
 #include <math.h>
 
 #include "lsr_bilagrid.h"
-#include "lsr_internal.h"
+#include "lsr_wave.h"
 
 namespace lsr {
 
@@ -368,10 +368,7 @@ __global__ __launch_bounds__(kBgThreads) void k_bg_tv_fwd(TvShape s, const float
         if (y + 1 < s.Y) { const float d = g[e + s.X] - v; sy += (double)d * (double)d; }
         if (l + 1 < s.L) { const float d = g[e + yx] - v; sl += (double)d * (double)d; }
     }
-#pragma unroll
-    for (int o = LSR_WAVE / 2; o > 0; o >>= 1) {
-        sx += __shfl_xor(sx, o); sy += __shfl_xor(sy, o); sl += __shfl_xor(sl, o);
-    }
+    wave_all_each(Add(), sx, sy, sl);
     const int wave = threadIdx.x / LSR_WAVE;
     if ((threadIdx.x & (LSR_WAVE - 1)) == 0) { s_red[3 * wave] = sx; s_red[3 * wave + 1] = sy; s_red[3 * wave + 2] = sl; }
     __syncthreads();
@@ -388,10 +385,7 @@ __global__ __launch_bounds__(kBgThreads) void k_bg_tv_finish(const double *__res
     __shared__ double s_red[3 * kBgThreads / LSR_WAVE];
     double sx = 0.0, sy = 0.0, sl = 0.0;
     for (int b = threadIdx.x; b < blocks; b += kBgThreads) { sx += slots[3 * b]; sy += slots[3 * b + 1]; sl += slots[3 * b + 2]; }
-#pragma unroll
-    for (int o = LSR_WAVE / 2; o > 0; o >>= 1) {
-        sx += __shfl_xor(sx, o); sy += __shfl_xor(sy, o); sl += __shfl_xor(sl, o);
-    }
+    wave_all_each(Add(), sx, sy, sl);
     const int wave = threadIdx.x / LSR_WAVE;
     if ((threadIdx.x & (LSR_WAVE - 1)) == 0) { s_red[3 * wave] = sx; s_red[3 * wave + 1] = sy; s_red[3 * wave + 2] = sl; }
     __syncthreads();

@@ -255,7 +255,7 @@ __device__ __forceinline__ void emit_half_lists(const HalfOut &ho, uint32_t n, u
         __syncthreads();
         if (wid == 0) {
             const uint64_t v = s_tab[lane];
-            uint64_t incl = v;
+            uint64_t incl = v;   // (wave_inclusive_scan of lsr_wave.h written out: the call renumbers the kernel's scalar registers)
 #pragma unroll
             for (int off = 1; off < LSR_WAVE; off <<= 1) { const uint64_t t = __shfl_up(incl, off); if (lane >= off) incl += t; }
             s_tab[LSR_WAVE + lane] = incl - v;
@@ -274,7 +274,7 @@ __device__ __forceinline__ void emit_half_lists(const HalfOut &ho, uint32_t n, u
                 const uint32_t bits = half_bits(m16, h);
                 const uint64_t bal = __ballot(bits != 0u);
                 if (bits) {
-                    const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+                    const uint32_t below = lane_rank(bal);
                     hdst[(size_t)h * n + (h ? run1 : run0) + (uint32_t)(off >> (32 * h)) + below] = list_entry(ho, idx, bits);
                 }
             }
@@ -285,23 +285,6 @@ __device__ __forceinline__ void emit_half_lists(const HalfOut &ho, uint32_t n, u
     if (tid < 2) hcnt[tid] = tid == 0 ? run0 : run1;
 }
 
-// Reductions over the 16 lanes of every DPP row (result in each lane of the row); all lanes of the wave active.
-template <int CTRL> __device__ __forceinline__ uint32_t dpp_u32(uint32_t x) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, 0xf, false); }
-#define LSR_ROW_REDUCE(name, op)                                                                        \
-    __device__ __forceinline__ uint32_t name(uint32_t x) {                                              \
-        x = op(x, dpp_u32<0xB1>(x));  /* quad_perm [1,0,3,2] */                                         \
-        x = op(x, dpp_u32<0x4E>(x));  /* quad_perm [2,3,0,1] */                                         \
-        x = op(x, dpp_u32<0x141>(x)); /* row_half_mirror */                                             \
-        return op(x, dpp_u32<0x140>(x)); /* row_mirror */                                               \
-    }
-__device__ __forceinline__ uint32_t add_u32(uint32_t a, uint32_t b) { return a + b; }
-__device__ __forceinline__ uint32_t min_u32(uint32_t a, uint32_t b) { return a < b ? a : b; }
-__device__ __forceinline__ uint32_t max_u32(uint32_t a, uint32_t b) { return a > b ? a : b; }
-LSR_ROW_REDUCE(row_min_u32, min_u32)
-LSR_ROW_REDUCE(row_max_u32, max_u32)
-LSR_ROW_REDUCE(row_sum_u32, add_u32)
-#undef LSR_ROW_REDUCE
-__device__ __forceinline__ uint32_t rdlane(uint32_t x, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)x, l); }
 __device__ __forceinline__ uint64_t uniform_u64(uint64_t x) {   // a value every lane holds, moved to scalar registers
     return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(x >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)x);
 }
@@ -422,14 +405,14 @@ __device__ __forceinline__ void sort_tile(uint64_t *s_keys, size_t vt, int tier,
         const uint32_t dw = (uint32_t)(kreg[q] >> 32);
         dmin = min(dmin, dw); dmax = max(dmax, dw);
     }
-    dmin = row_min_u32(dmin); dmax = row_max_u32(dmax);
-    const uint32_t wmin = min(min(rdlane(dmin, 0), rdlane(dmin, 16)), min(rdlane(dmin, 32), rdlane(dmin, 48)));
-    const uint32_t wmax = max(max(rdlane(dmax, 0), rdlane(dmax, 16)), max(rdlane(dmax, 32), rdlane(dmax, 48)));
+    dmin = row_all(dmin, Min()); dmax = row_all(dmax, Max());
+    const uint32_t wmin = min(min(readlane(dmin, 0), readlane(dmin, 16)), min(readlane(dmin, 32), readlane(dmin, 48)));
+    const uint32_t wmax = max(max(readlane(dmax, 0), readlane(dmax, 16)), max(readlane(dmax, 32), readlane(dmax, 48)));
     if (lane == 0) s_red32[wid] = make_uint2(wmin, wmax);
     __syncthreads();
     const uint2 part = s_red32[lane & (kWaves - 1)];      // (every row of the wave sees all partials)
-    dmin = (uint32_t)__builtin_amdgcn_readfirstlane((int)row_min_u32(part.x));
-    dmax = (uint32_t)__builtin_amdgcn_readfirstlane((int)row_max_u32(part.y));
+    dmin = (uint32_t)__builtin_amdgcn_readfirstlane((int)row_all(part.x, Min()));
+    dmax = (uint32_t)__builtin_amdgcn_readfirstlane((int)row_all(part.y, Max()));
     kmin = (uint64_t)dmin << 32; kmax = ((uint64_t)dmax << 32) | 0xFFFFFFFFull;
     // depth words spanning fewer than NB values (coplanar Gaussians): the index words have to spread the keys, or every
     // such tile would overfill its buckets and take the bitonic network — the exact 64-bit range, as a cold path
@@ -442,6 +425,7 @@ __device__ __forceinline__ void sort_tile(uint64_t *s_keys, size_t vt, int tier,
             const uint64_t k = kreg[q];
             lo = k < lo ? k : lo; hi = k > hi ? k : hi;
         }
+        // (the butterfly of wave_all, lsr_wave.h, for a min and a max in one loop; written out: two calls change this kernel's code)
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) {
             const uint64_t a = __shfl_xor(lo, off), b = __shfl_xor(hi, off);
@@ -478,16 +462,14 @@ __device__ __forceinline__ void sort_tile(uint64_t *s_keys, size_t vt, int tier,
         loc[q] = (NB % THREADS == 0 || tid * PER + q < NB) ? s_cnt[min(tid * PER + q, NB - 1)] : 0u;
         sum += loc[q]; mx = loc[q] > mx ? loc[q] : mx;
     }
-    uint32_t incl = sum;
-#pragma unroll
-    for (int off = 1; off < LSR_WAVE; off <<= 1) { const uint32_t t = __shfl_up(incl, off); if (lane >= off) incl += t; }
+    const uint32_t incl = wave_inclusive_scan(sum);
     if (lane == LSR_WAVE - 1) s_wsum[wid] = incl;
     if (mx > kBucketOverflow) *s_flag = 1;
     __syncthreads();
     uint32_t run = incl - sum;
     {   // the waves before this one: lane w reads wave w's total, one row sum instead of kWaves reads per thread
         const uint32_t mine = s_wsum[lane & (kWaves - 1)];
-        run += (uint32_t)__builtin_amdgcn_readfirstlane((int)row_sum_u32(lane < wid ? mine : 0u));
+        run += (uint32_t)__builtin_amdgcn_readfirstlane((int)row_all(lane < wid ? mine : 0u, Add()));
     }
     const bool overflow = *s_flag != 0;
     if (!overflow) {

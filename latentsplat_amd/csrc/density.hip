@@ -6,7 +6,7 @@
 // The plan: a workgroup owns a chunk of kPlanChunk consecutive Gaussians, one per lane.  k_densify_classify writes a
 // flag byte per Gaussian (bit 0 the original is emitted, bit 1 a clone, bit 2 the children) and the chunk's three sums;
 // k_densify_scan, one workgroup, turns the sums into exclusive bases (each lane a run of consecutive chunks) and writes
-// the counts; k_densify_emit scans the flags of its chunk again (block_exclusive_scan of lsr_tile_scan.h) and writes the
+// the counts; k_densify_emit scans the flags of its chunk again (block_exclusive_scan of lsr_wave.h) and writes the
 // map entries at base + rank.  The order is fixed by the indices alone: no atomics, the same bits every call.
 //
 // The gather is a streaming kernel.  f_rest and its two moments are 45 floats wide at degree 3 and carry most of the
@@ -23,7 +23,7 @@
 
 #include "lsr_density.h"
 #include "lsr_internal.h"
-#include "lsr_tile_scan.h"
+#include "lsr_wave.h"
 
 namespace lsr {
 
@@ -111,17 +111,9 @@ __global__ __launch_bounds__(kPlanChunk) void k_densify_classify(int64_t n, cons
 __global__ __launch_bounds__(kPlanScanThreads) void k_densify_scan(int64_t chunks, int n_split, uint32_t *__restrict__ sums,
                                                                   uint32_t *__restrict__ counts) {
     __shared__ uint32_t s_wave[kPlanScanThreads / LSR_WAVE];
-    const int64_t per = (chunks + kPlanScanThreads - 1) / kPlanScanThreads;
-    const int64_t lo = threadIdx.x * per < chunks ? threadIdx.x * per : chunks, hi = lo + per < chunks ? lo + per : chunks;
     uint32_t totals[3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        uint32_t *row = sums + k * chunks;
-        uint32_t mine = 0;
-        for (int64_t i = lo; i < hi; ++i) mine += row[i];
-        uint32_t run = block_exclusive_scan<kPlanScanThreads>(mine, s_wave, totals[k]);
-        for (int64_t i = lo; i < hi; ++i) { const uint32_t c = row[i]; row[i] = run; run += c; }
-    }
+    for (int k = 0; k < 3; ++k) scan_chunk_sums<kPlanScanThreads>(sums + k * chunks, chunks, s_wave, totals[k]);
     if (threadIdx.x == 0) {
         counts[0] = totals[0]; counts[1] = totals[1]; counts[2] = totals[2];
         counts[3] = totals[0] + totals[1] + (uint32_t)n_split * totals[2];

@@ -23,7 +23,7 @@
 #include <float.h>
 #include <math.h>
 
-#include "lsr_internal.h"
+#include "lsr_wave.h"
 #include "lsr_depth_head.h"
 
 namespace lsr {
@@ -38,23 +38,11 @@ struct DhArgs {
     float e, inv_e, scale;
 };
 
-template <int CTRL, int ROW_MASK = 0xf>
-__device__ __forceinline__ float dh_dpp(float x) {      // lanes without a source (or in a masked row) read 0
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, ROW_MASK, 0xf, false));
-}
-
-struct DhMax { __device__ __forceinline__ float operator()(float a, float b) const { return fmaxf(a, b); } };
-struct DhMin { __device__ __forceinline__ float operator()(float a, float b) const { return fminf(a, b); } };
-struct DhAdd { __device__ __forceinline__ float operator()(float a, float b) const { return a + b; } };
-
 // all-reduce over the L lanes of a group; the operands of every step are the same pair on both sides, so all lanes
 // return identical bits
 template <int L, class Op>
 __device__ __forceinline__ float dh_all(float x, Op op) {
-    x = op(x, dh_dpp<0xB1>(x));      // quad_perm [1,0,3,2]
-    x = op(x, dh_dpp<0x4E>(x));      // quad_perm [2,3,0,1]
-    x = op(x, dh_dpp<0x141>(x));     // row_half_mirror
-    x = op(x, dh_dpp<0x140>(x));     // row_mirror
+    x = row_all(x, op);
     if (L >= 32) x = op(x, __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(x), 0x401F)));   // lane ^ 16
     if (L >= 64) x = op(x, __shfl_xor(x, 32));
     return x;
@@ -63,12 +51,12 @@ __device__ __forceinline__ float dh_all(float x, Op op) {
 // inclusive prefix sum over the L lanes of a group
 template <int L>
 __device__ __forceinline__ float dh_scan(float x) {
-    x += dh_dpp<0x111>(x);           // row_shr:1
-    x += dh_dpp<0x112>(x);           // row_shr:2
-    x += dh_dpp<0x114>(x);           // row_shr:4
-    x += dh_dpp<0x118>(x);           // row_shr:8
-    if (L >= 32) x += dh_dpp<0x142, 0xA>(x);      // row_bcast15 into rows 1 and 3
-    if (L >= 64) x += dh_dpp<0x143, 0xC>(x);      // row_bcast31 into rows 2 and 3
+    x += dpp<0x111>(x);              // row_shr:1 (lanes without a source, or in a masked row, add 0)
+    x += dpp<0x112>(x);              // row_shr:2
+    x += dpp<0x114>(x);              // row_shr:4
+    x += dpp<0x118>(x);              // row_shr:8
+    if (L >= 32) x += dpp<0x142, 0xA>(x);         // row_bcast15 into rows 1 and 3
+    if (L >= 64) x += dpp<0x143, 0xC>(x);         // row_bcast31 into rows 2 and 3
     return x;
 }
 
@@ -93,11 +81,11 @@ __device__ __forceinline__ DhLane dh_lane(const DhArgs &a, const float *__restri
         }
     }
     DhLane r;
-    const float m = dh_all<L>(l, DhMax());
+    const float m = dh_all<L>(l, Max());
     const float e = active ? expf(l - m) : 0.0f;
-    const float s = dh_all<L>(e, DhAdd());
+    const float s = dh_all<L>(e, Add());
     r.p = e / s;
-    r.z = FLT_EPSILON + dh_all<L>(r.p, DhAdd());
+    r.z = FLT_EPSILON + dh_all<L>(r.p, Add());
     r.n = r.p / r.z;
     r.o = 1.0f / (1.0f + expf(-off));
     const float c = dh_scan<L>(r.n);
@@ -141,8 +129,8 @@ __global__ __launch_bounds__(kDhThreads) void k_depth_head_fwd(DhArgs a, const f
         // k rounds: the largest remaining p, then the lowest lane that holds it
         float pv = active ? r.p : -1.0f;
         for (int j = 0; j < a.k; ++j) {
-            const float m = dh_all<L>(pv, DhMax());
-            const int win = (int)dh_all<L>(pv == m ? (float)b : (float)L, DhMin());
+            const float m = dh_all<L>(pv, Max());
+            const int win = (int)dh_all<L>(pv == m ? (float)b : (float)L, Min());
             if (b == j) idx = win;
             if (b == win) pv = -1.0f;
         }
@@ -209,7 +197,7 @@ __global__ __launch_bounds__(kDhThreads) void k_depth_head_bwd(DhArgs a, const f
     }
     float dp = a.transmittance ? acc_g / r.den + acc_t : (acc_g - acc_t) / r.z;
     if (!active) dp = 0.0f;
-    const float dot = dh_all<L>(r.p * dp, DhAdd());
+    const float dot = dh_all<L>(r.p * dp, Add());
     const float dl = r.p * (dp - dot), da = acc_a * r.o * (1.0f - r.o);
     if (!(live && active)) return;
     float *dst = d_logits + row * a.grad_row_stride + (size_t)(b * a.F + f) * 2;

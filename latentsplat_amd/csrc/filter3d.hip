@@ -25,7 +25,7 @@
 #include <cmath>
 
 #include "lsr_filter3d.h"
-#include "lsr_internal.h"
+#include "lsr_wave.h"
 
 namespace lsr {
 
@@ -139,11 +139,7 @@ __global__ __launch_bounds__(kFilterThreads) void k_filter3d_pass(int n, const f
         const uint32_t bits = is_seen ? __float_as_uint(f) : 0u;
         mine = bits > mine ? bits : mine;
     }
-#pragma unroll
-    for (int step = LSR_WAVE / 2; step > 0; step >>= 1) {
-        const uint32_t other = (uint32_t)__shfl_xor((int)mine, step, LSR_WAVE);
-        mine = other > mine ? other : mine;
-    }
+    mine = wave_all(mine, Max());
     if ((threadIdx.x & (LSR_WAVE - 1)) == 0 && mine) atomicMax(max_bits, mine);
 }
 

@@ -46,7 +46,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 
-#include "lsr_internal.h"
+#include "lsr_wave.h"
 #include "lsr_knn.h"
 
 namespace lsr {
@@ -59,23 +59,14 @@ constexpr int kBBoxBlocks = 1024;
 constexpr int kCellBits = 21;
 constexpr float kCellMax = (float)((1 << kCellBits) - 1);
 
-__device__ __forceinline__ float wave_min(float v) {
-    for (int o = LSR_WAVE / 2; o; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-    for (int o = LSR_WAVE / 2; o; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-
 // min / max of three coordinates over a workgroup of kThreads; the result in every thread (s: 6 floats per wave)
 template <int kThreads>
 __device__ __forceinline__ void block_minmax3(float lo[3], float hi[3], float *s) {
     const int lane = threadIdx.x & (LSR_WAVE - 1), wave = threadIdx.x / LSR_WAVE;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        lo[k] = wave_min(lo[k]);
-        hi[k] = wave_max(hi[k]);
+        lo[k] = wave_all(lo[k], Min());
+        hi[k] = wave_all(hi[k], Max());
         if (lane == 0) { s[6 * wave + k] = lo[k]; s[6 * wave + 3 + k] = hi[k]; }
     }
     __syncthreads();
@@ -179,7 +170,7 @@ __global__ __launch_bounds__(kGroup) void k_knn_group_boxes(int64_t chunks, cons
         lo[0] = a.x; lo[1] = a.y; lo[2] = a.z; hi[0] = b.x; hi[1] = b.y; hi[2] = b.z;
     }
 #pragma unroll
-    for (int k = 0; k < 3; ++k) { lo[k] = wave_min(lo[k]); hi[k] = wave_max(hi[k]); }
+    for (int k = 0; k < 3; ++k) { lo[k] = wave_all(lo[k], Min()); hi[k] = wave_all(hi[k], Max()); }
     if (threadIdx.x == 0) {
         group_boxes[2 * (int64_t)blockIdx.x] = make_float4(lo[0], lo[1], lo[2], 0.0f);
         group_boxes[2 * (int64_t)blockIdx.x + 1] = make_float4(hi[0], hi[1], hi[2], 0.0f);
@@ -248,8 +239,8 @@ __global__ __launch_bounds__(kQueries) void k_knn_search(int64_t n, int64_t chun
     Best3 b = {INFINITY, INFINITY, INFINITY, INT32_MAX, INT32_MAX, INT32_MAX};
 
     // the box of the wave's queries
-    const float4 qmin = make_float4(wave_min(valid ? q.x : INFINITY), wave_min(valid ? q.y : INFINITY), wave_min(valid ? q.z : INFINITY), 0.0f);
-    const float4 qmax = make_float4(wave_max(valid ? q.x : -INFINITY), wave_max(valid ? q.y : -INFINITY), wave_max(valid ? q.z : -INFINITY), 0.0f);
+    const float4 qmin = make_float4(wave_all(valid ? q.x : INFINITY, Min()), wave_all(valid ? q.y : INFINITY, Min()), wave_all(valid ? q.z : INFINITY, Min()), 0.0f);
+    const float4 qmax = make_float4(wave_all(valid ? q.x : -INFINITY, Max()), wave_all(valid ? q.y : -INFINITY, Max()), wave_all(valid ? q.z : -INFINITY, Max()), 0.0f);
 
     // stage chunk ch, scan it, and return the wave's bound: the largest third-best distance of its queries
     const auto scan_chunk = [&](int64_t ch, bool own) {
@@ -259,7 +250,7 @@ __global__ __launch_bounds__(kQueries) void k_knn_search(int64_t n, int64_t chun
         __syncthreads();
         if (own) scan_staged<true>(b, q, me, s_pts, count);
         else scan_staged<false>(b, q, me, s_pts, count);
-        return wave_max(valid ? b.d2 : 0.0f);
+        return wave_all(valid ? b.d2 : 0.0f, Max());
     };
 
     float r2 = scan_chunk(c, true);

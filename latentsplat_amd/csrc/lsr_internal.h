@@ -371,23 +371,6 @@ inline ViewGradLayout view_grad_layout(const lsr_dims &d) {
     L.total = L.dpart + align_up((size_t)d.num_views * (size_t)cam_chunks(d) * 2 * 4);
     return L;
 }
-// Sum of v[0..31] over the 64 lanes of a wave (all lanes active): recursive halving, 32 exchanges instead of 6 per value.
-// Lane l returns the total of slot l & 31.  A fixed exchange pattern: bitwise reproducible.
-// (one template instance per step: every index is a constant, the array stays in registers)
-template <int H>
-__device__ __forceinline__ void wave_halve(float (&v)[32], int lane) {
-    const bool up = (lane & H) != 0;
-#pragma unroll
-    for (int k = 0; k < H; ++k) {
-        const float send = up ? v[k] : v[k + H], keep = up ? v[k + H] : v[k];
-        v[k] = keep + __shfl_xor(send, H);
-    }
-}
-__device__ __forceinline__ float wave_sum32(float (&v)[32]) {
-    const int lane = (int)(threadIdx.x & (LSR_WAVE - 1));
-    wave_halve<16>(v, lane); wave_halve<8>(v, lane); wave_halve<4>(v, lane); wave_halve<2>(v, lane); wave_halve<1>(v, lane);
-    return v[0] + __shfl_xor(v[0], 32);
-}
 hipError_t launch_preprocess_backward(const lsr_dims &d, const lsr_inputs &in, const char *geom,
                                       const int32_t *radii, const char *grad,
                                       const lsr_in_grads &gin, hipStream_t s, const CamGrad &cam = CamGrad{nullptr, 0, nullptr});

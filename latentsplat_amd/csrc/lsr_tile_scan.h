@@ -8,7 +8,7 @@
 // round 4 — the stage used to be a kernel of its own on the critical path of every forward) and by k_tile_scan, the
 // stand-alone kernel for calls with more tiles than that workgroup handles from registers.
 #pragma once
-#include "lsr_internal.h"
+#include "lsr_wave.h"
 
 namespace lsr {
 
@@ -37,31 +37,6 @@ __device__ __forceinline__ uint32_t scan_load(const uint32_t *p) {
     // the (mutually incoherent) per-XCD L2s the same way
     if (ATOMIC) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return *p;
-}
-
-// Block-wide exclusive prefix sum of one value per thread: wave scans in registers + one LDS hop (two barriers).
-template <int THREADS>
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t *s_wave, uint32_t &total) {
-    constexpr int kWaves = THREADS / LSR_WAVE;
-    const int lane = threadIdx.x & (LSR_WAVE - 1), wid = threadIdx.x / LSR_WAVE;
-    uint32_t incl = v;
-#pragma unroll
-    for (int off = 1; off < LSR_WAVE; off <<= 1) {
-        const uint32_t t = (uint32_t)__shfl_up((int)incl, off);
-        if (lane >= off) incl += t;
-    }
-    if (lane == LSR_WAVE - 1) s_wave[wid] = incl;
-    __syncthreads();
-    uint32_t base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-        const uint32_t x = s_wave[w];
-        tot += x;
-        base += w < wid ? x : 0u;
-    }
-    __syncthreads();   // s_wave may be reused
-    total = tot;
-    return base + incl - v;
 }
 
 // REGS = counts a thread keeps in registers; longer chunks (and REGS = 0: the folded instance, whose counts sit in
@@ -107,12 +82,9 @@ __device__ __forceinline__ void tile_scan_block(const uint32_t *count, uint32_t 
         for (int i = lo; i < hi; ++i) { const uint32_t c = scan_load<ATOMIC>(&count[i]); sum += c; sum64 += c; mx = max(mx, c); }
     }
     // one combined pass: exclusive scan of the chunk sums, the longest list, the 64-bit total (two barriers)
-    uint32_t incl = sum;
-#pragma unroll
-    for (int off = 1; off < LSR_WAVE; off <<= 1) {
-        const uint32_t t = (uint32_t)__shfl_up((int)incl, off);
-        if (lane >= off) incl += t;
-    }
+    const uint32_t incl = wave_inclusive_scan(sum);
+    // the butterfly of wave_all (lsr_wave.h), two operators in one loop; written out: through the shared primitive
+    // k_preprocess and k_preprocess_sh get other register assignments
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) { mx = max(mx, (uint32_t)__shfl_xor((int)mx, off)); sum64 += __shfl_xor(sum64, off); }
     if (lane == LSR_WAVE - 1) sh.wave[wid] = incl;

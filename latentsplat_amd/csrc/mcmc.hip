@@ -40,7 +40,7 @@
 
 #include "lsr_mcmc.h"
 #include "lsr_internal.h"
-#include "lsr_tile_scan.h"
+#include "lsr_wave.h"
 
 namespace lsr {
 
@@ -61,31 +61,6 @@ struct Binomials {
     }
 };
 __constant__ const Binomials kBinomials{};
-
-// Block-wide exclusive prefix sum of one uint64 per thread (block_exclusive_scan of lsr_tile_scan.h in 64 bits).
-template <int THREADS>
-__device__ __forceinline__ uint64_t block_exclusive_scan64(uint64_t v, uint64_t *s_wave, uint64_t &total) {
-    constexpr int kWaves = THREADS / LSR_WAVE;
-    const int lane = threadIdx.x & (LSR_WAVE - 1), wid = threadIdx.x / LSR_WAVE;
-    uint64_t incl = v;
-#pragma unroll
-    for (int off = 1; off < LSR_WAVE; off <<= 1) {
-        const uint64_t t = (uint64_t)__shfl_up((unsigned long long)incl, off);
-        if (lane >= off) incl += t;
-    }
-    if (lane == LSR_WAVE - 1) s_wave[wid] = incl;
-    __syncthreads();
-    uint64_t base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-        const uint64_t x = s_wave[w];
-        tot += x;
-        base += w < wid ? x : 0ull;
-    }
-    __syncthreads();   // s_wave may be reused
-    total = tot;
-    return base + incl - v;
-}
 
 static int64_t mcmc_chunks(int64_t n) { return (n + kMcmcChunk - 1) / kMcmcChunk; }
 
@@ -114,12 +89,8 @@ __global__ __launch_bounds__(kMcmcChunk) void k_mcmc_classify(int64_t n, const f
 __global__ __launch_bounds__(kMcmcScanThreads) void k_mcmc_classify_scan(int64_t n, int64_t chunks, uint32_t *__restrict__ sums,
                                                                         uint32_t *__restrict__ counts) {
     __shared__ uint32_t s_wave[kMcmcScanThreads / LSR_WAVE];
-    const int64_t per = (chunks + kMcmcScanThreads - 1) / kMcmcScanThreads;
-    const int64_t lo = threadIdx.x * per < chunks ? threadIdx.x * per : chunks, hi = lo + per < chunks ? lo + per : chunks;
-    uint32_t mine = 0, total;
-    for (int64_t i = lo; i < hi; ++i) mine += sums[i];
-    uint32_t run = block_exclusive_scan<kMcmcScanThreads>(mine, s_wave, total);
-    for (int64_t i = lo; i < hi; ++i) { const uint32_t c = sums[i]; sums[i] = run; run += c; }
+    uint32_t total;
+    scan_chunk_sums<kMcmcScanThreads>(sums, chunks, s_wave, total);
     if (threadIdx.x == 0) { counts[0] = total; counts[1] = (uint32_t)n - total; }
 }
 
@@ -161,19 +132,15 @@ __global__ __launch_bounds__(kMcmcChunk) void k_mcmc_sums(int64_t n, const float
     uint64_t q = 0;
     if (g < n) { q = mcmc_quantum(weights[g]); count[g] = 0u; }
     uint64_t total;
-    block_exclusive_scan64<kMcmcChunk>(q, s_wave, total);
+    block_exclusive_scan<kMcmcChunk>(q, s_wave, total);
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
 // one workgroup: sums [chunks] to exclusive bases in place, bases[chunks] = total
 __global__ __launch_bounds__(kMcmcScanThreads) void k_mcmc_scan(int64_t chunks, uint64_t *__restrict__ sums, uint64_t *__restrict__ total_out) {
     __shared__ uint64_t s_wave[kMcmcScanThreads / LSR_WAVE];
-    const int64_t per = (chunks + kMcmcScanThreads - 1) / kMcmcScanThreads;
-    const int64_t lo = threadIdx.x * per < chunks ? threadIdx.x * per : chunks, hi = lo + per < chunks ? lo + per : chunks;
-    uint64_t mine = 0, total;
-    for (int64_t i = lo; i < hi; ++i) mine += sums[i];
-    uint64_t run = block_exclusive_scan64<kMcmcScanThreads>(mine, s_wave, total);
-    for (int64_t i = lo; i < hi; ++i) { const uint64_t c = sums[i]; sums[i] = run; run += c; }
+    uint64_t total;
+    scan_chunk_sums<kMcmcScanThreads>(sums, chunks, s_wave, total);
     if (threadIdx.x == 0) {
         sums[chunks] = total;
         if (total_out) *total_out = total;
@@ -185,7 +152,7 @@ __global__ __launch_bounds__(kMcmcChunk) void k_mcmc_cum(int64_t n, const float 
     const int64_t g = (int64_t)blockIdx.x * kMcmcChunk + threadIdx.x;
     const uint64_t q = g < n ? mcmc_quantum(weights[g]) : 0u;
     uint64_t total;
-    const uint64_t before = block_exclusive_scan64<kMcmcChunk>(q, s_wave, total);
+    const uint64_t before = block_exclusive_scan<kMcmcChunk>(q, s_wave, total);
     if (g < n) ws.cum[g] = ws.bases[blockIdx.x] + before + q;
 }
 

@@ -20,7 +20,7 @@
 
 #include <cmath>
 
-#include "lsr_internal.h"
+#include "lsr_wave.h"
 #include "lsr_loss.h"
 
 namespace lsr {
@@ -69,11 +69,7 @@ __device__ __forceinline__ void ph_stage(float *__restrict__ dst, const float *_
 
 // sum of a lane's two values over the workgroup, in a fixed order; valid in thread 0
 __device__ __forceinline__ void ph_block_sum(double &a, double &b, double *s_red) {
-#pragma unroll
-    for (int o = LSR_WAVE / 2; o > 0; o >>= 1) {
-        a += __shfl_xor(a, o);
-        b += __shfl_xor(b, o);
-    }
+    wave_all_each(Add(), a, b);
     const int wave = threadIdx.x / LSR_WAVE;
     if ((threadIdx.x & (LSR_WAVE - 1)) == 0) {
         s_red[2 * wave] = a;
@@ -193,11 +189,7 @@ __global__ __launch_bounds__(kPhFinishThreads) void k_photo_finish(const double2
             const double2 t = p[i];
             a += t.x; b += t.y;
         }
-#pragma unroll
-        for (int o = LSR_WAVE / 2; o > 0; o >>= 1) {
-            a += __shfl_xor(a, o);
-            b += __shfl_xor(b, o);
-        }
+        wave_all_each(Add(), a, b);
         a *= inv_count_s; b *= inv_count_l;
         if (lane == 0) {
             if (ssim) ssim[v] = (float)a;

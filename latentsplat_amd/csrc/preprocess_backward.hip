@@ -21,7 +21,7 @@
 // lsr_set_projection_contraction between its forward and its backward.)
 // Spec: SURVEY.md Appendix A.6.
 #include "lsr_depth.h"
-#include "lsr_internal.h"
+#include "lsr_wave.h"
 #include "lsr_project.h"
 
 namespace lsr {
@@ -314,8 +314,7 @@ k_preprocess_bwd(PreBwdParams pk) {
                 p.cam.part[(vg * p.cam.chunks + chunk) * kCamSlots + lane] = r;
             // near / far of the depth modes: a pair of their own per (view, chunk), zeros in the native mode
             float dn = cv ? gz_n : 0.0f, df = cv ? gz_f : 0.0f;
-#pragma unroll
-            for (int m = LSR_WAVE / 2; m >= 1; m >>= 1) { dn += __shfl_xor(dn, m); df += __shfl_xor(df, m); }
+            wave_all_each(Add(), dn, df);
             if (lane == 0 && chunk < p.cam.chunks) *(float2 *)(p.cam.dpart + (vg * p.cam.chunks + chunk) * 2) = make_float2(dn, df);
         }
         if constexpr (CAM) continue;

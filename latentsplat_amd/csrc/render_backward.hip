@@ -42,6 +42,7 @@
 #include <type_traits>
 
 #include "lsr_blend.h"
+#include "lsr_wave.h"
 
 namespace lsr {
 
@@ -95,14 +96,13 @@ struct RenderBwdParams {
 // register, a dead pair nothing (lanes that end up with a dead pair hold junk and do not write).
 template <int CTRL>
 __device__ __forceinline__ float dpp_add(float x) {   // x + partner(x)
-    return x + f_from_u((unsigned)__builtin_amdgcn_update_dpp(0, (int)u_from_f(x), CTRL, 0xf, 0xf, false));
+    return x + dpp<CTRL>(x);
 }
 template <int CTRL, bool LO, bool HI>
 __device__ __forceinline__ float2_b pair_step(bool bit, float2_b lo, float2_b hi) {
     if (LO && HI) {
         const float kx = bit ? hi.x : lo.x, ky = bit ? hi.y : lo.y, sx = bit ? lo.x : hi.x, sy = bit ? lo.y : hi.y;
-        return float2_b{kx + f_from_u((unsigned)__builtin_amdgcn_update_dpp(0, (int)u_from_f(sx), CTRL, 0xf, 0xf, false)),
-                        ky + f_from_u((unsigned)__builtin_amdgcn_update_dpp(0, (int)u_from_f(sy), CTRL, 0xf, 0xf, false))};
+        return float2_b{kx + dpp<CTRL>(sx), ky + dpp<CTRL>(sy)};
     }
     if (LO) return float2_b{dpp_add<CTRL>(lo.x), dpp_add<CTRL>(lo.y)};
     if (HI) return float2_b{dpp_add<CTRL>(hi.x), dpp_add<CTRL>(hi.y)};
@@ -304,7 +304,8 @@ k_render_bwd(RenderBwdParams p) {
                 R2 = s0;
             }
         }
-        // wave-uniform upper bound of the list entries any pixel has to consider
+        // wave-uniform upper bound of the list entries any pixel has to consider (wave_all of lsr_wave.h written out:
+        // through the shared primitive the kernel's packed-math schedule and register assignments change)
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) maxlast = max(maxlast, (uint32_t)__shfl_xor((int)maxlast, off));
         maxlast = __builtin_amdgcn_readfirstlane(maxlast);
@@ -397,7 +398,7 @@ k_render_bwd(RenderBwdParams p) {
                 const uint32_t nb_b = (uint32_t)__builtin_popcountll(bal);
                 nk = max(nk, nb_b);
                 if (__builtin_amdgcn_inverse_ballot_w64(bal)) {
-                    at[b] = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+                    at[b] = lane_rank(bal);
                     if (REV) at[b] = nb_b - 1u - at[b];     // the sub-block's list in reverse order
                 }
             }

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "lsr_blend.h"
+#include "lsr_wave.h"
 
 namespace lsr {
 
@@ -313,8 +314,7 @@ k_render_fwd(RenderFwdParams p) {
                 const uint64_t bal = __ballot((m >> b) & 1u);
                 nk = max(nk, (uint32_t)__builtin_popcountll(bal));
                 if (__builtin_amdgcn_inverse_ballot_w64(bal)) {
-                    const uint32_t at = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-                    s_list[b][at] = my_off;
+                    s_list[b][lane_rank(bal)] = my_off;
                 }
             }
             nk = __builtin_amdgcn_readfirstlane(nk);
@@ -450,9 +450,7 @@ k_render_fwd(RenderFwdParams p) {
                     const uint32_t c1 = min(nk, c0 + 32u);
                     hist = 0u;
                     for (uint32_t i = c0; i < c1; ++i) entry_step(i);
-                    hist |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hist, 0xB1, 0xf, 0xf, false);    // quad_perm [1,0,3,2]
-                    hist |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hist, 0x4E, 0xf, 0xf, false);    // quad_perm [2,3,0,1]
-                    hist |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hist, 0x141, 0xf, 0xf, false);   // row_half_mirror
+                    hist = half_row_all(hist, Or());
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const uint32_t i = c0 + (uint32_t)(l8 + 8 * r);
@@ -556,9 +554,7 @@ k_order_items(const uint32_t *__restrict__ cost, uint32_t *__restrict__ order2, 
     }
     __syncthreads();
     const uint32_t mine = s_cnt[tid];
-    uint32_t incl = mine;
-#pragma unroll
-    for (int off = 1; off < LSR_WAVE; off <<= 1) { const uint32_t t = __shfl_up(incl, off); if (lane >= off) incl += t; }
+    const uint32_t incl = wave_inclusive_scan(mine);
     if (lane == LSR_WAVE - 1) s_wsum[wid] = incl;
     __syncthreads();
     uint32_t run = incl - mine;
@@ -695,8 +691,7 @@ __device__ __forceinline__ void render_row_item(const RenderFwdParams &p, const 
             const uint64_t bal = __ballot((m >> b) & 1u);
             nk = max(nk, (uint32_t)__builtin_popcountll(bal));
             if (__builtin_amdgcn_inverse_ballot_w64(bal)) {
-                const uint32_t at = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-                s_list[b][at] = my_off;
+                s_list[b][lane_rank(bal)] = my_off;
             }
         }
         nk = __builtin_amdgcn_readfirstlane(nk);
@@ -758,10 +753,7 @@ __device__ __forceinline__ void render_row_item(const RenderFwdParams &p, const 
                 const uint32_t c1 = min(nk, c0 + 32u);
                 hist = 0u;
                 for (uint32_t i = c0; i < c1; ++i) entry_step(i);
-                hist |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hist, 0xB1, 0xf, 0xf, false);    // quad_perm [1,0,3,2]
-                hist |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hist, 0x4E, 0xf, 0xf, false);    // quad_perm [2,3,0,1]
-                hist |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hist, 0x141, 0xf, 0xf, false);   // row_half_mirror
-                hist |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hist, 0x140, 0xf, 0xf, false);   // row_mirror
+                hist = row_all(hist, Or());
 #pragma unroll
                 for (int r = 0; r < 2; ++r) {
                     const uint32_t i = c0 + (uint32_t)(l16 + 16 * r);
@@ -912,10 +904,7 @@ __device__ __forceinline__ void render_subblock_item(const RenderFwdParams &p, c
         }
         const uint64_t bal = __ballot(m);
         const uint32_t nk = (uint32_t)__builtin_popcountll(bal);
-        if (m) {
-            const uint32_t at = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-            s_list[at] = my_off;
-        }
+        if (m) s_list[lane_rank(bal)] = my_off;
         wave_lds_fence();
         for (uint32_t i = 0; i < nk; i += 4) {
             if (done == ~0ull) break;

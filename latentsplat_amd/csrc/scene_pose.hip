@@ -30,7 +30,7 @@
 
 #include <algorithm>
 
-#include "lsr_internal.h"
+#include "lsr_wave.h"
 #include "lsr_sh_shape.h"
 #include "lsr_pose.h"
 #include "lsr_sh_generator_table.h"
@@ -107,30 +107,12 @@ __device__ __forceinline__ float pg_axis(const float *__restrict__ c, const floa
     return acc;
 }
 
-__device__ __forceinline__ float pg_readlane(float v, int lane) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane));
-}
-
-// v + (v of the lane the DPP control names), all 64 lanes active
-template <int CTRL>
-__device__ __forceinline__ float pg_dpp_add(float v) {
-    return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-
-// the sum of v over the 64 lanes as a uniform value, in a fixed order: within each row of 16 lanes by four DPP exchanges
-// (lane ^ 1, lane ^ 2, the mirrored half row, the mirrored row: every lane of a row ends with the same sum), then the
-// four rows as (r0 + r1) + (r2 + r3).  Six levels; no LDS traffic (a __shfl butterfly is six dependent LDS round trips).
+// the sum of v over the 64 lanes as a uniform value, in a fixed order: within each row of 16 lanes by row_all (every lane
+// of a row ends with the same sum), then the four rows as (r0 + r1) + (r2 + r3).  Six levels; no LDS traffic (a __shfl
+// butterfly is six dependent LDS round trips).
 __device__ __forceinline__ float pg_wave_sum(float v) {
-    v = pg_dpp_add<0xB1>(v);      // quad_perm [1, 0, 3, 2]
-    v = pg_dpp_add<0x4E>(v);      // quad_perm [2, 3, 0, 1]
-    v = pg_dpp_add<0x141>(v);     // row_half_mirror
-    v = pg_dpp_add<0x140>(v);     // row_mirror
-    const int b = __builtin_bit_cast(int, v);
-    const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 0));
-    const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 16));
-    const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32));
-    const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48));
-    return (r0 + r1) + (r2 + r3);
+    v = row_all<true>(v, Add());
+    return (readlane(v, 0) + readlane(v, 16)) + (readlane(v, 32) + readlane(v, 48));
 }
 
 template <int K>
@@ -228,7 +210,7 @@ __global__ __launch_bounds__(pg_chunk(K)) void k_scene_pose_grad(int64_t n, int 
         bool open = valid;
         unsigned long long todo = __ballot(open);
         for (int trip = 0; todo && trip < kPgTrips; ++trip) {
-            const int cur = __builtin_amdgcn_readlane(id, __ffsll((long long)todo) - 1);
+            const int cur = readlane(id, __ffsll((long long)todo) - 1);
             const bool mine = open && id == cur;
             const float r[7] = {pg_wave_sum(mine ? w0 : 0.0f), pg_wave_sum(mine ? w1 : 0.0f), pg_wave_sum(mine ? w2 : 0.0f),
                                 pg_wave_sum(mine ? t0 : 0.0f), pg_wave_sum(mine ? t1 : 0.0f), pg_wave_sum(mine ? t2 : 0.0f),
@@ -242,14 +224,14 @@ __global__ __launch_bounds__(pg_chunk(K)) void k_scene_pose_grad(int64_t n, int 
         }
         while (todo) {                                   // in lane order; uniform: todo lives in scalar registers
             const int src = __ffsll((long long)todo) - 1;
-            const int cur = __builtin_amdgcn_readlane(id, src);
-            float x = pg_readlane(w0, src);
-            x = lane == 1 ? pg_readlane(w1, src) : x;
-            x = lane == 2 ? pg_readlane(w2, src) : x;
-            x = lane == 3 ? pg_readlane(t0, src) : x;
-            x = lane == 4 ? pg_readlane(t1, src) : x;
-            x = lane == 5 ? pg_readlane(t2, src) : x;
-            x = lane == 6 ? pg_readlane(ls, src) : x;
+            const int cur = readlane(id, src);
+            float x = readlane(w0, src);
+            x = lane == 1 ? readlane(w1, src) : x;
+            x = lane == 2 ? readlane(w2, src) : x;
+            x = lane == 3 ? readlane(t0, src) : x;
+            x = lane == 4 ? readlane(t1, src) : x;
+            x = lane == 5 ? readlane(t2, src) : x;
+            x = lane == 6 ? readlane(ls, src) : x;
             if (lane < 7) tab[cur * 7 + lane] += (double)x;
             todo &= todo - 1;
         }

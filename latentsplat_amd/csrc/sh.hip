@@ -585,7 +585,8 @@ k_sh_bwd(ShParams pk) {
         } else {
             for (int j = 0; j < ntot; ++j) mg[j] = 0.0f;
         }
-        if constexpr (CAM) {   // (wave-uniform: every lane takes part in the exchanges)
+        if constexpr (CAM) {   // (wave-uniform: every lane takes part in the exchanges; wave_all_each of lsr_wave.h written
+                               // out: through the shared primitive the kernel gets other register assignments)
 #pragma unroll
             for (int m = LSR_WAVE / 2; m >= 1; m >>= 1)
 #pragma unroll

@@ -4,7 +4,7 @@
 // in /root/reference/src/model/decoder/cuda_splatting.py:75-82 (1/near scale invariance),
 // :111-113 (get_fov, tan), :115-118 (projection, inverse extrinsics, full projection) and
 // src/geometry/projection.py:233-247 (get_fov).  One thread per view, double precision inside.
-#include "lsr_internal.h"
+#include "lsr_wave.h"
 
 namespace lsr {
 
@@ -158,10 +158,7 @@ k_view_grad_partial(const float *__restrict__ part, const float *__restrict__ dp
             for (int c = 0; c < 3; ++c) b[c] += g_color[((size_t)v * 3 + c) * HW + px] * T;
         }
     }
-#pragma unroll
-    for (int m = LSR_WAVE / 2; m >= 1; m >>= 1)
-#pragma unroll
-        for (int c = 0; c < 5; ++c) b[c] += __shfl_xor(b[c], m);
+    wave_all_each(Add(), b[0], b[1], b[2], b[3], b[4]);
     if ((tid & (LSR_WAVE - 1)) == 0)
         for (int c = 0; c < 5; ++c) s_bg[tid / LSR_WAVE][c] = b[c];
     __syncthreads();
