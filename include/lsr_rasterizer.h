@@ -435,6 +435,25 @@ int lsr_backward_views(const lsr_dims *d, const lsr_inputs *in, const void *geom
                        void *grad_ws, const lsr_in_grads *gin, float *grad_views, void *view_grad_ws,
                        lsr_stream_t stream);
 
+/* ---- absolute view-space gradients (AbsGS; gsplat's absgrad) ----
+ * lsr_backward_absgrad is lsr_backward_views (grad_views / view_grad_ws NULL: no camera gradient) that also writes
+ *   means2D_abs [V][G][3] = ( W/2 * sum_p |u_p (A dx_p + B dy_p)|,  H/2 * sum_p |u_p (B dx_p + C dy_p)|,  0 )
+ * for every (view, Gaussian): the sums of the MAGNITUDES of the per-pixel contributions to the means2D gradient, in its
+ * units (NDC), where lsr_in_grads.means2D holds their signed sum.  p runs over the pixels one by one; d = mean_pix - pixel;
+ * (A, B, C) is the conic; u_p = opacity * G * dL/dalpha at the pixel (straight through the 0.99 clamp, 0 where the pixel
+ * skips the entry or has stopped; with LSR_FWD_ANTIALIAS the opacity is o' = o rho).  Hence means2D_abs >= |means2D|
+ * component by component, with equality for a splat that reaches one pixel.  A large splat whose per-pixel contributions
+ * cancel in the signed sum keeps its magnitude here: the densification statistic of AbsGS.
+ * Every row is written (a buffer need not be cleared); rows with radii == 0 are 0.  All other outputs are those of
+ * lsr_backward_views.  Supported with at most 4 payload channels in all (3 colour + 1 feature, or up to 4 features):
+ * LSR_EUNSUPPORTED beyond that, LSR_ENULL for a NULL means2D_abs, both before any GPU work.  lsr_in_grads and the ABI
+ * version (10) are unchanged: the symbol is an addition. */
+int lsr_backward_absgrad(const lsr_dims *d, const lsr_inputs *in, const void *geom_ws,
+                         const void *bin_ws, const void *img_ws, int64_t num_pairs,
+                         const int32_t *radii, const lsr_outputs *fwd, const lsr_out_grads *gout,
+                         void *grad_ws, const lsr_in_grads *gin, float *grad_views, void *view_grad_ws,
+                         float *means2D_abs, lsr_stream_t stream);
+
 /* ---- optional measurement hook (bench.py): when enabled, every stage kernel is bracketed by
  * hipEvents on the caller's stream; lsr_profile_read() waits for them, returns the accumulated
  * milliseconds and launch counts per stage since the previous read, and resets the totals.

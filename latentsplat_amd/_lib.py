@@ -27,6 +27,7 @@ FWD_FRONT_DONE = 8      # (ABI v10) lsr_forward_front has launched the front hal
 FWD_ANTIALIAS = 32      # opacity compensation for the 0.3 low-pass (bit 4 is reserved)
 MAX_SH_GROUP_FLOATS = 120   # C*Kf the fused latent-SH path supports (LDS budget of sh.hip)
 MAX_FEAT_CHANNELS = 32
+ABSGRAD_MAX_CHANNELS = 4   # payload channels (colour counts 3) lsr_backward_absgrad supports: kAbsGradMaxChannels of csrc/lsr_internal.h
 
 
 class LsrError(RuntimeError):
@@ -307,6 +308,7 @@ PROTOTYPES = {
     "lsr_backward": (_INT, _BWD),
     "lsr_view_grad_workspace_bytes": (_SZ, [_ptr_to(Dims)]),
     "lsr_backward_views": (_INT, _BWD + [_P, _P]),
+    "lsr_backward_absgrad": (_INT, _BWD + [_P, _P, _P]),
     "lsr_profile_enable": (None, [_INT]),
     "lsr_profile_num_stages": (_INT, None),
     "lsr_profile_stage_name": (_STR, [_INT]),

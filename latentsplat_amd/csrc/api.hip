@@ -741,11 +741,12 @@ int lsr_forward_status(const lsr_dims *d, const void *geom_ws, int64_t *num_pair
 }  // extern "C"
 
 // the body of lsr_backward (checked arguments, G > 0); cam != nullptr: the camera-gradient instances of the geometry and
-// SH backward kernels, which also store the partial records of dL/d(view record)
+// SH backward kernels, which also store the partial records of dL/d(view record); m2d_abs != nullptr: the ABS instances of
+// the compositing and projection backward, which also store the absolute view-space gradient (lsr_backward_absgrad)
 static int backward_impl(const lsr_dims *d, const lsr_inputs *in, const void *geom_ws, const void *bin_ws,
                          const void *img_ws, int64_t num_pairs, const int32_t *radii, const lsr_outputs *fwd,
                          const lsr_out_grads *gout, void *grad_ws, const lsr_in_grads *gin, const CamGrad *cam,
-                         hipStream_t s) {
+                         hipStream_t s, float *m2d_abs = nullptr) {
     if ((gout->color && d->color_mode != LSR_COLOR_NONE && !fwd->color) || (gout->feature && d->feat_channels > 0 && !fwd->feature) ||
         (gout->depth && !fwd->depth))
         return LSR_ENULL;
@@ -757,14 +758,15 @@ static int backward_impl(const lsr_dims *d, const lsr_inputs *in, const void *ge
     if (!(d->forward_flags & LSR_FWD_CLEARS_GRAD)) LSR_HIP(launch_clear_grad(*d, (char *)grad_ws, s));
     if (num_pairs > 0)
         LSR_STAGE("render_backward", s, launch_render_backward(*d, *in, (const char *)geom_ws, (const char *)bin_ws, num_pairs,
-                                       (const char *)img_ws, *fwd, *gout, (char *)grad_ws, s));
+                                       (const char *)img_ws, *fwd, *gout, (char *)grad_ws, s, m2d_abs != nullptr));
     // Geometry and SH backward: one launch each, all scenes (view groups) of the call at once (the scene in
     // blockIdx.y).  Both add into the scene's mean gradients, hence in stream order.
     if (!cam) {
-        LSR_STAGE("preprocess_backward", s, launch_preprocess_backward(*d, *in, (const char *)geom_ws, radii, (const char *)grad_ws, *gin, s));
+        LSR_STAGE("preprocess_backward", s, launch_preprocess_backward(*d, *in, (const char *)geom_ws, radii, (const char *)grad_ws, *gin, s,
+                                                                                      CamGrad{nullptr, 0, nullptr}, m2d_abs));
         LSR_STAGE("sh_backward", s, launch_sh_backward(*d, *in, (const char *)geom_ws, (const char *)grad_ws, *gin, s));
     } else {
-        LSR_STAGE("preprocess_backward", s, launch_preprocess_backward(*d, *in, (const char *)geom_ws, radii, (const char *)grad_ws, *gin, s, *cam));
+        LSR_STAGE("preprocess_backward", s, launch_preprocess_backward(*d, *in, (const char *)geom_ws, radii, (const char *)grad_ws, *gin, s, *cam, m2d_abs));
         LSR_STAGE("sh_backward", s, launch_sh_backward_cam(*d, *in, (const char *)geom_ws, (const char *)grad_ws, *gin, *cam, s));
     }
     return LSR_OK;
@@ -794,6 +796,37 @@ int lsr_backward_views(const lsr_dims *d, const lsr_inputs *in, const void *geom
     const CamGrad cam{(float *)((char *)view_grad_ws + view_grad_layout(*d).part), cam_chunks(*d),
                       (float *)((char *)view_grad_ws + view_grad_layout(*d).dpart)};
     rc = backward_impl(d, in, geom_ws, bin_ws, img_ws, num_pairs, radii, fwd, gout, grad_ws, gin, &cam, s);
+    if (rc) return rc;
+    const float *final_T = (const float *)((const char *)img_ws + img_layout(*d).final_T);
+    LSR_STAGE("view_grad", s, launch_view_grad_reduce(*d, (char *)view_grad_ws, sh_backward_runs(*d), final_T,
+                                                      d->color_mode != LSR_COLOR_NONE ? gout->color : nullptr, grad_views, s));
+    return LSR_OK;
+}
+
+int lsr_backward_absgrad(const lsr_dims *d, const lsr_inputs *in, const void *geom_ws, const void *bin_ws,
+                         const void *img_ws, int64_t num_pairs, const int32_t *radii, const lsr_outputs *fwd,
+                         const lsr_out_grads *gout, void *grad_ws, const lsr_in_grads *gin,
+                         float *grad_views, void *view_grad_ws, float *means2D_abs, lsr_stream_t stream) {
+    g_last_hip_error = 0;
+    int rc = check_dims(d);
+    if (rc) return rc;
+    rc = check_inputs(d, in);
+    if (rc) return rc;
+    if (!gout || !gin || !geom_ws || !img_ws || !grad_ws || !fwd || !means2D_abs) return LSR_ENULL;
+    if (grad_views && !view_grad_ws) return LSR_ENULL;
+    // record slots 14 / 15 are free only while the padded payload is 4 channels (render_backward.hip)
+    if (payload_channels(*d) > kAbsGradMaxChannels) return LSR_EUNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    if (d->num_gaussians == 0) {   // no rows of means2D_abs to write; the camera gradient is the background's
+        if (grad_views)
+            LSR_STAGE("view_grad", s, launch_view_grad_reduce(*d, (char *)view_grad_ws, false, nullptr,
+                                                              d->color_mode != LSR_COLOR_NONE ? gout->color : nullptr, grad_views, s));
+        return LSR_OK;
+    }
+    if (!grad_views) return backward_impl(d, in, geom_ws, bin_ws, img_ws, num_pairs, radii, fwd, gout, grad_ws, gin, nullptr, s, means2D_abs);
+    const CamGrad cam{(float *)((char *)view_grad_ws + view_grad_layout(*d).part), cam_chunks(*d),
+                      (float *)((char *)view_grad_ws + view_grad_layout(*d).dpart)};
+    rc = backward_impl(d, in, geom_ws, bin_ws, img_ws, num_pairs, radii, fwd, gout, grad_ws, gin, &cam, s, means2D_abs);
     if (rc) return rc;
     const float *final_T = (const float *)((const char *)img_ws + img_layout(*d).final_T);
     LSR_STAGE("view_grad", s, launch_view_grad_reduce(*d, (char *)view_grad_ws, sh_backward_runs(*d), final_T,

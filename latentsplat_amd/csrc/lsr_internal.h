@@ -340,7 +340,18 @@ hipError_t launch_clear_grad(const lsr_dims &d, char *grad, hipStream_t s);
 hipError_t launch_render_backward(const lsr_dims &d, const lsr_inputs &in, const char *geom,
                                   const char *bin, int64_t num_pairs, const char *img,
                                   const lsr_outputs &fwd, const lsr_out_grads &gout, char *grad,
-                                  hipStream_t s);
+                                  hipStream_t s, bool abs_grad = false);
+// ---- absolute view-space gradients (lsr_backward_absgrad; AbsGS) ----
+// abs_grad: the compositing backward's ABS instances also leave, in slots 14 / 15 of the 16-float gradient record (pair P7,
+// free whenever the padded payload is 4 channels: at most 4 channels in all),
+//   [14] sum_p |u_p de'/ddx_p|   [15] sum_p |u_p de'/ddy_p|     (e': the exponent of lsr_blend.h, in units of log2)
+// over the pixels p one by one; the projection backward's ABS instances store means2D_abs[v][g] =
+// (ln 2 * W / 2 * [14], ln 2 * H / 2 * [15], 0) for visible slots and zeros for culled ones.  No other reader of the record
+// looks at the two slots: k_preprocess_bwd's 16-float payload path adds them into accumulators of channels the call does not
+// have (stored under `c < feat_channels`), k_sh_bwd reads `j < ntot` only.
+constexpr float kLn2 = 0.6931471805599453f;
+inline int payload_channels(const lsr_dims &d) { return (d.color_mode != LSR_COLOR_NONE ? 3 : 0) + d.feat_channels; }
+constexpr int kAbsGradMaxChannels = 4;
 // ---- camera gradients (lsr_backward_views) ----
 // The geometry and SH backward kernels plain-store one partial record of dL/d(view record) per (view, 64-Gaussian chunk)
 // (the wave's sum: the view is wave-uniform in both); two small kernels (views.hip) add them up in a fixed order.  No float
@@ -373,7 +384,8 @@ inline ViewGradLayout view_grad_layout(const lsr_dims &d) {
 }
 hipError_t launch_preprocess_backward(const lsr_dims &d, const lsr_inputs &in, const char *geom,
                                       const int32_t *radii, const char *grad,
-                                      const lsr_in_grads &gin, hipStream_t s, const CamGrad &cam = CamGrad{nullptr, 0, nullptr});
+                                      const lsr_in_grads &gin, hipStream_t s, const CamGrad &cam = CamGrad{nullptr, 0, nullptr},
+                                      float *means2D_abs = nullptr);
 hipError_t launch_sh_backward_cam(const lsr_dims &d, const lsr_inputs &in, const char *geom, const char *grad,
                                   const lsr_in_grads &gin, const CamGrad &cam, hipStream_t s);
 bool sh_backward_runs(const lsr_dims &d);

@@ -38,6 +38,7 @@ struct PreBwdParams {
     lsr_in_grads g;
     GroupStrides gs;        // view groups (blockIdx.y): element offsets of the next group's slices
     CamGrad cam;            // camera-gradient instances (CAM): the partial records of dL/d(view record)
+    float *means2D_abs;     // ABS instances: [V][G][3] absolute view-space gradient (lsr_internal.h), else unused
 };
 
 constexpr int kPreBwdFeat = 8;   // shared direct-feature gradients kept in registers up to this many channels
@@ -56,7 +57,9 @@ constexpr int kPreBwdShared = 3 + 6 + 1 + kPreBwdFeat + 3;   // register accumul
 // AA (forwards run with LSR_FWD_ANTIALIAS): the record's opacity was o' = o rho, rho^2 = det0 / det (lsr_project.h), so the
 // moment m0 = sum o' G dL/dalpha is also rho dL/drho, and rho's dependence on the 2D covariance joins dL/d(a, b, c) below.
 // Instances of their own again: the ones without it are the code they were.
-template <int PARTS, bool FMA, bool CAM = false, bool AA = false>
+// ABS (lsr_backward_absgrad; plain instances only): next to means2D, store the absolute view-space gradient from slots 14 / 15
+// of the record, whose line the thread has just read.  Instances of their own once more.
+template <int PARTS, bool FMA, bool CAM = false, bool AA = false, bool ABS = false>
 __global__ void __launch_bounds__(kPreBwdThreads, 4)
 k_preprocess_bwd(PreBwdParams pk) {
     // view groups: blockIdx.y = group; its inputs, gradient outputs and workspace slices (uniform: scalar arithmetic)
@@ -69,8 +72,10 @@ k_preprocess_bwd(PreBwdParams pk) {
         if (p.g.color) p.g.color += g * pk.gs.color;
         if (p.g.features) p.g.features += g * pk.gs.feat;
         if (p.g.means2D) p.g.means2D += g * pk.gs.slots * 3;
+        if constexpr (ABS) p.means2D_abs += g * pk.gs.slots * 3;
     }
     constexpr int LPP = kPreBwdThreads / PARTS;               // Gaussians per block = lanes per part
+    static_assert(!(CAM && ABS), "the camera-gradient instance stores nothing but its partial records");
     __shared__ float s_part[PARTS > 1 ? (PARTS - 1) * kPreBwdShared * LPP : 1];
     const int part = __builtin_amdgcn_readfirstlane((int)threadIdx.x / LPP);   // wave-uniform
     const int slot = (int)threadIdx.x % LPP;
@@ -104,6 +109,16 @@ k_preprocess_bwd(PreBwdParams pk) {
         const float4 r0 = *(const float4 *)rc, r1 = *(const float4 *)(rc + 4);           // m1x m1y m2xx m2xy | m2yy m0 gz -
         float4 q0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), q1 = q0;
         if (pay16) { q0 = *(const float4 *)(rc + 8); q1 = *(const float4 *)(rc + 12); }
+        if constexpr (ABS) {
+            // slots 14 / 15: sums of magnitudes in the exponent's units (log2) and in pixels -> natural units, NDC (as m2x / m2y
+            // below).  Every live row is written: culled slots read the zero line.  (Stored here, while little else is live: next
+            // to the means2D store the two values and their address cost the instance a wave per SIMD.)
+            const float2 ab = *(const float2 *)(rc + 14);
+            if (live) {
+                float *oa = p.means2D_abs + 3 * o;
+                oa[0] = ab.x * (kLn2 * 0.5f * d.width); oa[1] = ab.y * (kLn2 * 0.5f * d.height); oa[2] = 0.0f;
+            }
+        }
         // opacity: the record holds m0 = sum opacity * G * dL/dalpha; dL/dopacity = m0 / opacity
         // (m0 != 0 implies opacity >= 1/255)
         // AA: m0 is taken with the record's o' = o rho, and dL/do = rho dL/do' = rho m0 / o' = m0 / o: the division by the
@@ -402,7 +417,7 @@ k_preprocess_bwd(PreBwdParams pk) {
 
 hipError_t launch_preprocess_backward(const lsr_dims &d_all, const lsr_inputs &in, const char *geom,
                                       const int32_t *radii, const char *grad,
-                                      const lsr_in_grads &gin, hipStream_t s, const CamGrad &cam) {
+                                      const lsr_in_grads &gin, hipStream_t s, const CamGrad &cam, float *means2D_abs) {
     if (d_all.num_gaussians == 0) return hipSuccess;
     const GeomLayout L = geom_layout(d_all);
     const GradLayout R = grad_layout(d_all);
@@ -415,14 +430,17 @@ hipError_t launch_preprocess_backward(const lsr_dims &d_all, const lsr_inputs &i
     p.zero_rec = (const float *)(grad + R.fixed - 256);
     p.g = gin;
     p.cam = cam;
+    p.means2D_abs = means2D_abs;
     prof_begin(kStPreprocessBwd, s);
     const int parts = d.num_views >= 4 ? 4 : (d.num_views >= 2 ? 2 : 1);
     const int per_block = kPreBwdThreads / parts;   // Gaussians per block
     const dim3 grid((unsigned)((d.num_gaussians + per_block - 1) / per_block), (unsigned)num_view_groups(d_all));
     // the projection convention of the forward (lsr_set_projection_contraction): the clamp decision must be its own
     const bool aa = (d.forward_flags & LSR_FWD_ANTIALIAS) != 0;   // the forward's flag word: its projection scaled the opacities
-#define LSR_PREBWD3(PT, FM, CM, AAV) hipLaunchKernelGGL((k_preprocess_bwd<PT, FM, CM, AAV>), grid, dim3(kPreBwdThreads), 0, s, p)
-#define LSR_PREBWD2(PT, FM, CM) do { if (aa) LSR_PREBWD3(PT, FM, CM, true); else LSR_PREBWD3(PT, FM, CM, false); } while (0)
+#define LSR_PREBWD3(PT, FM, CM, AAV, AB) hipLaunchKernelGGL((k_preprocess_bwd<PT, FM, CM, AAV, AB>), grid, dim3(kPreBwdThreads), 0, s, p)
+#define LSR_PREBWD2(PT, FM, CM) do { \
+        if (!CM && means2D_abs) { if (aa) LSR_PREBWD3(PT, FM, false, true, true); else LSR_PREBWD3(PT, FM, false, false, true); } \
+        else if (aa) LSR_PREBWD3(PT, FM, CM, true, false); else LSR_PREBWD3(PT, FM, CM, false, false); } while (0)
 #define LSR_PREBWD(FM, CM) do { \
         if (parts == 4) LSR_PREBWD2(4, FM, CM); else if (parts == 2) LSR_PREBWD2(2, FM, CM); else LSR_PREBWD2(1, FM, CM); } while (0)
     if (cam.part) {   // the camera gradient: a second launch over the same records (the plain instance follows below)

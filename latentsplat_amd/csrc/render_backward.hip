@@ -131,19 +131,26 @@ __device__ __forceinline__ void atomic_add_f32(float *addr, float v) { unsafeAto
 // chain: DESIGN.md).
 // SPLIT: the list-splitting instance for launches that cannot fill the wave slots (see the item loop); the plain instance
 // carries none of its tests.
-template <int NCHP, bool DEPTH_GRAD, int WPB, bool SPLIT>
+// ABS (absolute view-space gradients, AbsGS; 4 padded channels only): pair P7 of the record — slots 14 / 15, free whenever the
+// padded payload is 4 channels — also collects  sum_p |u_p de'/ddx_p|,  sum_p |u_p de'/ddy_p|  over the PIXELS p taken one by
+// one: the magnitude is formed per pixel, before the lane's two pixels are added and before any cross-lane sum.  With
+// de'/d(dx, dy) = -log2(e) (A dx + B dy, B dx + C dy) these are log2(e) x the magnitude sums of the per-pixel contributions
+// to dL/dmean_pix, which the moments cannot give (k_preprocess_bwd applies ln 2 and the NDC scale once per (view, Gaussian)).
+// Instances of their own: the ones without it are the code they were.
+template <int NCHP, bool DEPTH_GRAD, int WPB, bool SPLIT, bool ABS = false>
 __global__ void __launch_bounds__(LSR_WAVE * WPB)
 k_render_bwd(RenderBwdParams p) {
     // float4 per staged entry: odd (conflict-free staging stores) except for the 8-channel payload, whose
     // 16 floats are stored at a 64-byte stride (2-way conflicts in the staging stores only) so that the
     // slice fits 16 waves per CU
+    static_assert(!ABS || NCHP == 4, "pair P7 of the 16-float record is free only when the padded payload is 4 channels");
     constexpr int kEnt = NCHP == 8 ? 4 : ((2 + NCHP / 4) | 1);
     constexpr int RF = NCHP <= 8 ? 16 : (NCHP <= 12 ? 32 : 64);       // == rec_floats (lsr_internal.h)
     constexpr int NGRP = RF / 16;                                     // 16-value (8-pair) reduction passes per evaluation
     // words per row of the LDS gradient table: for the 16-float record without depth gradient only the live slots
     // (0..5 and 8..8+NCHP-1; the pair (6, 7) and the unused payload pairs have no column), the full record otherwise
     constexpr bool kPackRow = NCHP <= 8 && !DEPTH_GRAD;
-    constexpr int RT = kPackRow ? 6 + NCHP : RF;
+    constexpr int RT = kPackRow ? 6 + NCHP + (ABS ? 2 : 0) : RF;   // (ABS: slots 14 / 15 get the packed row's last column pair)
     constexpr int kListRow = LSR_WAVE + 2;    // u16 per list row: 33 words, so the eight lane groups' reads of list[b][i] hit eight banks
     struct Lds {
         float4 ent[WPB][LSR_WAVE + 1][kEnt];   // (x, y, a2, c2) (b2, log2 o, z, list position) payload...; slot 64 = null record
@@ -178,9 +185,9 @@ k_render_bwd(RenderBwdParams p) {
     const int grp = lane >> 3, gcol = grp & 3, grow = grp >> 2, l8 = lane & 7;
     const int lx = 2 * (lane & 1), ly = (lane >> 1) & 3;
     // this lane's pair of record slots (2 l8, 2 l8 + 1) -> columns of the table row (pair 3 has none when packed)
-    const int tcol = kPackRow ? (l8 < 4 ? 2 * l8 : 2 * l8 - 2) : 2 * l8;
+    const int tcol = kPackRow ? ((ABS && l8 == 7) ? 6 + NCHP : (l8 < 4 ? 2 * l8 : 2 * l8 - 2)) : 2 * l8;
     const int l16 = lane & 15, fgrp = lane >> 4;           // flush: one 64-byte record per 16 lanes
-    const int fcol = kPackRow ? (l16 < 8 ? l16 : l16 - 2) : l16;
+    const int fcol = kPackRow ? ((ABS && l16 >= 14) ? l16 - 8 + NCHP : (l16 < 8 ? l16 : l16 - 2)) : l16;
 
     const uint32_t simd_bins = (uint32_t)p.num_cus * 4u, slots = (uint32_t)p.num_cus * (uint32_t)WPB;
     const uint32_t vwave = (uint32_t)wid + (uint32_t)WPB * (blockIdx.x / (uint32_t)p.num_cus);   // 0 .. WPB-1 (one workgroup per CU: the quotient is 0)
@@ -507,13 +514,25 @@ k_render_bwd(RenderBwdParams p) {
                 for (int c = 0; c < NCHP; ++c) { const float2_b t = dpix[c] * w; gp[c] = t.x + t.y; }
                 float gz = 0.0f;
                 if (DEPTH_GRAD) { const float2_b t = ddep2 * w; gz = t.x + t.y; }
+                // ABS: |u de'/ddx|, |u de'/ddy| at each of the two pixels, then added (de'/ddx = 2 a2 dx + b2 dy = p1 + a2 dx,
+                // de'/ddy = b2 dx + 2 c2 dy)
+                float absx = 0.0f, absy = 0.0f;
+                if constexpr (ABS) {
+                    const float2_b ex_dx = __builtin_elementwise_fma(float2_b{a.z, a.z}, d2, p1);
+                    const float cy = 2.0f * (a.w * dy);
+                    const float2_b ex_dy = __builtin_elementwise_fma(float2_b{b.x, b.x}, d2, float2_b{cy, cy});
+                    const float2_b ux = u * ex_dx, uy = u * ex_dy;
+                    absx = __builtin_fabsf(ux.x) + __builtin_fabsf(ux.y);
+                    absy = __builtin_fabsf(uy.x) + __builtin_fabsf(uy.y);
+                }
                 // ---- sum over the sub-block's 8 lanes; lane j of the group ends up with the pair of slots (2j, 2j+1) ----
                 {
                     // pairs: P0 (mx, my) P1 (mxx, mxy) P2 (myy, u) P3 (gz, -) P4..P7 payload channels 0..7
-                    constexpr uint32_t LIVE = 0x7u | (DEPTH_GRAD ? 0x8u : 0u) | (((1u << ((NCHP < 8 ? NCHP : 8) / 2)) - 1u) << 4);
+                    // (ABS: P7 (absx, absy) in place of payload channels 6, 7, which a 4-channel instance does not have)
+                    constexpr uint32_t LIVE = 0x7u | (DEPTH_GRAD ? 0x8u : 0u) | (((1u << ((NCHP < 8 ? NCHP : 8) / 2)) - 1u) << 4) | (ABS ? 0x80u : 0u);
 #define GP2(k) float2_b{(k) < NCHP ? gp[(k) % NCHP] : 0.0f, (k) + 1 < NCHP ? gp[((k) + 1) % NCHP] : 0.0f}
                     const float2_b tot = group_reduce_pairs<LIVE>(float2_b{mx, my}, float2_b{mxx, mxy}, float2_b{myy, usum}, float2_b{gz, 0.0f},
-                                                                  GP2(0), GP2(2), GP2(4), GP2(6), l8);
+                                                                  GP2(0), GP2(2), GP2(4), ABS ? float2_b{absx, absy} : GP2(6), l8);
                     // plain read-modify-write: only this wave touches its table and a wave's LDS operations
                     // execute in order
                     accumulate(row, acc_old[0], tot, LIVE >> l8 & 1u);
@@ -536,7 +555,7 @@ k_render_bwd(RenderBwdParams p) {
                 const uint32_t g = s_gid[e];
 #pragma unroll
                 for (int gi = 0; gi < NGRP; ++gi) {
-                    const bool mine = !kPackRow || l16 < 6 || (l16 >= 8 && l16 < 8 + NCHP);   // slots without a column in a packed row
+                    const bool mine = !kPackRow || l16 < 6 || (l16 >= 8 && l16 < 8 + NCHP) || (ABS && l16 >= 14);   // slots without a column in a packed row
                     const float val = mine ? s_acc[e][16 * gi + fcol] : 0.0f;
                     if (mine) s_acc[e][16 * gi + fcol] = 0.0f;
                     if (hit && val != 0.0f) {
@@ -569,7 +588,7 @@ hipError_t launch_clear_grad(const lsr_dims &d, char *grad, hipStream_t s) {
     return launch_clear(grad, grad_layout(d).total, s);
 }
 
-template <int NCHP, bool DG, int WPB>
+template <int NCHP, bool DG, int WPB, bool ABS = false>
 static void launch_variant(RenderBwdParams p, uint64_t items, hipStream_t s) {
     // list splitting: as many waves per half-tile item (a power of two, at most 8) as the launch's wave slots hold.
     // LSR_BWD_PARTS = log2 of the number of parts forces it (0: never split).
@@ -582,14 +601,14 @@ static void launch_variant(RenderBwdParams p, uint64_t items, hipStream_t s) {
     // issue priority by progress (see the kernel): on for the instances it was measured to help, LSR_BWD_PRIO_PCT >= 0 forces a value
     const int prio_knob = env_int("LSR_BWD_PRIO_PCT", -1);
     p.prio_pct = prio_knob >= 0 ? prio_knob : ((!DG && (NCHP == 4 || (NCHP == 8 && pl > 0))) ? 18 : 0);
-    if (pl) hipLaunchKernelGGL((k_render_bwd<NCHP, DG, WPB, true>), dim3(p.num_cus), dim3(LSR_WAVE * WPB), 0, s, p);
-    else hipLaunchKernelGGL((k_render_bwd<NCHP, DG, WPB, false>), dim3(p.num_cus), dim3(LSR_WAVE * WPB), 0, s, p);
+    if (pl) hipLaunchKernelGGL((k_render_bwd<NCHP, DG, WPB, true, ABS>), dim3(p.num_cus), dim3(LSR_WAVE * WPB), 0, s, p);
+    else hipLaunchKernelGGL((k_render_bwd<NCHP, DG, WPB, false, ABS>), dim3(p.num_cus), dim3(LSR_WAVE * WPB), 0, s, p);
 }
 
 hipError_t launch_render_backward(const lsr_dims &d, const lsr_inputs &in, const char *geom,
                                   const char *bin, int64_t num_pairs, const char *img,
                                   const lsr_outputs &fwd, const lsr_out_grads &gout, char *grad,
-                                  hipStream_t s) {
+                                  hipStream_t s, bool abs_grad) {
     const GeomLayout L = geom_layout(d);
     const ImgLayout I = img_layout(d);
     const BinLayout B = bin_layout(d, num_pairs, 0);
@@ -621,6 +640,7 @@ hipError_t launch_render_backward(const lsr_dims &d, const lsr_inputs &in, const
     const int nch = (p.has_color ? 3 : 0) + d.feat_channels;
     const int nchp = nch <= 4 ? 4 : (nch <= 8 ? 8 : (nch <= 12 ? 12 : 36));
     const bool dg = gout.depth != nullptr;
+    if (abs_grad && nchp != 4) return hipErrorInvalidValue;
     prof_begin(kStRenderBwd, s);
     const uint64_t items = 2ull * (uint64_t)d.num_views * (uint64_t)p.T;   // upper bound of the header's item count
 #define LSR_RB(N, WPB)                                      \
@@ -628,7 +648,9 @@ hipError_t launch_render_backward(const lsr_dims &d, const lsr_inputs &in, const
         if (dg) launch_variant<N, true, WPB>(p, items, s);  \
         else launch_variant<N, false, WPB>(p, items, s);    \
     } while (0)
-    if (nchp == 4) LSR_RB(4, 16);
+    // the ABS instances (lsr_backward_absgrad, which has turned wider payloads away): slots 14 / 15 collect the magnitudes
+    if (abs_grad) { if (dg) launch_variant<4, true, 16, true>(p, items, s); else launch_variant<4, false, 16, true>(p, items, s); }
+    else if (nchp == 4) LSR_RB(4, 16);
     // packed table rows: 16 waves per CU fit with 64-byte staged entries.  (Round 4: this instance shows 34 % LDS bank-conflict
     // cycles — eight lane groups reading eight 64-byte records start in one of only four bank groups — but the odd
     // 80-byte stride costs a wave: 15 waves 0.969-0.977 ms, 14 waves 1.02 against 0.945-0.954 at configs[4].)

@@ -155,13 +155,30 @@ class DensityControl:
         self.denom = torch.zeros((n, 1), dtype=torch.float32, device=dev)
         self.max_radii2D = torch.zeros((n,), dtype=torch.float32, device=dev)
 
+    def render(self, views: Tensor, height: int, width: int, absgrad: bool = False, **kw):
+        """The densification render: ``scene.render(views, height, width, **kw)`` with the per-view ``(V, n, 3)`` leaf whose
+        ``.grad`` :meth:`update` takes after the backward.  Returns ``(outputs, leaf)``.  ``absgrad=False``: the leaf is the
+        render's ``means2D`` (the signed gradient, the published statistic); ``absgrad=True``: its ``means2D_abs`` (the
+        absolute gradient of AbsGS, :func:`latentsplat_amd.rasterizer.rasterize_views`; colour-only renders, which a scene's
+        are)."""
+        leaf = torch.zeros((views.shape[0], self.scene.num_gaussians, 3), dtype=torch.float32, device=self.scene._xyz.device,
+                           requires_grad=True)
+        kw["means2D_abs" if absgrad else "means2D"] = leaf
+        return self.scene.render(views, height, width, **kw), leaf
+
     def update(self, means2D_grad: Tensor, radii: Tensor) -> None:
         """One step's statistics, one launch.  ``means2D_grad`` is the PER-VIEW ``(V, n, 3)`` gradient: render with
         ``means2D=torch.zeros(V, n, 3, requires_grad=True)`` and pass its ``.grad``; ``radii`` is the render's ``(V, n)``
         output.  Each view counts as one published ``add_densification_stats`` call, and the gradient is taken as it
         arrives (a loss that is a mean over ``V`` views gives each view ``1 / V`` of the published single-view
         gradient: scale the threshold, not the statistics).  A shared ``(n, 3)`` tensor has already summed the views
-        and is refused."""
+        and is refused.
+
+        The ABSOLUTE view-space gradient (AbsGS; gsplat's ``absgrad``) is fed the same way: render with
+        ``means2D_abs=torch.zeros(V, n, 3, requires_grad=True)`` (:meth:`render` with ``absgrad=True`` does) and pass that
+        leaf's ``.grad``.  Its per-pixel contributions do not cancel, so a large blurry splat reaches the threshold; the
+        values are larger than the signed gradient's, and the threshold has to follow (gsplat documents 8e-4 next to the
+        classic 2e-4)."""
         if torch.is_tensor(means2D_grad) and means2D_grad.dim() == 2:
             raise _lib.LsrError("DensityControl.update takes the per-view (V, n, 3) gradient; a shared (n, 3) means2D has "
                                 "already summed the views")

@@ -292,7 +292,7 @@ class _RasterizeViews(torch.autograd.Function):
     def forward(ctx, views, means3D, means2D, cov3D, opacities, shs, colors_precomp, features,
                 H: int, W: int, sh_degree: int, debug: bool, feat_sh_degree: int = -1,
                 shs_channel_major: bool = False, pair_capacity: int = 0, max_tile_hint: int = 0, grad_mode: bool = True,
-                antialiasing: bool = False):
+                antialiasing: bool = False, means2D_abs: Optional[Tensor] = None):
         lib = _lib.load()
         ctx.set_materialize_grads(False)  # unused outputs (mask / depth ...) arrive as None, not zeros
         dev = means3D.device
@@ -338,6 +338,14 @@ class _RasterizeViews(torch.autograd.Function):
         if Cf > _lib.MAX_FEAT_CHANNELS:
             raise LsrError(f"features has {Cf} channels; at most {_lib.MAX_FEAT_CHANNELS} are supported")
         K = 0 if shs is None else (shs.shape[-1] if shs_channel_major else shs.shape[-2])
+        if means2D_abs is not None:
+            # the absolute view-space gradient rides in the two record slots that are free up to 4 payload channels
+            nch = (3 if color is not None else 0) + Cf
+            if nch > _lib.ABSGRAD_MAX_CHANNELS:
+                raise LsrError(f"means2D_abs: {nch} payload channels; the absolute gradient is supported with at most "
+                               f"{_lib.ABSGRAD_MAX_CHANNELS} (colour counts 3)")
+            if tuple(means2D_abs.shape) not in ((V, G, 3), (G, 3)):
+                raise LsrError(f"means2D_abs: shape {tuple(means2D_abs.shape)}, expected {(V, G, 3)}")
         slices: list = []
         strides = (_stride(means3D, 2, V, "means3D", slices), _stride(cov3D, cov_base, V, "cov3D_precomp", slices),
                    _stride(opacities, 2, V, "opacities", slices),
@@ -467,6 +475,7 @@ class _RasterizeViews(torch.autograd.Function):
             _LAST_PLAN, _LAST_STATUS = None, dict(num_pairs=npairs.value, max_tile_pairs=maxtile.value, overflow=False)
         ctx.debug = debug
         ctx.m2d_shape = None if means2D is None else tuple(means2D.shape)
+        ctx.m2d_abs_shape = None if means2D_abs is None else tuple(means2D_abs.shape)
         ctx.has = (shs is not None, colors_precomp is not None, features is not None)
         ctx.mark_non_differentiable(radii)
         empty = views.new_empty(0)
@@ -505,6 +514,10 @@ class _RasterizeViews(torch.autograd.Function):
         d_feat = torch.empty_like(features) if has_f else None
         want_m2d = ctx.m2d_shape is not None and ctx.needs_input_grad[2]
         d_m2d = torch.empty((V, G, 3), **f32) if want_m2d else None   # 12 B per (view, Gaussian) nobody reads otherwise
+        # the absolute view-space gradient (lsr_backward_absgrad); without the argument: today's calls, bit for bit
+        abs_asked = ctx.m2d_abs_shape is not None and ctx.needs_input_grad[18]
+        want_abs = abs_asked and G > 0                                   # (no Gaussians: no rows, the classic call)
+        d_abs = torch.empty((V, G, 3), **f32) if abs_asked else None
         # the gradient workspace the forward zeroed; a second backward over the same graph (retain_graph) gets a fresh one
         # and has lsr_backward clear it itself (dims without the flag)
         gradws, plan.gradws = plan.gradws, None
@@ -520,7 +533,16 @@ class _RasterizeViews(torch.autograd.Function):
         stream = _args.stream(dev)
         d_views = None
         with torch.cuda.device(dev):
-            if ctx.needs_input_grad[0]:
+            if want_abs:
+                vgws = None
+                if ctx.needs_input_grad[0]:
+                    d_views = torch.empty((V, _lib.VIEW_FLOATS), **f32)
+                    vgws = torch.empty(lib.lsr_view_grad_workspace_bytes(C.byref(d)), dtype=torch.uint8, device=dev)
+                _lib.check(lib.lsr_backward_absgrad(C.byref(d), C.byref(inp), ptr(plan.geom), ptr(plan.bin), ptr(plan.img),
+                                                    plan.num_pairs, ptr(plan.radii), C.byref(fwd), C.byref(gout), ptr(gradws),
+                                                    C.byref(gin), ptr(d_views), ptr(vgws), ptr(d_abs), stream),
+                           "lsr_backward_absgrad")
+            elif ctx.needs_input_grad[0]:
                 # the camera gradient as well (lsr_backward_views): the same kernels' camera-gradient instances, then a
                 # fixed-order reduction of their partial records
                 d_views = torch.empty((V, _lib.VIEW_FLOATS), **f32)
@@ -538,10 +560,12 @@ class _RasterizeViews(torch.autograd.Function):
             d_m2d = None
         elif len(ctx.m2d_shape) == 2:  # one (G,3) tensor shared by the views
             d_m2d = d_m2d.sum(0) if V > 1 else d_m2d[0]
+        if abs_asked and len(ctx.m2d_abs_shape) == 2:  # one (G,3) tensor shared by the views
+            d_abs = d_abs.sum(0) if V > 1 else d_abs[0]
         # order: views, means3D, means2D, cov3D, opacities, shs, colors_precomp, features, H, W, deg,
-        #        debug, feat_sh_degree, shs_channel_major, pair_capacity, max_tile_hint, grad_mode, antialiasing
+        #        debug, feat_sh_degree, shs_channel_major, pair_capacity, max_tile_hint, grad_mode, antialiasing, means2D_abs
         return (d_views, d_means, d_m2d, d_cov, d_opac, d_color if has_shs else None,
-                d_color if has_cp else None, d_feat, None, None, None, None, None, None, None, None, None, None)
+                d_color if has_cp else None, d_feat, None, None, None, None, None, None, None, None, None, None, d_abs)
 
 
 def rasterize_views(views: Tensor, image_height: int, image_width: int, sh_degree: int, means3D: Tensor,
@@ -549,7 +573,8 @@ def rasterize_views(views: Tensor, image_height: int, image_width: int, sh_degre
                     colors_precomp: Optional[Tensor] = None, features: Optional[Tensor] = None,
                     means2D: Optional[Tensor] = None, debug: bool = False,
                     feature_sh: Optional[Tensor] = None, shs_channel_major: bool = False,
-                    pair_capacity: Optional[int] = None, max_tile_hint: int = 4096, antialiasing: bool = False):
+                    pair_capacity: Optional[int] = None, max_tile_hint: int = 4096, antialiasing: bool = False,
+                    means2D_abs: Optional[Tensor] = None):
     """Render V views in one call.  ``views`` is the (V,44) table of :func:`make_view_table`; every
     per-Gaussian tensor is either shared ``(G,...)`` or per view ``(V,G,...)``.
     Returns ``(color (V,3,H,W)|None, feature (V,C,H,W)|None, mask (V,H,W), depth (V,H,W), radii (V,G))``.
@@ -576,7 +601,15 @@ def rasterize_views(views: Tensor, image_height: int, image_width: int, sh_degre
     ``rasterize_mode="antialiased"``): every splat's opacity is multiplied by ``sqrt(max(0.000025, det0 / det))``, the
     determinants of its projected covariance before and after the 0.3 low-pass, so that a sub-pixel splat emits the light of
     its true extent instead of that of the dilated blob.  Radii and tile lists are those of the classic mode; the gradients of
-    means, covariances and the view table include the factor's."""
+    means, covariances and the view table include the factor's.
+
+    ``means2D_abs`` (optional, ``(V,G,3)``, requires grad) only exists to receive the ABSOLUTE view-space gradient (AbsGS;
+    gsplat's ``absgrad=True``; ``lsr_backward_absgrad``): per (view, Gaussian) the sum over the pixels of the magnitudes of
+    the per-pixel contributions to the ``means2D`` gradient, in the same units, where ``means2D.grad`` holds their signed sum
+    — in which the contributions of a large blurry splat cancel, so that :class:`~latentsplat_amd.density.DensityControl`
+    never splits it.  ``means2D_abs.grad >= |means2D.grad|`` component-wise; rows with ``radii == 0`` are 0.  Supported with
+    at most 4 payload channels (colour counts 3): more raise :class:`LsrError`.  Without the argument the call is the one it
+    always was."""
     V = views.shape[0]
     feat_sh_degree = -1
     if feature_sh is not None:
@@ -588,7 +621,8 @@ def rasterize_views(views: Tensor, image_height: int, image_width: int, sh_degre
     color, feat, mask, depth, radii = _RasterizeViews.apply(
         views, means3D, means2D, cov3D_precomp, opacities, shs, colors_precomp, features,
         int(image_height), int(image_width), int(sh_degree), bool(debug), int(feat_sh_degree),
-        bool(shs_channel_major), int(pair_capacity or 0), int(max_tile_hint), torch.is_grad_enabled(), bool(antialiasing))
+        bool(shs_channel_major), int(pair_capacity or 0), int(max_tile_hint), torch.is_grad_enabled(), bool(antialiasing),
+        means2D_abs)
     return (color if color.numel() else None, feat if feat.numel() else None, mask, depth, radii)
 
 
@@ -687,7 +721,9 @@ class GaussianRasterizer(nn.Module):
             return z > _NEAR_CULL
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, features=None,
-                scales=None, rotations=None, cov3D_precomp=None):
+                scales=None, rotations=None, cov3D_precomp=None, means2D_abs=None):
+        """``means2D_abs`` (optional, ``(G,3)`` like ``means2D``, or ``(1,G,3)``): its ``.grad`` receives the absolute
+        view-space gradient (:func:`rasterize_views`)."""
         rs = self.raster_settings
         if shs is not None and colors_precomp is not None:
             raise Exception("Please provide at most one of SHs / precomputed colors!")
@@ -700,6 +736,6 @@ class GaussianRasterizer(nn.Module):
         color, feat, mask, depth, radii = _RasterizeViews.apply(
             views, means3D, means2D, cov3D_precomp, opacities, shs, colors_precomp, features,
             int(rs.image_height), int(rs.image_width), int(rs.sh_degree), bool(rs.debug), -1, False, 0, 0, torch.is_grad_enabled(),
-            bool(rs.antialiasing))
+            bool(rs.antialiasing), means2D_abs)
         return (color[0] if color.numel() else None, feat[0] if feat.numel() else None,
                 mask, depth, radii[0])

@@ -60,6 +60,12 @@ opacities and scales, which any viewer shows filtered.  `fit.json` then holds `f
 `--antialiasing` renders the targets and every step of the fit with the rasterizer's opacity compensation for its 0.3
 screen-space low-pass (the published trainer's `--antialiasing`); `fit.json` holds `antialiasing`.
 
+`--absgrad` (with `--densify-interval`) densifies on the ABSOLUTE view-space gradient of AbsGS (gsplat's
+`absgrad`): the densification render also passes a per-view `(V, n, 3)` `means2D_abs`, and `DensityControl.update` gets ITS
+gradient — the sum over the pixels of the magnitudes of their contributions, in which a large blurry splat's contributions do
+not cancel.  `--densify-grad-threshold` then defaults to `8e-4 / views`, gsplat's documented companion value divided by the
+views as above: a default, not a measurement.  `fit.json` holds `absgrad`.
+
 `--bilateral-grid X Y L` trains with bilateral-grid appearance compensation (`latentsplat_amd.BilateralGrid`):
 every fitted render goes through one X x Y x L grid of colour affines per view before the loss (`1 1 1`: one affine per view,
 the published trainer's exposure compensation; `16 16 8`: the published grid), `--tv-weight` (default 10, the published one)
@@ -76,7 +82,7 @@ usage: python tools/fit_ply.py scene.ply --out DIR [--views 8] [--size 256] [--s
                                [--optimizer torch|fused|sparse] [--lr-position-final F] [--lr-position-max-steps S]
                                [--from-points] [--sh-degree-interval 0]
                                [--strategy adc|mcmc] [--cap-max N] [--noise-lr 5e5] [--opacity-reg 0.01] [--scale-reg 0.01]
-                               [--filter-3d] [--filter-3d-interval 100] [--antialiasing]
+                               [--filter-3d] [--filter-3d-interval 100] [--antialiasing] [--absgrad]
                                [--bilateral-grid X Y L] [--bilateral-grid-lr 2e-3] [--tv-weight 10] [--target-jitter 0]"""
 from __future__ import annotations
 
@@ -132,7 +138,7 @@ def main(argv=None) -> dict:
     ap.add_argument("--densify-from", type=int, default=0, help="no densification before this step")
     ap.add_argument("--densify-until", type=int, default=None, help="no densification (and no statistics) after this step (default: --steps)")
     ap.add_argument("--densify-grad-threshold", type=float, default=None,
-                    help="on the mean view-space gradient (default 2e-4 / --views: a default, not a measurement)")
+                    help="on the mean view-space gradient (default 2e-4 / --views, with --absgrad 8e-4 / --views: defaults, not measurements)")
     ap.add_argument("--min-opacity", type=float, default=0.005, help="Gaussians below it are pruned at a densification")
     ap.add_argument("--opacity-reset-interval", type=int, default=0, help="reset the opacities every this many steps (0: never)")
     ap.add_argument("--from-points", action="store_true",
@@ -148,6 +154,8 @@ def main(argv=None) -> dict:
                     help="train with the 3D smoothing filter of Mip-Splatting and also write point_cloud_fused.ply")
     ap.add_argument("--antialiasing", action="store_true",
                     help="render with opacity compensation for the 0.3 screen-space low-pass (default: the classic mode)")
+    ap.add_argument("--absgrad", action="store_true",
+                    help="densify on the absolute view-space gradient (AbsGS): means2D_abs of the render instead of means2D")
     ap.add_argument("--filter-3d-interval", type=int, default=100, help="recompute the 3D filter every this many steps (the published cadence)")
     ap.add_argument("--bilateral-grid", type=int, nargs=3, default=None, metavar=("X", "Y", "L"),
                     help="one X x Y x L bilateral grid of colour affines per view between render and loss (default: none; "
@@ -226,7 +234,8 @@ def main(argv=None) -> dict:
         from latentsplat_amd.density import DensityControl
         control = DensityControl(scene)
         until = a.steps if a.densify_until is None else a.densify_until
-        threshold = 2e-4 / a.views if a.densify_grad_threshold is None else a.densify_grad_threshold
+        # (8e-4: the value gsplat documents next to absgrad; like 2e-4 a default, not a measurement)
+        threshold = (8e-4 if a.absgrad else 2e-4) / a.views if a.densify_grad_threshold is None else a.densify_grad_threshold
     grids, tv = None, None
     if a.bilateral_grid is not None:
         from latentsplat_amd.bilagrid import BilateralGrid
@@ -253,8 +262,9 @@ def main(argv=None) -> dict:
         opt.zero_grad(set_to_none=True)
         if densify and step < until:
             means2D = torch.zeros((a.views, scene.num_gaussians, 3), device=dev, requires_grad=True)
+            stat = dict(means2D_abs=torch.zeros_like(means2D, requires_grad=True)) if a.absgrad else {}
             render, _, _, _, radii = scene.render(views, a.size, a.size, filter_3d=filter_3d, means2D=means2D,
-                                                    antialiasing=a.antialiasing)
+                                                    antialiasing=a.antialiasing, **stat)
         else:
             means2D = None
             render, _, _, _, radii = scene.render(views, a.size, a.size, filter_3d=filter_3d, antialiasing=a.antialiasing)
@@ -280,7 +290,7 @@ def main(argv=None) -> dict:
         losses.append(loss.detach())
         if means2D is not None:
             done = step + 1
-            control.update(means2D.grad, radii)
+            control.update(stat["means2D_abs"].grad if a.absgrad else means2D.grad, radii)
             if done > a.densify_from and done % a.densify_interval == 0:
                 size = 20.0 if a.opacity_reset_interval and done > a.opacity_reset_interval else 0.0
                 counts = control.densify_and_prune(opt, threshold, a.min_opacity, float(extent), size, generator=gen_dev)
@@ -306,7 +316,7 @@ def main(argv=None) -> dict:
                timed_steps=a.steps - warm, gaussians=scene.num_gaussians, sh_degree=scene.max_sh_degree, views=a.views,
                size=a.size, noise=a.noise, seed=a.seed, extent=float(extent), lambda_dssim=a.lambda_dssim, optimizer=a.optimizer,
                from_points=bool(a.from_points), active_sh_degree_last=scene.active_sh_degree,
-               antialiasing=bool(a.antialiasing))
+               antialiasing=bool(a.antialiasing), absgrad=bool(a.absgrad))
     if densify:
         res.update(gaussians_first=gaussians_first, gaussians_last=scene.num_gaussians, densify_events=events)
     if mcmc is not None:
