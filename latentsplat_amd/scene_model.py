@@ -369,6 +369,12 @@ class GaussianScene(nn.Module):
         :func:`latentsplat_amd.transform.transform_scene`, then through the unchanged activation.  With ``poses`` (a
         :class:`latentsplat_amd.pose.PartPoses`) instead: through :func:`latentsplat_amd.pose.pose_scene`, which also hands
         the poses their gradient."""
+        xyz, rest, scaling, rotation = self._posed_parameters(transforms, transform_idx, filter_3d, check, poses)
+        return xyz, _ActivateScene.apply(self._features_dc, rest, self._opacity, scaling, rotation, float(scale_modifier), geometry)
+
+    def _posed_parameters(self, transforms: Optional[Tensor], transform_idx: Optional[Tensor], filter_3d, check: bool = True,
+                          poses=None):
+        """The raw parameters of the posed scene, ``(xyz, features_rest, scaling, rotation)``: what :meth:`_posed` activates."""
         from .transform import transform_scene
         if poses is not None and transforms is not None:
             raise _lib.LsrError("poses together with transforms: a scene is posed by one or the other (poses are the "
@@ -381,11 +387,8 @@ class GaussianScene(nn.Module):
             raise _lib.LsrError("a GaussianScene is activated and rendered on the MI355X: move it to a ROCm ('cuda') device; "
                                 "there is no CPU fallback")
         if poses is not None:
-            xyz, rest, scaling, rotation = poses(self._xyz, self._features_rest, self._scaling, self._rotation, transform_idx)
-        else:
-            xyz, rest, scaling, rotation = transform_scene(self._xyz, self._features_rest, self._scaling, self._rotation,
-                                                           transforms, transform_idx, check=check)
-        return xyz, _ActivateScene.apply(self._features_dc, rest, self._opacity, scaling, rotation, float(scale_modifier), geometry)
+            return poses(self._xyz, self._features_rest, self._scaling, self._rotation, transform_idx)
+        return transform_scene(self._xyz, self._features_rest, self._scaling, self._rotation, transforms, transform_idx, check=check)
 
     def activated(self, scale_modifier: float = 1.0, filter_3d: Optional[Tensor] = None, transforms: Optional[Tensor] = None,
                   transform_idx: Optional[Tensor] = None, check_transforms: bool = True, poses=None) -> Scene3DGS:
@@ -435,6 +438,42 @@ class GaussianScene(nn.Module):
             return rasterize_views(views, height, width, self.active_sh_degree, xyz, cov, opacities, shs=shs, **kw)
         shs, opacities, cov, _, _ = self._activate(scale_modifier, False, filter_3d)
         return rasterize_views(views, height, width, self.active_sh_degree, self._xyz, cov, opacities, shs=shs, **kw)
+
+    def render_with_normals(self, views: Tensor, height: int, width: int, scale_modifier: float = 1.0,
+                            filter_3d: Optional[Tensor] = None, transforms: Optional[Tensor] = None,
+                            transform_idx: Optional[Tensor] = None, check_transforms: bool = True, poses=None,
+                            antialiasing: bool = False, **kw):
+        """:meth:`render` with the normals of the Gaussians (:func:`latentsplat_amd.normals.gaussian_normals`: the shortest
+        axis of each, turned toward the camera, in camera space) as the ``features`` payload:
+        ``(color, normal_map, mask, depth, radii)``.  ``normal_map (V, 3, H, W)`` is the blended sum of alpha T n (background
+        0, not renormalised), which with ``depth`` and ``mask`` is what
+        :func:`latentsplat_amd.normals.normal_consistency_loss` takes.  Every keyword is :meth:`render`'s.
+
+        With ``transforms`` / ``poses`` the normals are those of the POSED raw scaling and rotation.  The payload is taken,
+        so a caller's own ``features`` / ``feature_sh`` is refused.  Colour and normals are six payload channels: with
+        ``means2D_abs`` the rasterizer's refusal of more than 4 payload channels applies unchanged (take the absolute
+        gradient from a plain :meth:`render`).  The view table must carry depth mode NATIVE (what ``build_view_table`` /
+        ``make_view_table`` write by default): the loss reads ``depth`` as the blended view-space z; nothing is read back to
+        check it.  The normals hand a gradient to ``_rotation`` alone (the argmin and the sign are piecewise constant);
+        every other gradient is the rasterizer's."""
+        from .normals import gaussian_normals
+        from .rasterizer import rasterize_views
+        if kw.get("features") is not None or kw.get("feature_sh") is not None:
+            raise _lib.LsrError("render_with_normals: the features payload carries the normals; features / feature_sh of the "
+                                "caller's own are refused (render them with render)")
+        kw.pop("features", None)
+        kw.pop("feature_sh", None)
+        if antialiasing:
+            kw["antialiasing"] = True
+        if transforms is not None or poses is not None:
+            xyz, rest, scaling, rotation = self._posed_parameters(transforms, transform_idx, filter_3d, check_transforms, poses)
+            shs, opacities, cov, _, _ = _ActivateScene.apply(self._features_dc, rest, self._opacity, scaling, rotation,
+                                                             float(scale_modifier), False)
+        else:
+            xyz, scaling, rotation = self._xyz, self._scaling, self._rotation
+            shs, opacities, cov, _, _ = self._activate(scale_modifier, False, filter_3d)
+        normals = gaussian_normals(views, xyz, scaling, rotation)
+        return rasterize_views(views, height, width, self.active_sh_degree, xyz, cov, opacities, shs=shs, features=normals, **kw)
 
     def transform_(self, M: Tensor, idx: Optional[Tensor] = None) -> "GaussianScene":
         """Move the scene in place by the similarity ``M (4, 4)`` (or ``(T, 4, 4)`` with ``idx (n,)`` naming the transform

@@ -76,6 +76,13 @@ per-channel affine (gain uniform in [1 - S, 1 + S], offset uniform in [-S / 4, S
 that disagree, for the grids to absorb.  `fit.json` then holds `bilateral_grid`, `tv_weight` and `tv_last`, and/or
 `target_jitter`; `bilateral_grids.pt` holds the module's state dict.
 
+`--normal-reg W` with W > 0 adds W times the depth-normal consistency loss: from step `--normal-reg-from`
+(default 0) on, every step renders with `GaussianScene.render_with_normals` and `normal_consistency_loss` compares the blended
+normals with the normals of the rendered depth at the pixels covered more than `--normal-alpha-min` (default 0.5: a default,
+not a measurement).  `--flatten-reg W` adds W times `flatten_loss`, the mean shortest extent.  Together with `--absgrad` the
+normal term is refused (six payload channels).  `fit.json` then holds the four values and `normal_loss_first / _last`.
+Without the two weights the run is the one it was.
+
 usage: python tools/fit_ply.py scene.ply --out DIR [--views 8] [--size 256] [--steps 200] [--noise 1.0] [--seed 0] [--distance 2.5]
                                [--lambda-dssim 0.0] [--drop 0.0] [--densify-interval 0] [--densify-from 0] [--densify-until STEPS]
                                [--densify-grad-threshold 2e-4/VIEWS] [--min-opacity 0.005] [--opacity-reset-interval 0]
@@ -83,7 +90,8 @@ usage: python tools/fit_ply.py scene.ply --out DIR [--views 8] [--size 256] [--s
                                [--from-points] [--sh-degree-interval 0]
                                [--strategy adc|mcmc] [--cap-max N] [--noise-lr 5e5] [--opacity-reg 0.01] [--scale-reg 0.01]
                                [--filter-3d] [--filter-3d-interval 100] [--antialiasing] [--absgrad]
-                               [--bilateral-grid X Y L] [--bilateral-grid-lr 2e-3] [--tv-weight 10] [--target-jitter 0]"""
+                               [--bilateral-grid X Y L] [--bilateral-grid-lr 2e-3] [--tv-weight 10] [--target-jitter 0]
+                               [--normal-reg 0] [--normal-reg-from 0] [--normal-alpha-min 0.5] [--flatten-reg 0]"""
 from __future__ import annotations
 
 import argparse
@@ -162,11 +170,22 @@ def main(argv=None) -> dict:
                          "1 1 1: one affine per view; 16 16 8: the published grid)")
     ap.add_argument("--bilateral-grid-lr", type=float, default=2e-3, help="Adam rate of the grids (the published default, not a measurement)")
     ap.add_argument("--tv-weight", type=float, default=10.0, help="weight of the grids' total variation in the loss (the published default)")
+    ap.add_argument("--normal-reg", type=float, default=0.0,
+                    help="weight of the depth-normal consistency loss (0: off, the default): every step renders the normals of "
+                         "the Gaussians next to the colour and compares them with the normals of the rendered depth")
+    ap.add_argument("--normal-reg-from", type=int, default=0, help="no normal consistency loss before this step")
+    ap.add_argument("--normal-alpha-min", type=float, default=0.5,
+                    help="pixels the scene covers less than this take no part in the normal loss (a default, not a measurement)")
+    ap.add_argument("--flatten-reg", type=float, default=0.0, help="weight of mean(min_k exp(scaling)) in the loss (0: off, the default)")
     ap.add_argument("--target-jitter", type=float, default=0.0,
                     help="S > 0: a seeded per-channel affine on every target view, gain in [1 - S, 1 + S], offset in [-S / 4, S / 4] (default 0: none)")
     a = ap.parse_args(argv)
     if a.steps < 1 or a.views < 1:
         sys.exit("fit_ply needs at least one step and one view")
+    if a.normal_reg < 0.0 or a.flatten_reg < 0.0 or not a.normal_alpha_min > 0.0:
+        sys.exit("--normal-reg and --flatten-reg must not be negative and --normal-alpha-min must be positive")
+    if a.normal_reg > 0.0 and a.absgrad:
+        sys.exit("--normal-reg with --absgrad: colour and normals are six payload channels, the absolute gradient takes at most four")
     if not 0.0 <= a.lambda_dssim <= 1.0:
         sys.exit("--lambda-dssim must be in [0, 1]")
     if not 0.0 <= a.drop < 1.0 or a.densify_interval < 0 or a.opacity_reset_interval < 0 or a.sh_degree_interval < 0:
@@ -185,6 +204,7 @@ def main(argv=None) -> dict:
         sys.exit("fit_ply needs an MI355X: no ROCm device is visible (there is no CPU fallback)")
     from latentsplat_amd.rasterizer import build_view_table
     from latentsplat_amd.losses import photometric_loss
+    from latentsplat_amd.normals import flatten_loss, normal_consistency_loss
     from latentsplat_amd.optim import SceneAdam, expon_lr, visible_from_radii
     from latentsplat_amd.scene_model import GaussianScene
     dev = torch.device("cuda:0")
@@ -253,27 +273,36 @@ def main(argv=None) -> dict:
 
     refresh_filter(0, "start")
     warm = min(WARMUP_STEPS, a.steps // 2)
-    losses = []
+    losses, normal_losses = [], []
     t0 = None
     for step in range(a.steps):
         if step == warm:
             torch.cuda.synchronize(dev)
             t0 = time.perf_counter()
         opt.zero_grad(set_to_none=True)
+        with_normals = a.normal_reg > 0.0 and step >= a.normal_reg_from
+        render_scene = scene.render_with_normals if with_normals else scene.render      # (without --normal-reg: the call it was)
         if densify and step < until:
             means2D = torch.zeros((a.views, scene.num_gaussians, 3), device=dev, requires_grad=True)
             stat = dict(means2D_abs=torch.zeros_like(means2D, requires_grad=True)) if a.absgrad else {}
-            render, _, _, _, radii = scene.render(views, a.size, a.size, filter_3d=filter_3d, means2D=means2D,
-                                                    antialiasing=a.antialiasing, **stat)
+            render, normal_map, mask, depth, radii = render_scene(views, a.size, a.size, filter_3d=filter_3d, means2D=means2D,
+                                                                  antialiasing=a.antialiasing, **stat)
         else:
             means2D = None
-            render, _, _, _, radii = scene.render(views, a.size, a.size, filter_3d=filter_3d, antialiasing=a.antialiasing)
+            render, normal_map, mask, depth, radii = render_scene(views, a.size, a.size, filter_3d=filter_3d,
+                                                                  antialiasing=a.antialiasing)
         if grids is not None:
             grid_opt.zero_grad(set_to_none=True)
             render = grids(render, view_idx)
         loss = photometric_loss(render, target, a.lambda_dssim) if a.lambda_dssim > 0 else (render - target).abs().mean()
         if mcmc is not None:
             loss = loss + mcmc.regularizer(a.opacity_reg, a.scale_reg)
+        if with_normals:
+            normal_loss = normal_consistency_loss(normal_map, depth, mask, views, a.normal_alpha_min)
+            normal_losses.append(normal_loss.detach())
+            loss = loss + a.normal_reg * normal_loss
+        if a.flatten_reg > 0.0:
+            loss = loss + a.flatten_reg * flatten_loss(scene._scaling)
         if grids is not None:
             tv = grids.tv_loss()
             loss = loss + a.tv_weight * tv
@@ -317,6 +346,11 @@ def main(argv=None) -> dict:
                size=a.size, noise=a.noise, seed=a.seed, extent=float(extent), lambda_dssim=a.lambda_dssim, optimizer=a.optimizer,
                from_points=bool(a.from_points), active_sh_degree_last=scene.active_sh_degree,
                antialiasing=bool(a.antialiasing), absgrad=bool(a.absgrad))
+    if a.normal_reg > 0.0 or a.flatten_reg > 0.0:
+        res.update(normal_reg=a.normal_reg, normal_reg_from=a.normal_reg_from, normal_alpha_min=a.normal_alpha_min,
+                   flatten_reg=a.flatten_reg)
+        if normal_losses:
+            res.update(normal_loss_first=float(normal_losses[0]), normal_loss_last=float(normal_losses[-1]))
     if densify:
         res.update(gaussians_first=gaussians_first, gaussians_last=scene.num_gaussians, densify_events=events)
     if mcmc is not None:

@@ -12,9 +12,12 @@
 Files written by this project's own `export_ply` store the opacity as it is: pass `--opacity raw` for those.
 `--antialiasing` renders with the rasterizer's opacity compensation for its 0.3 screen-space low-pass (INTEGRATION.md §21);
 `status.json` holds `antialiasing`.
+`--normals OUT.npy` also writes `(2, V, 3, H, W)`: the rendered normal map (the Gaussians' shortest axes, turned toward the
+camera, blended as a payload and divided by the mask where it exceeds `--normal-alpha-min`) and the normals of the rendered
+depth (`depth_to_normals`, 0 where invalid) of the same views, both in camera space.
 
 usage: python tools/render_ply.py scene.ply --out renders [--views 8] [--size 256] [--distance 2.5] [--opacity logit]
-                                  [--antialiasing]"""
+                                  [--antialiasing] [--normals OUT.npy] [--normal-alpha-min 0.5]"""
 from __future__ import annotations
 
 import argparse
@@ -72,6 +75,9 @@ def main(argv=None) -> dict:
     ap.add_argument("--background", type=float, nargs=3, default=(0.0, 0.0, 0.0))
     ap.add_argument("--antialiasing", action="store_true",
                     help="opacity compensation for the 0.3 screen-space low-pass (default: the classic mode)")
+    ap.add_argument("--normals", default=None, metavar="OUT.npy",
+                    help="also write the rendered normal map and the normals of the rendered depth, (2, V, 3, H, W)")
+    ap.add_argument("--normal-alpha-min", type=float, default=0.5, help="(a default, not a measurement)")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         sys.exit("render_ply needs an MI355X: no ROCm device is visible (there is no CPU fallback)")
@@ -90,6 +96,15 @@ def main(argv=None) -> dict:
             color, _, mask, depth, radii = rasterize_views(views, a.size, a.size, s.sh_degree, s.means, s.covariances,
                                                            s.opacities, shs=s.shs, antialiasing=a.antialiasing)
             status = last_forward_status()
+            if a.normals:       # a second render with the normals as the payload (depth and mask are the first one's)
+                from latentsplat_amd.normals import depth_to_normals, gaussian_normals
+                payload = gaussian_normals(views, s.means, s.scales, s.rotations)
+                normal_map = rasterize_views(views, a.size, a.size, s.sh_degree, s.means, s.covariances, s.opacities, shs=s.shs,
+                                             features=payload, antialiasing=a.antialiasing)[1]
+                covered = (mask > a.normal_alpha_min)[:, None]
+                normal_map = torch.where(covered, normal_map / mask[:, None].clamp_min(1e-12), torch.zeros_like(normal_map))
+                from_depth, _ = depth_to_normals(depth, mask, views, a.normal_alpha_min)
+                both = torch.stack([normal_map, from_depth])
             depth = depth * near[:, None, None]        # (the table rescales the scene so that near == 1)
     finally:
         set_color_sh_convention(convention)
@@ -97,6 +112,8 @@ def main(argv=None) -> dict:
     np.save(os.path.join(a.out, "color.npy"), color.cpu().numpy())
     np.save(os.path.join(a.out, "mask.npy"), mask.cpu().numpy())
     np.save(os.path.join(a.out, "depth.npy"), depth.cpu().numpy())
+    if a.normals:
+        np.save(a.normals, both.cpu().numpy())
     status = dict(status, gaussians=int(s.means.shape[0]), sh_degree=int(s.sh_degree), views=a.views, size=a.size,
                   visible=[int(v) for v in (radii > 0).sum(dim=1).tolist()], centre=[float(c) for c in centre.tolist()],
                   extent=float(extent), antialiasing=bool(a.antialiasing))
