@@ -9,6 +9,26 @@ R = 5
 TAPS = 2 * R + 1
 C1, C2 = 0.01 ** 2, 0.03 ** 2
 TILE = 32            # kPhTile of csrc/photometric.hip: output pixels per tile, each way
+WAVE = 64            # lanes of a wave: k_photo_finish adds the slots of an image WAVE at a time ...
+FINISH_WAVES = 16    # ... and its 1024 lanes are 16 waves, wave w taking the images w, w + 16, ...
+
+
+def photo_shift(H: int, W: int) -> float:
+    """photo_shift of csrc/photometric.hip: the constant both kernels subtract from the images, 0.5 times the image's share
+    of its zero-padded extent, to the nearest eighth."""
+    share = H * W / ((H + 2.0 * R) * (W + 2.0 * R))
+    return math.floor(4.0 * share + 0.5) / 8.0
+
+
+def tile_grid(H: int, W: int):
+    """(tiles_y, tiles_x) of one plane."""
+    return (H + TILE - 1) // TILE, (W + TILE - 1) // TILE
+
+
+def slots_per_image(shape) -> int:
+    """Workspace slots k_photo_finish adds per image of a ``(V, C, H, W)`` call: one per tile of every plane."""
+    ty, tx = tile_grid(*shape[2:])
+    return shape[1] * ty * tx
 
 
 def window() -> np.ndarray:

@@ -12,6 +12,7 @@ lsr_bilagrid_slice_path:
   * 16 x 16 pixel tiles, footprint in LDS: default_64 (a 32-tile would reach 800 nodes), default_33x65 (partial tiles both ways);
   * no tile's footprint fits, the parameter read and its gradient added in global memory: grid_wider_than_image, largest_8,
     largest_40 (nine 16-tiles, the outer ones partial)."""
+import functools
 import json
 import os
 import sys
@@ -57,6 +58,37 @@ def test_matches_float64_within_the_stock_compositions_error(hip_device, name):
     for n in range(ref.CASES[name][3]):
         if n not in idx:
             assert not grad_grids[n].any(), (name, n)
+
+
+TV_BLOCK_ELEMS, TV_MAX_BLOCKS = 256 * 8, 1024       # kBgThreads * kTvPerThread, kTvMaxBlocks of csrc/bilagrid.hip
+TV_PAST_THE_GRID = (3, 12, 16, 64, 64)              # no image goes with it: a case of its own, beside ref.CASES
+
+
+@functools.lru_cache(maxsize=None)
+def _tv_past_the_grid():
+    """Seeded grids past the capped grid of the two total-variation kernels, the float64 restatement and the stock float32
+    loop: computed once, shared, never modified."""
+    g = torch.Generator().manual_seed(4242 + len(ref.CASES))
+    grids = torch.eye(3, 4).reshape(1, 12, 1, 1, 1) + 0.3 * torch.randn(*TV_PAST_THE_GRID, generator=g)
+    up = 1.7
+    want, yard = ref.restate_tv(grids, up), ref.stock_tv(grids, up, dtype=torch.float32)
+    return grids, up, {k: v.numpy() for k, v in want.items()}, {k: v.numpy() for k, v in yard.items()}
+
+
+def test_total_variation_past_the_grid_cap(hip_device):
+    """Both kernels launch one workgroup per 2048 elements, at most 1024, and a lane strides over all the launch's lanes: up
+    to the cap a lane takes at most eight elements whatever the size (786 432 floats, the largest grid of ref.CASES, are 384
+    workgroups); 2 359 296 floats would be 1152 workgroups, run on 1024, and every lane takes a ninth element."""
+    from latentsplat_amd import bilagrid as bg
+    grids, up, want, yard = _tv_past_the_grid()
+    assert grids.numel() == 2_359_296 > TV_BLOCK_ELEMS * TV_MAX_BLOCKS
+    assert max(int(np.prod(c[0])) * 12 * c[3] for c in ref.CASES.values()) == 786_432 < TV_BLOCK_ELEMS * TV_MAX_BLOCKS
+    d = grids.to(hip_device)
+    grad_tv = torch.full((1,), up, device=hip_device)
+    tv, grad = bg.tv_forward(d), bg.tv_backward(d, grad_tv)
+    ref.held("tv", tv.cpu().numpy(), want["tv"], yard["tv"], "tv past the grid:")
+    ref.held("grad_tv", grad.cpu().numpy(), want["grad"], yard["grad"], "tv past the grid:")
+    assert torch.equal(_bits(tv), _bits(bg.tv_forward(d))) and torch.equal(_bits(grad), _bits(bg.tv_backward(d, grad_tv)))
 
 
 def test_forward_gives_the_same_bits_every_call_and_on_a_side_stream(hip_device):

@@ -10,7 +10,9 @@ inputs, with a floor of 2^-20 of the quantity's scale (its largest magnitude).  
 Sizes: the constants of csrc/density.hip are kPlanChunk = 256 Gaussians per classify / emit workgroup, kPlanScanThreads =
 256 lanes of the one workgroup that scans the chunk sums, kApplyElems = 4096 destination floats per gather workgroup and
 kDensityThreads = 256 per accumulate workgroup.  70 001 Gaussians are 274 chunks: more than one workgroup in every
-kernel, and more chunk sums than scan lanes, so that lanes walk two sums each (the scan's second level)."""
+kernel, and more chunk sums than scan lanes, so that lanes walk two sums each (the scan's second level).  524 291
+Gaussians (PAST_THE_GRID, one accumulate and one plan-and-apply case) are past the accumulate grid's cap of 2048
+workgroups and are 2049 chunks, nine sums per scan lane: the trips a scene of half a million Gaussians takes."""
 import functools
 import json
 import os
@@ -31,6 +33,11 @@ PLAN_CHUNK, SCAN_THREADS, APPLY_ELEMS = 256, 256, 4096
 BIG = 70_001
 assert BIG > PLAN_CHUNK * SCAN_THREADS and 3 * BIG > APPLY_ELEMS
 SIZES = [0, 1, 63, 64, 65, 255, 257, 1000, BIG]
+# The accumulate grid is capped at kDensityMaxBlocks = 2048 workgroups of 256 lanes; past that, lanes take a second row.
+# The same size is 2049 chunks of the plan: each lane of the scan walks ceil(2049 / 256) = 9 chunk sums, the last lanes
+# none.  One case each, outside the cross-products, on the narrowest tables (K = 1).
+GRID_ROWS = 2048 * 256
+PAST_THE_GRID = GRID_ROWS + 3
 SH_COEFFS = (1, 4, 16)
 FLOOR = 2.0 ** -20
 MARGIN = 4.0
@@ -73,6 +80,17 @@ def _stats_case(n, V):
 @pytest.mark.parametrize("V", [1, 4, 16])
 @pytest.mark.parametrize("n", SIZES)
 def test_accumulate_matches(hip_device, n, V):
+    _check_accumulate(hip_device, n, V)
+
+
+def test_accumulate_past_the_grid_cap(hip_device):
+    """2049 workgroups' worth of rows on a grid capped at 2048: the first three lanes take a second row."""
+    _, _, start, want, _ = _stats_case(PAST_THE_GRID, 2)
+    assert (want[1][GRID_ROWS:] != start[1][GRID_ROWS:]).any()             # ... and those rows have something to add
+    _check_accumulate(hip_device, PAST_THE_GRID, 2)
+
+
+def _check_accumulate(hip_device, n, V):
     from latentsplat_amd import accumulate_density_stats
     grad, radii, start, want, stock = _stats_case(n, V)
     runs = []
@@ -223,6 +241,20 @@ def test_both_moment_settings_and_every_width_meet_the_large_size(hip_device):
         inp, thr, map_, counts, eps, moments, rows, stock = _case(BIG, N, True, K)
         show = f"n={BIG} N={N} K={K} with moments:"
         _check(BIG, N, _run(hip_device, inp, thr, N, eps, moments), inp, map_, counts, moments, rows, stock, show)
+
+
+def test_plan_and_apply_past_256_chunks_per_scan_lane(hip_device):
+    """PAST_THE_GRID rows are 2049 chunks: k_densify_scan's first 228 lanes walk nine sums each (the last of them six) and the rest none.  K = 1
+    (no f_rest), N = 2, size pruning on, with the moments: the map and the counts exact, the children on the bar."""
+    n, N, K = PAST_THE_GRID, 2, 1
+    chunks = -(-n // PLAN_CHUNK)
+    assert chunks == 2049 and -(-chunks // SCAN_THREADS) == 9
+    inp, thr, map_, counts, eps, moments, rows, stock = _case(n, N, True, K)
+    show = f"n={n} N={N} size=True K={K} moments=True:"
+    got = _run(hip_device, inp, thr, N, eps, moments)
+    print(show, "counts", got[1].tolist(), ref.outcomes(map_, n))
+    assert min(ref.outcomes(map_, n).values()) > 0
+    _check(n, N, got, inp, map_, counts, moments, rows, stock, show)
 
 
 SPECIAL = dict(

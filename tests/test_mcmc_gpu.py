@@ -14,7 +14,8 @@ classification, sources), kMcmcScanThreads = 256 lanes of the one workgroup that
 per draw / noise / destination workgroup and kMcmcApplyElems = 2048 destination floats per workgroup.  70 001 rows are 274
 chunks: more than one workgroup in every kernel, and more chunk sums than scan lanes, so that lanes walk two sums each
 (the scan's second level); its n / 20 = 3500 draws are 14 draw workgroups and, three floats wide, 6 destination
-workgroups."""
+workgroups.  524 291 rows (PAST_THE_GRID: sampling, classification and noise, one case each) are 2049 chunks, nine sums
+per scan lane, and past the noise grid's cap of 2048 workgroups: the trips a scene of half a million Gaussians takes."""
 import functools
 import json
 import math
@@ -36,6 +37,11 @@ CHUNK, SCAN_THREADS, THREADS, APPLY_ELEMS = 256, 256, 256, 2048
 BIG = 70_001
 assert BIG > CHUNK * SCAN_THREADS and BIG // 20 > THREADS and 3 * (BIG // 20) > APPLY_ELEMS
 SIZES = [0, 1, 63, 64, 65, 255, 257, 1000, BIG]
+# The noise grid is capped at kMcmcMaxBlocks = 2048 workgroups of 256 lanes; past that, lanes take a second row.  The same
+# size is 2049 chunks: each lane of the two scans walks ceil(2049 / 256) = 9 chunk sums.  One case each, outside the
+# cross-products.
+GRID_ROWS = 2048 * 256
+PAST_THE_GRID = GRID_ROWS + 3
 FLOOR = 2.0 ** -20
 MARGIN = 4.0
 LAST_UNIFORM = 1.0 - 2.0 ** -53
@@ -105,9 +111,21 @@ def _sample(dev, w, u):
 @pytest.mark.parametrize("kind", ["zeros30", "one_row", "nasty", "few", "all_zero"])
 @pytest.mark.parametrize("n", SIZES)
 def test_sampling_is_exact(hip_device, n, kind):
+    draws = [0] if n == 0 else sorted({0, 1, 64, 65, n // 20} | ({5000} if kind == "few" else set()))
+    _check_sampling(hip_device, n, kind, draws)
+
+
+@pytest.mark.parametrize("kind", ["zeros30", "nasty"])
+def test_sampling_is_exact_past_the_grid_cap(hip_device, kind):
+    """2049 chunks: k_mcmc_scan's lanes walk nine chunk sums each, and a draw searches 2049 bases (twelve halvings)."""
+    chunks = -(-PAST_THE_GRID // CHUNK)
+    assert chunks == 2049 and -(-chunks // SCAN_THREADS) == 9
+    _check_sampling(hip_device, PAST_THE_GRID, kind, [65, PAST_THE_GRID // 20])
+
+
+def _check_sampling(hip_device, n, kind, draws):
     rng = np.random.default_rng(100 * n + len(kind))
     w = np.zeros(n, np.float32) if kind == "all_zero" else _weights(kind, n, rng)
-    draws = [0] if n == 0 else sorted({0, 1, 64, 65, n // 20} | ({5000} if kind == "few" else set()))
     for m in draws:
         u = _uniforms(m, rng)
         want_idx, want_count, want_total = ref.sample(w, u)
@@ -129,6 +147,15 @@ def test_sampling_is_exact(hip_device, n, kind):
 
 @pytest.mark.parametrize("n", SIZES)
 def test_classification_is_exact(hip_device, n):
+    _check_classification(hip_device, n)
+
+
+def test_classification_is_exact_past_the_grid_cap(hip_device):
+    """2049 chunks: k_mcmc_classify_scan's lanes walk nine chunk sums each."""
+    _check_classification(hip_device, PAST_THE_GRID)
+
+
+def _check_classification(hip_device, n):
     from latentsplat_amd.mcmc import classify_dead, dead_logit
     rng = np.random.default_rng(n)
     thr = np.float32(dead_logit(0.005))
@@ -356,6 +383,18 @@ def _noise(dev, inp, xyz):
 
 @pytest.mark.parametrize("n", SIZES)
 def test_noise_matches(hip_device, n):
+    _check_noise(hip_device, n)
+
+
+def test_noise_matches_past_the_grid_cap(hip_device):
+    """2049 workgroups' worth of rows on a grid capped at 2048: the first three lanes take a second row, and it moves."""
+    inp, want, stock = _noise_case(PAST_THE_GRID)
+    bar = max(MARGIN * np.abs(stock - want).max(), FLOOR * np.abs(want).max())
+    assert np.abs(want[GRID_ROWS:]).max() > 10 * bar         # a row left where it was would be far off the bar
+    _check_noise(hip_device, PAST_THE_GRID)
+
+
+def _check_noise(hip_device, n):
     inp, want, stock = _noise_case(n)
     show = f"n={n}:"
     inc = _noise(hip_device, inp, np.zeros((n, 3), np.float32)).cpu().numpy()

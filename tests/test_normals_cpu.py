@@ -193,6 +193,34 @@ def test_gradcheck_of_both_restatements():
     assert abs(fd - float((g * d).sum())) <= 1e-7 * max(1.0, abs(fd))
 
 
+def test_the_gpu_cases_reach_both_loops_of_the_finish_kernel():
+    """k_nc_finish (csrc/normals.hip): wave w of 16 adds the images w, w + 16, ..., lane l of 64 the tiles l, l + 64, ... of
+    an image.  What the GPU test's cases reach, so that nobody trims them without seeing what goes."""
+    from tests.test_normals_gpu import FINISH_WAVES, PAST_THE_FINISH, SIZES, TILE, WAVE
+    assert (FINISH_WAVES, WAVE, TILE) == (16, 64, 32)
+    tiles = lambda H, W: ((H + TILE - 1) // TILE) * ((W + TILE - 1) // TILE)
+    assert max(tiles(H, W) for H, W in SIZES) == 12                       # the sizes of the cross-product stop short of both
+    reached = {(V, H, W): (V, tiles(H, W)) for V, H, W, _ in PAST_THE_FINISH}
+    assert reached == {(17, 3, 3): (17, 1), (33, 5, 4): (33, 1), (1, 3, 2049): (1, 65), (1, 3, 2081): (1, 66), (2, 257, 225): (2, 72),
+                       (2, 258, 225): (2, 72)}
+    views, slots = [r[0] for r in reached.values()], [r[1] for r in reached.values()]
+    assert any(FINISH_WAVES < v <= 2 * FINISH_WAVES for v in views) and any(v > 2 * FINISH_WAVES for v in views)
+    assert sum(s > WAVE for s in slots) >= 3 and WAVE + 1 in slots        # one lane alone takes a second tile; more do
+    assert any(H > 2 * TILE + 1 and W > 2 * TILE + 1 and V > 1 for V, H, W, _ in PAST_THE_FINISH)   # interior tiles, two images
+    second_trip = 0                                                       # cases whose tiles from the 65th on hold valid pixels
+    for V, H, W, offcentre in PAST_THE_FINISH:
+        kw = dict(offcentre=True, scale40=tuple(np.linspace(0.5, 2.0, V)), zero_block=True) if offcentre else {}
+        case = nref.image_case(V, H, W, seed=H + W + V, **kw)             # as the GPU test's _image_refs forms it
+        nref.check_image_case(case)
+        out = nref.consistency(*nref.to(torch.float64, case["normal_map"], case["depth"], case["alpha"], case["views"]))
+        ty, tx = (H + TILE - 1) // TILE, (W + TILE - 1) // TILE
+        padded = torch.nn.functional.pad(out["valid"], (0, tx * TILE - W, 0, ty * TILE - H))
+        per_tile = padded.reshape(V, ty, TILE, tx, TILE).any(4).any(2).reshape(V, ty * tx)     # in the order of the slots
+        second_trip += bool(per_tile[:, WAVE:].any(1).all())
+        assert len(np.unique(out["per_view"].numpy())) == V               # no two images share a mean: a swap shows
+    assert second_trip >= 2
+
+
 def test_the_builders_keep_every_case_off_its_thresholds():
     for n, V, kw in ((1, 1, {}), (65, 3, dict(quat_scale=1e-3)), (257, 5, dict(quat_scale=1e3, ties="two")),
                      (100, 3, dict(ties="three", scale40=(0.5, 1.0, 2.0)))):

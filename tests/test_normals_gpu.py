@@ -57,6 +57,32 @@ def test_scene_normals_against_float64(hip_device, n, V):
     assert float((out.norm(dim=-1) - 1).abs().max()) < 1e-6
 
 
+@functools.lru_cache(maxsize=None)
+def _cyclic_case(n, V, B):
+    """V views that repeat B distinct cameras of make_views cyclically.  A full circle of hundreds of cameras cannot keep
+    every axis 1e-2 off perpendicular to every view direction (some camera always comes that close, and the builder's redraw
+    does not end), so the case is scene_case at B views, which meets check_scene_case as it stands, with
+    views[v] = base[v % B].  B is coprime to 256: record v and record v - 256 are different cameras."""
+    assert np.gcd(B, 256) == 1 and V > 256
+    case = nref.scene_case(n, B, seed=10 * n + V)
+    case["views"] = np.ascontiguousarray(case["views"][np.arange(V) % B])
+    return case
+
+
+@pytest.mark.parametrize("n,V,B", [(65, 257, 5), (63, 600, 7)])
+def test_scene_normals_with_more_cameras_than_compaction_lanes(hip_device, n, V, B):
+    """k_normals_cameras is one workgroup of 256 lanes: from camera 256 on a lane compacts a second record, and a third."""
+    case = _cyclic_case(n, V, B)
+    assert not np.array_equal(case["views"][256], case["views"][0]) and np.array_equal(case["views"][B], case["views"][0])
+    t64 = lambda a: torch.from_numpy(np.asarray(a, np.float64))
+    cos = nref.view_cosines(*(t64(case[k]) for k in A_KEYS)).numpy()
+    flips = (cos > 0).any(0) & (cos < 0).any(0)
+    assert flips.any() and not flips.all()                   # some Gaussians change sign between views, some do not
+    out, grad = _check_A(case, hip_device, f"n={n} V={V} cyclic over {B}")
+    assert float((out.norm(dim=-1) - 1).abs().max()) < 1e-6 and float(grad.abs().max()) > 0
+    assert np.array_equal(_bits(out), _bits(out[:B][torch.arange(V, device=hip_device) % B]))      # one camera, one answer
+
+
 @pytest.mark.parametrize("quat_scale", [1e-3, 1e3])
 def test_scene_normals_of_raw_quaternions(hip_device, quat_scale):
     """The kernel normalises: quaternions a thousand times shorter and longer than unit, and a scene scale != 1 in slot 40."""
@@ -113,6 +139,15 @@ def test_only_the_rotation_receives_a_gradient(hip_device):
 B_KEYS = ("normal_map", "depth", "alpha", "views")
 GRAD_LOSS = 0.75
 SIZES = [(3, 3), (1, 5), (2, 7), (5, 4), (33, 31), (65, 34), (70, 97)]
+# (V, H, W, offcentre) past the loops of k_nc_finish, which no size above enters a second time: its 16 waves take the
+# images w, w + 16, ... and a wave's 64 lanes the tiles l, l + 64, ... of an image (tests/test_normals_cpu.py asserts what
+# each case reaches).  One row of valid pixels under 65 tiles, 66 tiles with a partial last one, and 9 x 8 tiles with
+# interior ones.  At 3 x 2049 and 257 x 225 the tiles from the 65th on hold border pixels alone and their slots are 0: a
+# finish kernel that left them out would not show there, so 258 x 225 goes with them, whose ninth row of tiles holds a
+# row of valid pixels.
+FINISH_WAVES, WAVE, TILE = 16, 64, 32
+PAST_THE_FINISH = [(17, 3, 3, False), (33, 5, 4, True), (1, 3, 2049, False), (1, 3, 2081, True), (2, 257, 225, True),
+                   (2, 258, 225, True)]
 
 
 @functools.lru_cache(maxsize=None)
@@ -139,6 +174,16 @@ def _run_B(case: dict, dev, want=("loss", "per_view", "depth_normals", "valid"),
 @pytest.mark.parametrize("V", [1, 3])
 @pytest.mark.parametrize("H,W", SIZES)
 def test_normal_consistency_against_float64(hip_device, H, W, V, offcentre):
+    _check_B(hip_device, V, H, W, offcentre)
+
+
+@pytest.mark.parametrize("V,H,W,offcentre", PAST_THE_FINISH)
+def test_normal_consistency_against_float64_past_the_finish_loops(hip_device, V, H, W, offcentre):
+    """per_view is compared element by element: an image credited to the wrong wave, or a tile left out, shows."""
+    _check_B(hip_device, V, H, W, offcentre)
+
+
+def _check_B(hip_device, V, H, W, offcentre):
     case, want, stock = _image_refs(V, H, W, offcentre)
     show = f"{V}x{H}x{W} offcentre={offcentre}"
     got = _run_B(case, hip_device)

@@ -62,6 +62,54 @@ def test_metric_mode_matches_the_scipy_filter():
     assert np.abs(got - want).max() <= 1e-12
 
 
+# ---- what the GPU test's shapes reach ----
+
+# shape of tests/test_photometric_gpu.py SHAPES -> (photo_shift, slots per image, (tiles_y, tiles_x)), worked out by hand from
+# csrc/photometric.hip: share = H W / ((H + 10)(W + 10)), shift = floor(4 share + 0.5) / 8, one slot per 32 x 32 tile of every
+# plane.  A shape that is dropped or "simplified" has to be taken out of this table too, and the coverage below then says
+# what is lost.
+REACHED = {
+    (1, 1, 1, 1): (0.0, 1, (1, 1)),
+    (1, 3, 7, 5): (0.125, 3, (1, 1)),
+    (2, 3, 11, 11): (0.125, 3, (1, 1)),
+    (1, 3, 10, 12): (0.125, 3, (1, 1)),
+    (2, 3, 37, 53): (0.375, 12, (2, 2)),
+    (3, 1, 64, 64): (0.375, 4, (2, 2)),
+    (1, 4, 33, 17): (0.25, 8, (2, 1)),
+    (1, 2, 31, 32): (0.25, 2, (1, 1)),
+    (1, 2, 32, 33): (0.25, 4, (1, 2)),
+    (1, 2, 33, 31): (0.25, 4, (2, 1)),
+    (1, 3, 160, 160): (0.5, 75, (5, 5)),
+    (2, 3, 96, 352): (0.5, 99, (3, 11)),
+    (1, 1, 33, 2081): (0.375, 132, (2, 66)),
+    (17, 1, 7, 5): (0.125, 1, (1, 1)),
+    (33, 2, 11, 11): (0.125, 2, (1, 1)),
+}
+
+
+def test_the_gpu_shapes_reach_every_trip_count_of_a_full_size_fit():
+    from tests.test_photometric_gpu import FULL_SIZE, SHAPES
+    assert ref.TILE == 32 and ref.WAVE == 64 and ref.FINISH_WAVES == 16
+    assert sorted(SHAPES) == sorted(REACHED) and len(set(SHAPES)) == len(SHAPES)
+    for shape in SHAPES:
+        shift, slots, tiles = REACHED[shape]
+        assert ref.photo_shift(*shape[2:]) == shift, shape
+        assert ref.slots_per_image(shape) == slots, shape
+        assert ref.tile_grid(*shape[2:]) == tiles, shape
+    # the shift: every value it takes; 0.5 from 145 px a side, and at every larger square image
+    assert {ref.photo_shift(*s[2:]) for s in SHAPES} == {0.0, 0.125, 0.25, 0.375, 0.5}
+    assert ref.photo_shift(144, 144) == 0.375 and all(ref.photo_shift(s, s) == 0.5 for s in (145, 256, 800, 4000))
+    assert ref.photo_shift(64, 64) == 0.375 and REACHED[FULL_SIZE][0] == 0.5
+    # k_photo_finish: lanes that take a second slot of an image, and a third; waves that take a second image, and a third
+    slots = [ref.slots_per_image(s) for s in SHAPES]
+    assert any(ref.WAVE < n <= 2 * ref.WAVE for n in slots) and any(n > 2 * ref.WAVE for n in slots)
+    assert any(ref.FINISH_WAVES < s[0] <= 2 * ref.FINISH_WAVES for s in SHAPES) and any(s[0] > 2 * ref.FINISH_WAVES for s in SHAPES)
+    # an interior tile, whose 42 x 42 halo lies wholly inside the image: tile 1 covers 32..63 and reads 27..68, each way
+    assert any(min(ref.tile_grid(*s[2:])) >= 3 and min(s[2:]) >= 2 * ref.TILE + ref.R for s in SHAPES)
+    # partial tiles both ways next to the long row of tiles
+    assert any(ref.slots_per_image(s) > 2 * ref.WAVE and s[2] % ref.TILE and s[3] % ref.TILE for s in SHAPES)
+
+
 # ---- host-only ABI ----
 
 def _dims(**kw):
