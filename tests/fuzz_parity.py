@@ -9,11 +9,12 @@ the draws go through the scene-level inputs of the decoder path — in-kernel sc
 colour SH, latent SH evaluated in-kernel, shared by all views (the fused projection + SH kernel) or per view; an eighth
 compare the no-sync (latency) forward bit for bit with the synchronous one).
 
-    python -m tests.fuzz_parity --seconds 240 --seed 1 [--edges] [--out fuzz_parity.json]
+    python -m tests.fuzz_parity --seconds 240 --seed 1 [--edges | --grids] [--out fuzz_parity.json]
 
 --edges draws instead from the frustum-edge scenes (tests/util.py make_edge_scene: the Jacobian clamp band to single ulps,
 the near cull, means outside the cone, border rectangles, wide-baseline targets), from a stream of its own: the default
-draws of every seed, and their `--only N` reproductions, are unchanged.
+draws of every seed, and their `--only N` reproductions, are unchanged.  --grids, likewise from its own stream, draws from the
+tile grids and work-item counts at which the kernels change instance or scheduling branch (tests/grid_variants.py).
 
 The suite's BUDGETS for how much of a scene may sit next to a discontinuity (2 % of the pixels, 1 % of the Gaussians: tuned
 to its own scenes) are lifted here — a 7 x 50 image under 30-pixel splats has more — while every bar stays: pixels and
@@ -78,6 +79,56 @@ def draw_edges(rng: random.Random):
     return case, mode, contracted
 
 
+GRID_SIDES = [256, 272, 400, 496, 520, 528, 1040]
+GRID_STRIPS = [(40, 4090), (4090, 40)]
+GRID_PIXELS = 8 * 528 * 528      # most pixels of a draw over all views: what the oracle's gradient pass costs
+
+
+def draw_grids(rng: random.Random):
+    """One case of the `grids` mode (--grids): image sides around the tile-grid switches of tests/grid_variants.py (1024 /
+    4096 / 8192 tiles and (view, tile) counts, 255 tile columns or rows), 1 to 8 views — the work-item counts on both sides
+    of every instance's wave slots — and payload widths on every padded width (4, 8, 12, 36).  Splats of 1-12 px (2-40 px on
+    the strips, whose Gaussians are spread over 4090 px) at opacity up to 1 and few enough Gaussians that the oracle's
+    fragile list does not overflow and a case takes seconds.  Drawn from its own stream."""
+    if rng.random() < 0.25:
+        H, W = rng.choice(GRID_STRIPS)
+        G, sigma = rng.choice([20000, 30000]), (2.0, 40.0)
+    else:
+        H, W = rng.choice(GRID_SIDES), rng.choice(GRID_SIDES)
+        G, sigma = rng.choice([1500, 3000, 4000]), (1.0, 12.0)
+    views = rng.randint(1, 8)
+    while views > 1 and views * H * W > GRID_PIXELS:
+        views -= 1
+    # (colour degree, direct feature channels) -> 4, 4, 7, 8, 11, 12, 35 payload channels
+    color, fc = rng.choice([(None, 4), (0, 1), (1, 4), (2, 5), (2, 8), (0, 9), (1, 32)])
+    mode = rng.choice(["forward", "backward", "backward_aux", "fused_shared"])
+    case = dict(G=G, size=(H, W), views=views, color_sh_degree=color, feature_channels=fc, sigma_px=sigma, opacity_scale=1.0,
+                seed=rng.randrange(1 << 30))
+    if mode == "fused_shared":   # square images, harmonics only: the fused kernel or (fuse = 0) k_preprocess with 2 / 4 views per workgroup
+        side = rng.choice(GRID_SIDES[:-1])
+        case.update(size=(side, side), G=1500, sigma_px=(1.0, 12.0), color_sh_degree=rng.choice([None, 1, 3]),
+                    feature_channels=rng.choice([4, 8]), feature_sh_degree=rng.choice([0, 1]), fuse=rng.choice([0, 1]))
+    return case, mode, False
+
+
+def run_grid_case(dev, case: dict, mode: str):
+    from latentsplat_amd import _lib
+    c = dict(case)
+    fuse = c.pop("fuse", 1)
+    sc, H, W = tp._scene(c)
+    if mode == "fused_shared":
+        try:
+            _lib.set_knob("LSR_FUSE_SH", fuse)
+            tp._fused_scene_check(dev, sc, H, True)
+        finally:
+            _lib.set_knob("LSR_FUSE_SH", 1)
+    elif mode == "forward":
+        bi = util.boundary_inputs(sc, H, W, bg=(0.2, 0.4, 0.6))
+        tp._check_forward(bi, util.HipRun(bi, dev))
+    else:
+        tp._grad_scene(dev, sc, H, W, mode == "backward_aux")
+
+
 def run_edge_case(dev, case: dict, mode: str):
     c = dict(case)
     pop, H, W = c.pop("pop"), c.pop("H"), c.pop("W")
@@ -123,7 +174,7 @@ def classify(msg: str) -> str:
     return "other"
 
 
-def run_case(dev, case: dict, mode: str, contracted: bool):
+def run_case(dev, case: dict, mode: str, contracted: bool, grids: bool = False):
     from latentsplat_amd import _lib
     from oracle import oracle as orc
     lib = _lib.load()
@@ -133,6 +184,8 @@ def run_case(dev, case: dict, mode: str, contracted: bool):
             orc.set_fma_contraction(True)
         if "pop" in case:   # --edges
             run_edge_case(dev, case, mode)
+        elif grids:
+            run_grid_case(dev, case, mode)
         elif mode.startswith("fused"):   # scene-level inputs: in-kernel scene scale, 3x3 covariances, stored-layout colour SH, latent SH
             cfg = dict(case, size=max(case["size"]), feature_channels=case["feature_channels"] or 4, views=max(1, case["views"] + (mode == "fused_shared")))
             cfg.setdefault("feature_sh_degree", 2)
@@ -171,8 +224,8 @@ def run_case(dev, case: dict, mode: str, contracted: bool):
             orc.set_fma_contraction(False)
 
 
-def sweep(dev, seed: int, seconds: float, max_cases: int = 0, only: int = -1, edges: bool = False) -> dict:
-    rng = random.Random(f"edges:{seed}") if edges else random.Random(seed)
+def sweep(dev, seed: int, seconds: float, max_cases: int = 0, only: int = -1, edges: bool = False, grids: bool = False) -> dict:
+    rng = random.Random(f"edges:{seed}") if edges else (random.Random(f"grids:{seed}") if grids else random.Random(seed))
     t0 = time.time()
     done, failures, by_mode = 0, [], {}
     worst_clean, over_suite_bar = 0.0, 0
@@ -181,6 +234,8 @@ def sweep(dev, seed: int, seconds: float, max_cases: int = 0, only: int = -1, ed
         while (time.time() - t0 < seconds and (not max_cases or done < max_cases)) or (only >= 0 and n <= only):
             if edges:
                 case, mode, contracted = draw_edges(rng)
+            elif grids:
+                case, mode, contracted = draw_grids(rng)
             else:
                 case = draw(rng)
                 mode = rng.choice(["forward", "forward", "forward", "backward", "backward_aux", "fused_shared", "fused_per_view", "nosync"])
@@ -192,7 +247,7 @@ def sweep(dev, seed: int, seconds: float, max_cases: int = 0, only: int = -1, ed
                 continue
             n0 = len(util.ACCOUNTING)
             try:
-                run_case(dev, dict(case), mode, contracted)
+                run_case(dev, dict(case), mode, contracted, grids)
                 by_mode[mode] = by_mode.get(mode, 0) + 1
             except Exception as e:   # noqa: BLE001 — every failure is a finding to record, whatever its type
                 msg = f"{type(e).__name__}: {str(e)[:400]}"
@@ -208,7 +263,7 @@ def sweep(dev, seed: int, seconds: float, max_cases: int = 0, only: int = -1, ed
                 break
     failures = [f for f in failures if f["kind"] != "budget"]
     kinds = {k: sum(f["kind"] == k for f in failures) for k in ("exact", "bar", "other")}
-    return dict(seed=seed, edges=edges, seconds=round(time.time() - t0, 1), cases=done, passed=done - len(failures), passed_by_mode=by_mode,
+    return dict(seed=seed, edges=edges, grids=grids, seconds=round(time.time() - t0, 1), cases=done, passed=done - len(failures), passed_by_mode=by_mode,
                 failed_by_kind=kinds, worst_clean_row_over_scale=worst_clean, cases_over_suite_clean_bar=int(over_suite_bar), failures=failures)
 
 
@@ -218,9 +273,10 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--only", type=int, default=-1, help="run only draw N of the seed")
     ap.add_argument("--edges", action="store_true", help="the frustum-edge scenes of tests/util.py make_edge_scene (own draw stream)")
+    ap.add_argument("--grids", action="store_true", help="the tile-grid and work-queue switches of tests/grid_variants.py (own draw stream)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
-    res = sweep(torch.device("cuda", 0), args.seed, args.seconds, only=args.only, edges=args.edges)
+    res = sweep(torch.device("cuda", 0), args.seed, args.seconds, only=args.only, edges=args.edges, grids=args.grids)
     print(json.dumps(res, indent=1, default=str))
     if args.out:
         with open(args.out, "w") as f:
