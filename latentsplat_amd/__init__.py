@@ -9,7 +9,9 @@ depths and opacities; the op itself is ``latentsplat_amd.depth_head.depth_head``
 and the SSIM metric in HIP), ``bilagrid`` (bilateral-grid appearance compensation between render and loss: per-image grids of
 colour affines sliced by position and luminance, and their total variation, in HIP), ``transform`` (similarity transforms of a
 scene: positions, quaternions, log-scales and every SH band of the view-dependent colour in one HIP pass; posed parts, merge), ``pose`` (the same transforms as learnable quaternions, translations and log-scales: the pose gradient of a scene's rigid parts in one HIP pass, reduced per part without atomics), ``vq`` (codebook compression of a scene: weighted k-means with a fused distance-and-argmin on the f32 matrix
-instruction and a bit-reproducible float64 centroid update, in HIP; quantised scenes in and out of one compressed file), ``normals`` (the depth-normal consistency regulariser: per-view normals of the Gaussians and the fused image-space loss against the normals of the rendered depth, in HIP) and ``synthetic`` (seeded scenes for tests / bench).
+instruction and a bit-reproducible float64 centroid update, in HIP; quantised scenes in and out of one compressed file), ``normals`` (the depth-normal consistency regulariser: per-view normals of the Gaussians and the fused image-space loss against the normals of the rendered depth, in HIP), ``mesh`` (mesh extraction: rendered depth fused into a
+truncated signed distance volume in one pass over the volume per batch of views, and marching tetrahedra, in HIP; mesh ``.ply``
+files) and ``synthetic`` (seeded scenes for tests / bench).
 """
 __version__ = "0.1.0"
 
@@ -32,6 +34,7 @@ _LAZY = {"rotate_sh": "sh_rotate", "GaussianAdapter": "gaussian_adapter", "Gauss
          "contribution_weights": "vq",
          "gaussian_normals": "normals", "normal_consistency_loss": "normals", "depth_to_normals": "normals",
          "flatten_loss": "normals",
+         "TSDFVolume": "mesh", "save_mesh_ply": "mesh", "load_mesh_ply": "mesh",
          "adam_step": "optim", "SceneAdam": "optim", "expon_lr": "optim", "visible_from_radii": "optim"}
 
 

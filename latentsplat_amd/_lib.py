@@ -1,5 +1,5 @@
 """ctypes binding of ``liblsr_hip.so`` (C ABI: include/lsr_rasterizer.h, include/lsr_adapter.h, include/lsr_latent.h, include/lsr_ply.h,
-include/lsr_sh_rotate.h, include/lsr_depth_head.h, include/lsr_scene.h, include/lsr_loss.h, include/lsr_density.h, include/lsr_optim.h, include/lsr_knn.h, include/lsr_mcmc.h, include/lsr_filter3d.h, include/lsr_bilagrid.h, include/lsr_transform.h, include/lsr_vq.h, include/lsr_pose.h, include/lsr_normals.h).
+include/lsr_sh_rotate.h, include/lsr_depth_head.h, include/lsr_scene.h, include/lsr_loss.h, include/lsr_density.h, include/lsr_optim.h, include/lsr_knn.h, include/lsr_mcmc.h, include/lsr_filter3d.h, include/lsr_bilagrid.h, include/lsr_transform.h, include/lsr_vq.h, include/lsr_pose.h, include/lsr_normals.h, include/lsr_mesh.h).
 
 The library is built in-tree by ``latentsplat_amd/csrc/Makefile`` (``__graft_entry__.build()``).
 There is no CPU fallback: if the shared object is missing or not loadable this module raises, and
@@ -277,6 +277,15 @@ class NormalDims(C.Structure):       # lsr_normal_dims (include/lsr_normals.h)
 NORMALS_MAX_ROWS, NORMALS_MAX_VIEWS = 1 << 28, 65536                # LSR_NORMALS_MAX_*
 
 
+class TsdfDims(C.Structure):         # lsr_tsdf_dims (include/lsr_mesh.h)
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("origin", C.c_float * 3), ("voxel_size", C.c_float),
+                ("trunc", C.c_float), ("has_color", C.c_int32), ("reserved0", C.c_int32), ("reserved1", C.c_int32),
+                ("reserved2", C.c_int32)]
+
+
+TSDF_MIN_EXTENT, TSDF_MAX_EXTENT, TSDF_MAX_VOXELS, TSDF_MAX_VIEWS = 2, 2048, 1 << 30, 1024   # LSR_TSDF_*
+
+
 def transform_record_floats(degree: int) -> int:
     """LSR_TRANSFORM_RECORD_FLOATS: the 20-float header and the band blocks 1..degree (20, 29, 54, 103, 184)."""
     return TRANSFORM_HEADER_FLOATS + sh_rotate_table_floats(degree) - 1
@@ -385,6 +394,11 @@ PROTOTYPES = {
     "lsr_normal_consistency_workspace_bytes": (_SZ, [_ptr_to(NormalDims)]),
     "lsr_normal_consistency_forward": (_INT, [_ptr_to(NormalDims)] + [_P] * 10),
     "lsr_normal_consistency_backward": (_INT, [_ptr_to(NormalDims)] + [_P] * 9),
+    "lsr_tsdf_workspace_bytes": (_SZ, [_I32]),
+    "lsr_tsdf_integrate": (_INT, [_ptr_to(TsdfDims), _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _F, _F, _F, _P, _P]),
+    "lsr_mesh_workspace_bytes": (_SZ, [_ptr_to(TsdfDims)]),
+    "lsr_mesh_count": (_INT, [_ptr_to(TsdfDims), _P, _P, _F, _P, _P, _P]),
+    "lsr_mesh_emit": (_INT, [_ptr_to(TsdfDims), _P, _P, _P, _F, _P, _P, _I64, _I64, _P, _P, _P, _P]),
 }
 EXPORTS = tuple(PROTOTYPES)
 

@@ -475,6 +475,32 @@ class GaussianScene(nn.Module):
         normals = gaussian_normals(views, xyz, scaling, rotation)
         return rasterize_views(views, height, width, self.active_sh_degree, xyz, cov, opacities, shs=shs, features=normals, **kw)
 
+    @torch.no_grad()
+    def extract_mesh(self, views: Tensor, height: int, width: int, voxel_size: float, bounds=None, trunc: Optional[float] = None,
+                     batch: int = 8, min_weight: float = 1.0, **render_kw):
+        """A triangle mesh of the scene's surface, ``(vertices (Nv, 3), faces (Nf, 3) int32, colors (Nv, 3))``: the views
+        are rendered ``batch`` at a time (colour, depth of depth mode NATIVE, mask: :meth:`render`, which ``render_kw``
+        goes to), fused into a :class:`latentsplat_amd.mesh.TSDFVolume` of ``voxel_size`` (world units) and the zero level
+        set is extracted by marching tetrahedra.  ``bounds = (lo, hi)`` defaults to the box of the positions of the
+        Gaussians with opacity above 0.5, padded by ``trunc`` (default: 4 voxel sizes; a default, not a measurement).
+        ``views`` must carry depth mode NATIVE, as for :meth:`render_with_normals`.  Values only; one host read for the
+        default bounds and one for the mesh's size."""
+        from .mesh import TSDFVolume
+        trunc = 4.0 * float(voxel_size) if trunc is None else float(trunc)
+        if bounds is None:
+            solid = self._xyz[torch.sigmoid(self._opacity).reshape(-1) > 0.5]
+            if solid.shape[0] == 0:
+                raise _lib.LsrError("extract_mesh: no Gaussian has opacity above 0.5; pass bounds")
+            lo, hi = (solid.min(dim=0).values - trunc).tolist(), (solid.max(dim=0).values + trunc).tolist()
+        else:
+            lo, hi = bounds
+        volume = TSDFVolume.from_bounds(lo, hi, voxel_size, trunc=trunc, color=True, device=self._xyz.device)
+        for at in range(0, views.shape[0], max(1, int(batch))):
+            v = views[at:at + max(1, int(batch))]
+            color, _, mask, depth, _ = self.render(v, height, width, **render_kw)
+            volume.integrate(depth, mask, v, color=color)
+        return volume.extract_mesh(min_weight)
+
     def transform_(self, M: Tensor, idx: Optional[Tensor] = None) -> "GaussianScene":
         """Move the scene in place by the similarity ``M (4, 4)`` (or ``(T, 4, 4)`` with ``idx (n,)`` naming the transform
         of each Gaussian; out of range: not moved), under ``no_grad``: ``_xyz``, ``_features_rest`` (every SH band rotated
