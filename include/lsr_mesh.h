@@ -125,6 +125,28 @@ int lsr_mesh_emit(const lsr_tsdf_dims *dims, const float *tsdf, const float *wei
                   void *workspace, const int64_t *counts, int64_t capacity_vertices, int64_t capacity_faces, float *vertices,
                   float *vertex_colors, int32_t *faces, lsr_stream_t stream);
 
+/* ---- C: connected components over shared vertex indices (the cleanup after extraction: keep the largest clusters) ----
+ *
+ * labels[v] ends as the lowest vertex index of v's connected component; two vertices are connected when a face names
+ * both BY INDEX (lsr_mesh_emit numbers a vertex once per lattice edge, so its meshes qualify).  A vertex in no face
+ * labels itself.  The caller drives rounds:
+ *   lsr_mesh_components_init    labels[v] = v;
+ *   lsr_mesh_components_round   clears *changed (device int32), then HOOK: per face, each corner's label chain is
+ *                               followed to its root and the larger roots' labels take the smallest root by integer
+ *                               atomicMin, and *changed becomes 1 when a face saw two roots; then COMPRESS:
+ *                               labels[v] = root(v).  Three stream operations.
+ * and repeats the round until *changed stays 0; it reads the flag itself and caps the rounds (O(log nv) are needed unless
+ * the numbering is adversarial).  labels[x] <= x always and every write lowers a label, so every walk inside a round ends
+ * in at most x steps; the fixed point is each component's minimum whatever order the threads ran in (integer atomicMin
+ * only): two runs give the same labels.  A face with a corner outside [0, nv) is skipped by the kernel; callers are
+ * expected to refuse such a mesh.
+ * LSR_EINVAL: a negative count, a count above LSR_MESH_MAX_ELEMENTS.  LSR_ENULL: labels NULL with nv > 0 (init); changed
+ * NULL, faces or labels NULL with nv > 0 and nf > 0 (round).  nv == 0 or nf == 0: a round only clears the flag. */
+#define LSR_MESH_MAX_ELEMENTS (1 << 30)
+int lsr_mesh_components_init(int64_t num_vertices, int32_t *labels, lsr_stream_t stream);
+int lsr_mesh_components_round(int64_t num_vertices, int64_t num_faces, const int32_t *faces, int32_t *labels, int32_t *changed,
+                              lsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,9 @@ colour affines sliced by position and luminance, and their total variation, in H
 scene: positions, quaternions, log-scales and every SH band of the view-dependent colour in one HIP pass; posed parts, merge), ``pose`` (the same transforms as learnable quaternions, translations and log-scales: the pose gradient of a scene's rigid parts in one HIP pass, reduced per part without atomics), ``vq`` (codebook compression of a scene: weighted k-means with a fused distance-and-argmin on the f32 matrix
 instruction and a bit-reproducible float64 centroid update, in HIP; quantised scenes in and out of one compressed file), ``normals`` (the depth-normal consistency regulariser: per-view normals of the Gaussians and the fused image-space loss against the normals of the rendered depth, in HIP), ``mesh`` (mesh extraction: rendered depth fused into a
 truncated signed distance volume in one pass over the volume per batch of views, and marching tetrahedra, in HIP; mesh ``.ply``
-files) and ``synthetic`` (seeded scenes for tests / bench).
+files; connected components and the cleanup that keeps the largest clusters), ``nn`` (the exact nearest neighbour of one
+cloud's points in another: a persistent index over a reference cloud, in HIP), ``mesh_eval`` (what scores a mesh against a
+ground-truth cloud: accuracy, completeness, Chamfer, precision / recall / F-score, and an area-weighted mesh sampler) and ``synthetic`` (seeded scenes for tests / bench).
 """
 __version__ = "0.1.0"
 
@@ -35,6 +37,9 @@ _LAZY = {"rotate_sh": "sh_rotate", "GaussianAdapter": "gaussian_adapter", "Gauss
          "gaussian_normals": "normals", "normal_consistency_loss": "normals", "depth_to_normals": "normals",
          "flatten_loss": "normals",
          "TSDFVolume": "mesh", "save_mesh_ply": "mesh", "load_mesh_ply": "mesh",
+         "mesh_components": "mesh", "clean_mesh": "mesh",
+         "NearestIndex": "nn", "nearest": "nn",
+         "cloud_metrics": "mesh_eval", "sample_mesh": "mesh_eval",
          "adam_step": "optim", "SceneAdam": "optim", "expon_lr": "optim", "visible_from_radii": "optim"}
 
 

@@ -1,5 +1,5 @@
 """ctypes binding of ``liblsr_hip.so`` (C ABI: include/lsr_rasterizer.h, include/lsr_adapter.h, include/lsr_latent.h, include/lsr_ply.h,
-include/lsr_sh_rotate.h, include/lsr_depth_head.h, include/lsr_scene.h, include/lsr_loss.h, include/lsr_density.h, include/lsr_optim.h, include/lsr_knn.h, include/lsr_mcmc.h, include/lsr_filter3d.h, include/lsr_bilagrid.h, include/lsr_transform.h, include/lsr_vq.h, include/lsr_pose.h, include/lsr_normals.h, include/lsr_mesh.h).
+include/lsr_sh_rotate.h, include/lsr_depth_head.h, include/lsr_scene.h, include/lsr_loss.h, include/lsr_density.h, include/lsr_optim.h, include/lsr_knn.h, include/lsr_mcmc.h, include/lsr_filter3d.h, include/lsr_bilagrid.h, include/lsr_transform.h, include/lsr_vq.h, include/lsr_pose.h, include/lsr_normals.h, include/lsr_mesh.h, include/lsr_nn.h).
 
 The library is built in-tree by ``latentsplat_amd/csrc/Makefile`` (``__graft_entry__.build()``).
 There is no CPU fallback: if the shared object is missing or not loadable this module raises, and
@@ -284,6 +284,7 @@ class TsdfDims(C.Structure):         # lsr_tsdf_dims (include/lsr_mesh.h)
 
 
 TSDF_MIN_EXTENT, TSDF_MAX_EXTENT, TSDF_MAX_VOXELS, TSDF_MAX_VIEWS = 2, 2048, 1 << 30, 1024   # LSR_TSDF_*
+MESH_MAX_ELEMENTS, MESH_COMPONENT_ROUNDS = 1 << 30, 64              # LSR_MESH_MAX_ELEMENTS; the cap of mesh.mesh_components
 
 
 def transform_record_floats(degree: int) -> int:
@@ -399,6 +400,13 @@ PROTOTYPES = {
     "lsr_mesh_workspace_bytes": (_SZ, [_ptr_to(TsdfDims)]),
     "lsr_mesh_count": (_INT, [_ptr_to(TsdfDims), _P, _P, _F, _P, _P, _P]),
     "lsr_mesh_emit": (_INT, [_ptr_to(TsdfDims), _P, _P, _P, _F, _P, _P, _I64, _I64, _P, _P, _P, _P]),
+    "lsr_mesh_components_init": (_INT, [_I64, _P, _P]),
+    "lsr_mesh_components_round": (_INT, [_I64, _I64, _P, _P, _P, _P]),
+    "lsr_nn_index_bytes": (_SZ, [_I64]),
+    "lsr_nn_build_workspace_bytes": (_SZ, [_I64]),
+    "lsr_nn_build": (_INT, [_I64, _P, _P, _P, _P]),
+    "lsr_nn_query_workspace_bytes": (_SZ, [_I64]),
+    "lsr_nn_query": (_INT, [_I64, _P, _I64, _P, _P, _P, _P, _P]),
 }
 EXPORTS = tuple(PROTOTYPES)
 

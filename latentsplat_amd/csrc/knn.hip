@@ -46,37 +46,12 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 
-#include "lsr_wave.h"
+#include "lsr_morton.h"
 #include "lsr_knn.h"
 
 namespace lsr {
 
-constexpr int kChunk = 128;            // sorted points per chunk: one box of the first level, one LDS stage
-constexpr int kQueries = 64;           // queries per workgroup of the search: one wavefront, one query per lane
-constexpr int kGroup = 64;             // chunks per second-level box = lanes of one ballot
-constexpr int kKnnThreads = 256;       // lanes per workgroup of the box and key kernels
-constexpr int kBBoxBlocks = 1024;
-constexpr int kCellBits = 21;
-constexpr float kCellMax = (float)((1 << kCellBits) - 1);
-
-// min / max of three coordinates over a workgroup of kThreads; the result in every thread (s: 6 floats per wave)
-template <int kThreads>
-__device__ __forceinline__ void block_minmax3(float lo[3], float hi[3], float *s) {
-    const int lane = threadIdx.x & (LSR_WAVE - 1), wave = threadIdx.x / LSR_WAVE;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        lo[k] = wave_all(lo[k], Min());
-        hi[k] = wave_all(hi[k], Max());
-        if (lane == 0) { s[6 * wave + k] = lo[k]; s[6 * wave + 3 + k] = hi[k]; }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-        for (int w = 0; w < kThreads / LSR_WAVE; ++w) {
-            lo[k] = fminf(lo[k], s[6 * w + k]);
-            hi[k] = fmaxf(hi[k], s[6 * w + 3 + k]);
-        }
-}
+// (the constants, block_minmax3, spread_bits, box_dist2 and nearest_bit are in lsr_morton.h, shared with nn.hip)
 
 __global__ __launch_bounds__(kKnnThreads) void k_knn_bbox(int64_t n, const float *__restrict__ points, float *__restrict__ partial) {
     __shared__ float s[6 * kKnnThreads / LSR_WAVE];
@@ -111,15 +86,6 @@ __global__ __launch_bounds__(kKnnThreads) void k_knn_bbox_final(int blocks, cons
         grid[0] = lo[0]; grid[1] = lo[1]; grid[2] = lo[2];
         grid[3] = extent > 0.0f && extent < INFINITY ? kCellMax / extent : 0.0f;      // (no division by a zero extent)
     }
-}
-
-__device__ __forceinline__ uint64_t spread_bits(uint64_t x) {      // bit i of 21 to bit 3 i
-    x = (x | x << 32) & 0x001f00000000ffffull;
-    x = (x | x << 16) & 0x001f0000ff0000ffull;
-    x = (x | x << 8) & 0x100f00f00f00f00full;
-    x = (x | x << 4) & 0x10c30c30c30c30c3ull;
-    x = (x | x << 2) & 0x1249249249249249ull;
-    return x;
 }
 
 __global__ __launch_bounds__(kKnnThreads) void k_knn_keys(int64_t n, const float *__restrict__ points, const float *__restrict__ grid,
@@ -177,14 +143,6 @@ __global__ __launch_bounds__(kGroup) void k_knn_group_boxes(int64_t chunks, cons
     }
 }
 
-// squared distance between two boxes (0 where they overlap); a point is the box with amin == amax
-__device__ __forceinline__ float box_dist2(const float4 &amin, const float4 &amax, const float4 &bmin, const float4 &bmax) {
-    const float gx = fmaxf(0.0f, fmaxf(bmin.x - amax.x, amin.x - bmax.x));
-    const float gy = fmaxf(0.0f, fmaxf(bmin.y - amax.y, amin.y - bmax.y));
-    const float gz = fmaxf(0.0f, fmaxf(bmin.z - amax.z, amin.z - bmax.z));
-    return gx * gx + gy * gy + gz * gz;
-}
-
 // the best three of a query, ordered by (distance, index)
 struct Best3 {
     float d0, d1, d2;
@@ -214,13 +172,6 @@ __device__ __forceinline__ void scan_staged(Best3 &b, const float4 &q, int me, c
         const int idx = __float_as_int(p.w);
         if (d <= b.d2 && (!kSkipSelf || idx != me)) consider(b, d, idx);
     }
-}
-
-// the set bit of `mask` nearest to position `pos` (0..63); mask != 0
-__device__ __forceinline__ int nearest_bit(uint64_t mask, int pos) {
-    const uint64_t up = mask >> pos, down = pos ? mask & ((1ull << pos) - 1ull) : 0ull;
-    const int u = up ? pos + __builtin_ctzll(up) : 1 << 20, d = down ? 63 - __builtin_clzll(down) : -(1 << 20);
-    return u - pos <= pos - d ? u : d;
 }
 
 // One wavefront per workgroup: kQueries == LSR_WAVE, so the workgroup's bound and its decisions are the wave's own — a
@@ -308,9 +259,6 @@ struct KnnWorkspace {
     size_t partial, grid, keys_in, keys_out, order, sorted, chunk_boxes, group_boxes, sort_temp, sort_temp_bytes, total;
 };
 
-static int64_t knn_chunks(int64_t n) { return (n + kChunk - 1) / kChunk; }
-static int64_t knn_groups(int64_t n) { return (knn_chunks(n) + kGroup - 1) / kGroup; }
-
 static KnnWorkspace knn_workspace(int64_t n) {
     KnnWorkspace w;
     size_t at = 0;
@@ -321,15 +269,50 @@ static KnnWorkspace knn_workspace(int64_t n) {
     w.keys_out = take((size_t)n * sizeof(uint64_t));
     w.order = take((size_t)n * sizeof(uint32_t));
     w.sorted = take((size_t)n * sizeof(float4));
-    w.chunk_boxes = take((size_t)knn_chunks(n) * 2 * sizeof(float4));
-    w.group_boxes = take((size_t)knn_groups(n) * 2 * sizeof(float4));
-    // the sort's temporary storage: its own copies of the keys and the values, histograms and per-block states.  What it
-    // asks for depends on the device's tuning, which cannot be asked without a device: this is a reservation, and
-    // lsr_knn3 checks the sort's own figure against it before it launches anything.
-    w.sort_temp_bytes = align_up((size_t)n * sizeof(uint64_t)) + align_up((size_t)n * sizeof(uint32_t)) + (size_t)n * 16 + (1u << 20);
+    w.chunk_boxes = take((size_t)morton_chunks(n) * 2 * sizeof(float4));
+    w.group_boxes = take((size_t)morton_groups(n) * 2 * sizeof(float4));
+    w.sort_temp_bytes = morton_sort_temp_bytes(n);      // a reservation: lsr_knn3 checks the sort's own figure against it
     w.sort_temp = take(w.sort_temp_bytes);
     w.total = at;
     return w;
+}
+
+// ---- the build of the index (lsr_morton.h): what lsr_knn3 and nn.hip share ----
+
+int morton_sort_fits(int64_t n, size_t reserved, hipStream_t stream) {
+    const rocprim::counting_iterator<uint32_t> iota(0u);
+    size_t temp_bytes = 0;
+    const hipError_t e = rocprim::radix_sort_pairs(nullptr, temp_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, iota,
+                                                   (uint32_t *)nullptr, (unsigned int)n, 0u, 3u * kCellBits, stream);
+    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
+    return temp_bytes > reserved ? LSR_EUNSUPPORTED : LSR_OK;
+}
+
+static unsigned morton_blocks(int64_t n) { return (unsigned)std::min<int64_t>((n + kKnnThreads - 1) / kKnnThreads, kBBoxBlocks); }
+
+void morton_grid(int64_t n, const float *points, float *partial, float *grid, hipStream_t stream) {
+    const unsigned blocks = morton_blocks(n);
+    hipLaunchKernelGGL(k_knn_bbox, dim3(blocks), dim3(kKnnThreads), 0, stream, n, points, partial);
+    hipLaunchKernelGGL(k_knn_bbox_final, dim3(1), dim3(kKnnThreads), 0, stream, (int)blocks, partial, grid);
+}
+
+int morton_sort(int64_t n, const float *points, const float *grid, uint64_t *keys_in, uint64_t *keys_out, uint32_t *order,
+                void *sort_temp, size_t sort_temp_bytes, hipStream_t stream) {
+    const rocprim::counting_iterator<uint32_t> iota(0u);
+    hipLaunchKernelGGL(k_knn_keys, dim3(morton_blocks(n)), dim3(kKnnThreads), 0, stream, n, points, grid, keys_in);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess)
+        e = rocprim::radix_sort_pairs(sort_temp, sort_temp_bytes, keys_in, keys_out, iota, order, (unsigned int)n, 0u,
+                                      3u * kCellBits, stream);
+    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
+    return LSR_OK;
+}
+
+void morton_gather(int64_t n, const float *points, const uint32_t *order, float4 *sorted, float4 *chunk_boxes,
+                   float4 *group_boxes, hipStream_t stream) {
+    const int64_t chunks = morton_chunks(n), groups = morton_groups(n);
+    hipLaunchKernelGGL(k_knn_gather, dim3((unsigned)chunks), dim3(kChunk), 0, stream, n, points, order, sorted, chunk_boxes);
+    hipLaunchKernelGGL(k_knn_group_boxes, dim3((unsigned)groups), dim3(kGroup), 0, stream, chunks, chunk_boxes, group_boxes);
 }
 
 }  // namespace lsr
@@ -361,26 +344,14 @@ int lsr_knn3(int64_t n, const float *points, float *mean_dist2, float *dist2, in
     uint32_t *order = (uint32_t *)(base + w.order);
     float4 *sorted = (float4 *)(base + w.sorted), *chunk_boxes = (float4 *)(base + w.chunk_boxes);
     float4 *group_boxes = (float4 *)(base + w.group_boxes);
-    const rocprim::counting_iterator<uint32_t> iota(0u);
-    size_t temp_bytes = 0;
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, temp_bytes, keys_in, keys_out, iota, order, (unsigned int)n, 0u,
-                                             3u * kCellBits, s);
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    if (temp_bytes > w.sort_temp_bytes) return LSR_EUNSUPPORTED;
-    const int64_t chunks = knn_chunks(n), groups = knn_groups(n);
-    const unsigned blocks = (unsigned)std::min<int64_t>((n + kKnnThreads - 1) / kKnnThreads, kBBoxBlocks);
-    hipLaunchKernelGGL(k_knn_bbox, dim3(blocks), dim3(kKnnThreads), 0, s, n, points, partial);
-    hipLaunchKernelGGL(k_knn_bbox_final, dim3(1), dim3(kKnnThreads), 0, s, (int)blocks, partial, grid);
-    hipLaunchKernelGGL(k_knn_keys, dim3(blocks), dim3(kKnnThreads), 0, s, n, points, grid, keys_in);
-    e = hipGetLastError();
-    if (e == hipSuccess)
-        e = rocprim::radix_sort_pairs(base + w.sort_temp, temp_bytes, keys_in, keys_out, iota, order, (unsigned int)n, 0u,
-                                      3u * kCellBits, s);
-    if (e != hipSuccess) { note_hip_error((int)e); return LSR_ELAUNCH; }
-    hipLaunchKernelGGL(k_knn_gather, dim3((unsigned)chunks), dim3(kChunk), 0, s, n, points, order, sorted, chunk_boxes);
-    hipLaunchKernelGGL(k_knn_group_boxes, dim3((unsigned)groups), dim3(kGroup), 0, s, chunks, chunk_boxes, group_boxes);
-    hipLaunchKernelGGL(k_knn_search, dim3((unsigned)((n + kQueries - 1) / kQueries)), dim3(kQueries), 0, s, n, chunks, groups, sorted, chunk_boxes,
-                       group_boxes, mean_dist2, dist2, index);
+    int rc = morton_sort_fits(n, w.sort_temp_bytes, s);
+    if (rc != LSR_OK) return rc;
+    morton_grid(n, points, partial, grid, s);
+    rc = morton_sort(n, points, grid, keys_in, keys_out, order, base + w.sort_temp, w.sort_temp_bytes, s);
+    if (rc != LSR_OK) return rc;
+    morton_gather(n, points, order, sorted, chunk_boxes, group_boxes, s);
+    hipLaunchKernelGGL(k_knn_search, dim3((unsigned)((n + kQueries - 1) / kQueries)), dim3(kQueries), 0, s, n, morton_chunks(n),
+                       morton_groups(n), sorted, chunk_boxes, group_boxes, mean_dist2, dist2, index);
     return launch_status();
 }
 

@@ -12,6 +12,9 @@ set.  This module is that step:
    cube: no case table, unambiguous, watertight): ``(vertices, faces, colors)``.  It reads the two counts once, which is
    its only synchronisation, and allocates exactly.
 3. :func:`save_mesh_ply` / :func:`load_mesh_ply` write and read a binary little-endian triangle-mesh ``.ply`` with numpy.
+4. :func:`mesh_components` labels the connected components of a mesh (csrc/mesh_components.hip: hook and compress rounds
+   with integer ``atomicMin``) and :func:`clean_mesh` keeps the largest of them: the ``post_process_mesh`` step that
+   removes the floaters every TSDF of rendered depth contains.
 
 :meth:`latentsplat_amd.scene_model.GaussianScene.extract_mesh` composes render, fusion and extraction.
 
@@ -139,6 +142,93 @@ class TSDFVolume:
             _lib.call("lsr_mesh_emit", C.byref(self._dims), ptr(self.tsdf), ptr(self.weight), ptr(self.color), float(min_weight),
                       ptr(ws), ptr(counts), nv, nf, ptr(vertices), ptr(colors), ptr(faces), _args.stream(dev))
         return vertices, faces, colors
+
+
+def _faces(faces, num_vertices=None) -> Tensor:
+    faces = _args.i32(_WHO, "faces", faces)
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise _lib.LsrError(f"faces must be (nf, 3), got {tuple(faces.shape)}")
+    if faces.shape[0] > _lib.MESH_MAX_ELEMENTS or (num_vertices is not None and not 0 <= num_vertices <= _lib.MESH_MAX_ELEMENTS):
+        raise _lib.LsrError(f"a mesh has at most {_lib.MESH_MAX_ELEMENTS} vertices and faces")
+    return faces.detach().contiguous()
+
+
+def mesh_components(faces: Tensor, num_vertices: int, return_rounds: bool = False):
+    """``labels (num_vertices,) int32``: the lowest vertex index of every vertex's connected component.  Two vertices are
+    connected when a face of ``faces (nf, 3) int32`` names both BY INDEX (:meth:`TSDFVolume.extract_mesh` numbers a vertex
+    once per lattice edge, so its meshes qualify; a soup with duplicated coordinates does not).  A vertex in no face
+    labels itself.  A corner outside ``[0, num_vertices)`` is refused before anything is launched (one reduction, one
+    host read).  The rounds of hooking and compression (include/lsr_mesh.h, part C) are driven from here: the changed
+    flag is read after every round, and more than 64 rounds raise instead of looping (O(log nv) are needed).
+    ``return_rounds``: also the number of rounds run, the confirming one included."""
+    num_vertices = int(num_vertices)
+    f = _faces(faces, num_vertices)
+    dev, nf = f.device, f.shape[0]
+    if nf > 0:
+        lo, hi = (int(x) for x in torch.stack([f.min(), f.max()]).tolist())
+        if lo < 0 or hi >= num_vertices:
+            raise _lib.LsrError(f"faces name vertices {lo}..{hi}, outside 0..{num_vertices - 1}")
+    labels = torch.empty((num_vertices,), dtype=torch.int32, device=dev)
+    changed = torch.zeros((1,), dtype=torch.int32, device=dev)
+    rounds = 0
+    with torch.cuda.device(dev):
+        _lib.call("lsr_mesh_components_init", num_vertices, ptr(labels), _args.stream(dev))
+        if nf > 0 and num_vertices > 0:
+            while True:
+                if rounds == _lib.MESH_COMPONENT_ROUNDS:
+                    raise _lib.LsrError(f"mesh_components did not converge in {rounds} rounds")
+                _lib.call("lsr_mesh_components_round", num_vertices, nf, ptr(f), ptr(labels), ptr(changed), _args.stream(dev))
+                rounds += 1
+                if int(changed.item()) == 0:
+                    break
+    return (labels, rounds) if return_rounds else labels
+
+
+def clean_mesh(vertices: Tensor, faces: Tensor, colors: Optional[Tensor] = None, keep_largest: Optional[int] = None,
+               min_faces: Optional[int] = None):
+    """``(vertices, faces, colors, info)`` without the small connected components (the published ``post_process_mesh``).
+    A component's size is its FACE count.  ``keep_largest=K`` keeps the K largest (ties toward the lower label, the
+    component's lowest vertex index); ``min_faces=F`` keeps those of at least F faces; with both a component has to pass
+    both; with neither the mesh is returned as it is.  Vertices in no face form components of size 0: any filter drops
+    them.  Kept faces and vertices stay in their original order, indices remapped.  The labels are HIP
+    (:func:`mesh_components`); the compaction is plain torch (``bincount``, ``cumsum``) with one host read.
+    ``info``: ``components`` (those with at least one face), ``components_kept``, ``faces_kept``, ``faces_dropped``,
+    ``vertices_kept``, ``vertices_dropped``."""
+    vertices = _args.f32(_WHO, "vertices", vertices)
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise _lib.LsrError(f"vertices must be (nv, 3), got {tuple(vertices.shape)}")
+    nv, dev = vertices.shape[0], vertices.device
+    f = _faces(_args.i32(_WHO, "faces", faces, None, dev), nv)
+    if colors is not None:
+        colors = _args.f32(_WHO, "colors", colors, (nv, 3), dev)
+    for name, value in (("keep_largest", keep_largest), ("min_faces", min_faces)):
+        if value is not None and int(value) < 0:
+            raise _lib.LsrError(f"{name} must not be negative")
+    nf = f.shape[0]
+    labels = mesh_components(f, nv).long()
+    size = torch.bincount(labels[f[:, 0].long()], minlength=nv) if nf > 0 else torch.zeros((nv,), dtype=torch.int64, device=dev)
+    keep = size > 0                                        # per label: a component with faces
+    components = keep.sum()
+    if min_faces is not None:
+        keep = keep & (size >= int(min_faces))
+    if keep_largest is not None:
+        # the K largest, ties toward the lower label: a stable descending sort of the sizes keeps equal sizes in label order
+        order = torch.sort(size, descending=True, stable=True).indices[:int(keep_largest)]
+        top = torch.zeros_like(keep)
+        top[order] = True
+        keep = keep & top
+    if keep_largest is None and min_faces is None:
+        keep_vertex = torch.ones((nv,), dtype=torch.bool, device=dev)
+        keep_face = torch.ones((nf,), dtype=torch.bool, device=dev)
+    else:
+        keep_vertex = keep[labels]
+        keep_face = keep_vertex[f[:, 0].long()] if nf > 0 else torch.zeros((0,), dtype=torch.bool, device=dev)
+    remap = torch.cumsum(keep_vertex.long(), 0) - 1
+    counts = torch.stack([components, (keep & (size > 0)).sum(), keep_face.sum(), keep_vertex.sum()]).tolist()      # the one host read
+    out_faces = remap[f[keep_face].long()].to(torch.int32)
+    info = dict(components=int(counts[0]), components_kept=int(counts[1]), faces_kept=int(counts[2]), faces_dropped=nf - int(counts[2]),
+                vertices_kept=int(counts[3]), vertices_dropped=nv - int(counts[3]))
+    return vertices[keep_vertex], out_faces, None if colors is None else colors[keep_vertex], info
 
 
 def _numpy(a, dtype):

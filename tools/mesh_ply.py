@@ -12,10 +12,13 @@
 `--voxel-size` is in scene units (default: 1/128 of the scene's extent); `--trunc` defaults to 4 voxel sizes (a default,
 not a measurement).  `--filter-3d` renders with the 3D smoothing filter of the same cameras and
 `--antialiasing` with the rasterizer's opacity compensation, as a scene trained with them expects.
+`--keep-largest K` keeps the K connected components with the most faces and `--min-faces F` those of at least F faces
+(`clean_mesh`, INTEGRATION.md §25: the floaters every TSDF of rendered depth contains); both are off by default and the
+output is unchanged without them.
 A scene trained with `tools/fit_ply.py --normal-reg` has the depth this step needs.
 
 usage: python tools/mesh_ply.py scene.ply --out mesh.ply [--views 32] [--size 512] [--voxel-size v] [--trunc t] [--distance 2.5]
-                                [--filter-3d] [--antialiasing]"""
+                                [--filter-3d] [--antialiasing] [--keep-largest K] [--min-faces F]"""
 from __future__ import annotations
 
 import argparse
@@ -45,11 +48,13 @@ def main(argv=None) -> dict:
     ap.add_argument("--distance", type=float, default=2.5, help="circle radius in scene extents")
     ap.add_argument("--filter-3d", action="store_true", help="render with the 3D smoothing filter of these cameras")
     ap.add_argument("--antialiasing", action="store_true", help="opacity compensation for the 0.3 screen-space low-pass")
+    ap.add_argument("--keep-largest", type=int, default=None, help="keep the K connected components with the most faces")
+    ap.add_argument("--min-faces", type=int, default=None, help="keep the connected components of at least F faces")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         sys.exit("mesh_ply needs an MI355X: no ROCm device is visible (there is no CPU fallback)")
     from latentsplat_amd import GaussianScene
-    from latentsplat_amd.mesh import save_mesh_ply
+    from latentsplat_amd.mesh import clean_mesh, save_mesh_ply
     from latentsplat_amd.rasterizer import build_view_table, get_color_sh_convention, set_color_sh_convention
     dev = torch.device("cuda:0")
     convention = get_color_sh_convention()
@@ -65,12 +70,17 @@ def main(argv=None) -> dict:
             if a.filter_3d:
                 kw["filter_3d"] = scene.compute_filter_3d(views, a.size)
             vertices, faces, colors = scene.extract_mesh(views, a.size, a.size, voxel, trunc=a.trunc, **kw)
+            cleanup = None
+            if a.keep_largest is not None or a.min_faces is not None:
+                vertices, faces, colors, cleanup = clean_mesh(vertices, faces, colors, keep_largest=a.keep_largest, min_faces=a.min_faces)
     finally:
         set_color_sh_convention(convention)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     save_mesh_ply(a.out, vertices, faces, colors)
     status = dict(gaussians=scene.num_gaussians, views=a.views, size=a.size, voxel_size=voxel, vertices=int(vertices.shape[0]),
                   faces=int(faces.shape[0]), filter_3d=bool(a.filter_3d), antialiasing=bool(a.antialiasing), out=a.out)
+    if cleanup is not None:
+        status["cleanup"] = dict(keep_largest=a.keep_largest, min_faces=a.min_faces, **cleanup)
     print(json.dumps(status))
     return status
 
