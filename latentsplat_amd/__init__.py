@@ -13,7 +13,10 @@ instruction and a bit-reproducible float64 centroid update, in HIP; quantised sc
 truncated signed distance volume in one pass over the volume per batch of views, and marching tetrahedra, in HIP; mesh ``.ply``
 files; connected components and the cleanup that keeps the largest clusters), ``nn`` (the exact nearest neighbour of one
 cloud's points in another: a persistent index over a reference cloud, in HIP), ``mesh_eval`` (what scores a mesh against a
-ground-truth cloud: accuracy, completeness, Chamfer, precision / recall / F-score, and an area-weighted mesh sampler) and ``synthetic`` (seeded scenes for tests / bench).
+ground-truth cloud: accuracy, completeness, Chamfer, precision / recall / F-score, and an area-weighted mesh sampler), ``images`` (photographs
+resampled onto the rasterizer's centred, distortion-free camera at the training resolution, with a coverage map, in HIP),
+``capture`` (a photographed capture: the COLMAP sparse model through a strict host reader, prepared targets, a train / test
+split, camera tables and the initial scene) and ``synthetic`` (seeded scenes for tests / bench).
 """
 __version__ = "0.1.0"
 
@@ -40,6 +43,8 @@ _LAZY = {"rotate_sh": "sh_rotate", "GaussianAdapter": "gaussian_adapter", "Gauss
          "mesh_components": "mesh", "clean_mesh": "mesh",
          "NearestIndex": "nn", "nearest": "nn",
          "cloud_metrics": "mesh_eval", "sample_mesh": "mesh_eval",
+         "prepare_images": "images", "SourceCamera": "images",
+         "Capture": "capture", "read_colmap_model": "capture", "ColmapModel": "capture",
          "adam_step": "optim", "SceneAdam": "optim", "expon_lr": "optim", "visible_from_radii": "optim"}
 
 

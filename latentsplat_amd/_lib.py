@@ -1,5 +1,5 @@
 """ctypes binding of ``liblsr_hip.so`` (C ABI: include/lsr_rasterizer.h, include/lsr_adapter.h, include/lsr_latent.h, include/lsr_ply.h,
-include/lsr_sh_rotate.h, include/lsr_depth_head.h, include/lsr_scene.h, include/lsr_loss.h, include/lsr_density.h, include/lsr_optim.h, include/lsr_knn.h, include/lsr_mcmc.h, include/lsr_filter3d.h, include/lsr_bilagrid.h, include/lsr_transform.h, include/lsr_vq.h, include/lsr_pose.h, include/lsr_normals.h, include/lsr_mesh.h, include/lsr_nn.h).
+include/lsr_sh_rotate.h, include/lsr_depth_head.h, include/lsr_scene.h, include/lsr_loss.h, include/lsr_density.h, include/lsr_optim.h, include/lsr_knn.h, include/lsr_mcmc.h, include/lsr_filter3d.h, include/lsr_bilagrid.h, include/lsr_transform.h, include/lsr_vq.h, include/lsr_pose.h, include/lsr_normals.h, include/lsr_mesh.h, include/lsr_nn.h, include/lsr_colmap.h, include/lsr_image.h).
 
 The library is built in-tree by ``latentsplat_amd/csrc/Makefile`` (``__graft_entry__.build()``).
 There is no CPU fallback: if the shared object is missing or not loadable this module raises, and
@@ -287,6 +287,30 @@ TSDF_MIN_EXTENT, TSDF_MAX_EXTENT, TSDF_MAX_VOXELS, TSDF_MAX_VIEWS = 2, 2048, 1 <
 MESH_MAX_ELEMENTS, MESH_COMPONENT_ROUNDS = 1 << 30, 64              # LSR_MESH_MAX_ELEMENTS; the cap of mesh.mesh_components
 
 
+class ColmapCounts(C.Structure):     # lsr_colmap_counts (include/lsr_colmap.h)
+    _fields_ = [("cameras", C.c_int64), ("images", C.c_int64), ("points", C.c_int64), ("name_bytes", C.c_int64),
+                ("format", C.c_int32), ("reserved", C.c_int32)]
+
+
+COLMAP_BINARY, COLMAP_TEXT = 0, 1                                   # lsr_colmap_counts.format
+COLMAP_MAX_PARAMS, COLMAP_MAX_EXTENT, COLMAP_MAX_NAME = 8, 65536, 1023   # LSR_COLMAP_MAX_*
+# COLMAP's model ids the reader takes: name, parameter count (f cx cy | fx fy cx cy | f cx cy k | f cx cy k1 k2 | fx fy cx cy k1 k2 p1 p2)
+COLMAP_MODELS = {0: ("SIMPLE_PINHOLE", 3), 1: ("PINHOLE", 4), 2: ("SIMPLE_RADIAL", 4), 3: ("RADIAL", 5), 4: ("OPENCV", 8)}
+
+
+class ImageCamera(C.Structure):      # lsr_image_camera (include/lsr_image.h)
+    _fields_ = [("model", C.c_int32), ("reserved", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("dist", C.c_float * 4)]
+
+
+class ImageDims(C.Structure):        # lsr_image_dims
+    _fields_ = [("batch", C.c_int32), ("src_height", C.c_int32), ("src_width", C.c_int32), ("channels", C.c_int32),
+                ("height", C.c_int32), ("width", C.c_int32), ("fx", C.c_float), ("fy", C.c_float)]
+
+
+IMAGE_MAX_SUBSAMPLES, IMAGE_MAX_EXTENT = 16, 65536                  # LSR_IMAGE_MAX_*
+
+
 def transform_record_floats(degree: int) -> int:
     """LSR_TRANSFORM_RECORD_FLOATS: the 20-float header and the band blocks 1..degree (20, 29, 54, 103, 184)."""
     return TRANSFORM_HEADER_FLOATS + sh_rotate_table_floats(degree) - 1
@@ -407,6 +431,13 @@ PROTOTYPES = {
     "lsr_nn_build": (_INT, [_I64, _P, _P, _P, _P]),
     "lsr_nn_query_workspace_bytes": (_SZ, [_I64]),
     "lsr_nn_query": (_INT, [_I64, _P, _I64, _P, _P, _P, _P, _P]),
+    "lsr_colmap_count": (_INT, [_STR, _ptr_to(ColmapCounts)]),
+    "lsr_colmap_read_cameras": (_INT, [_STR, _P, _P, _P, _P, _I64]),
+    "lsr_colmap_read_images": (_INT, [_STR, _P, _P, _P, _P, _P, _P, _I64, _I64]),
+    "lsr_colmap_read_points": (_INT, [_STR, _P, _P, _P, _P, _I64]),
+    "lsr_colmap_last_error": (_STR, None),
+    "lsr_image_subsamples": (_INT, [_ptr_to(ImageDims), _ptr_to(ImageCamera)]),
+    "lsr_image_prepare": (_INT, [_ptr_to(ImageDims), _ptr_to(ImageCamera), _P, _P, _P, _P, _P]),
 }
 EXPORTS = tuple(PROTOTYPES)
 

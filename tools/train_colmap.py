@@ -1,0 +1,214 @@
+#!/usr/bin/env python
+"""Train a 3DGS scene from a photographed capture: a COLMAP sparse model and its photographs.
+
+  1. `Capture.load(ROOT, --sparse, --images, --resolution)`: the model through the library's host reader, the photographs
+     resampled in HIP onto the centred, distortion-free camera the rasterizer implements (`lsr_image_prepare`), with a
+     coverage map per image; every `--hold`-th image by sorted name is held out (the published rule; 0: none);
+  2. the scene starts from the model's points: `capture.initial_scene(--sh-degree)` (`GaussianScene.from_point_cloud`);
+  3. each step draws `--batch` training views of one output size from a seeded shuffle (every view once per epoch) and
+     minimises `photometric_loss(render * coverage, target * coverage, --lambda-dssim)`: where the photograph has nothing to
+     say both sides are 0;
+  4. `SceneAdam`, one parameter group per tensor at the published trainer's customary rates (position 1.6e-4 -> 1.6e-6 times
+     `cameras_extent` on the `expon_lr` schedule over the run, f_dc 2.5e-3, f_rest f_dc / 20, opacity 5e-2, scaling 5e-3,
+     rotation 1e-3; eps 1e-15): defaults, not measurements;
+  5. `--strategy adc` (the default): `DensityControl` every `--densify-interval` steps between `--densify-from` and
+     `--densify-until`, opacity resets every `--opacity-reset-interval`; the loss is a mean over the batch, so the
+     threshold defaults to `2e-4 / batch`.  `--strategy mcmc`: `MCMCControl` on the same schedule up to `--cap-max`, its two
+     regularisers in the loss, position noise after every step.  `--densify-interval 0` turns either off;
+  6. `--sh-degree-interval I`: one more SH band every I steps (0: never).  `--antialiasing`: the rasterizer's opacity
+     compensation.  `--filter-3d`: the 3D smoothing filter over the training cameras, recomputed after every density event
+     and every `--filter-3d-interval` steps (per output size, the smallest filter wins);
+  7. `point_cloud.ply` and `metrics.json` in `--out`: `loss_first`, `loss_last`, `gaussians`, `ms_per_step` (after a
+     warm-up), and on the held-out views `psnr` and `ssim` (`compute_ssim`) over the covered pixels: the render and the target
+     multiplied by the coverage, the squared error averaged over the covered values only.
+
+usage: python tools/train_colmap.py ROOT --out DIR [--sparse sparse/0] [--images images] [--resolution 1] [--hold 8] [--steps 30000]
+                                    [--batch 1] [--seed 0] [--lambda-dssim 0.2] [--sh-degree 3] [--sh-degree-interval 1000]
+                                    [--strategy adc|mcmc] [--densify-interval 100] [--densify-from 500] [--densify-until 15000]
+                                    [--densify-grad-threshold 2e-4/BATCH] [--min-opacity 0.005] [--opacity-reset-interval 3000]
+                                    [--cap-max N] [--noise-lr 5e5] [--opacity-reg 0.01] [--scale-reg 0.01]
+                                    [--antialiasing] [--filter-3d] [--filter-3d-interval 100]"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import random
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+WARMUP_STEPS = 5            # steps left out of the time per step (fewer when there are fewer than 10 steps)
+EVAL_BATCH = 4
+
+
+def batches(groups: dict, batch: int, rng: random.Random):
+    """One epoch: every view once, in batches of at most `batch` views of one output size, batches in a seeded order."""
+    out = []
+    for size in sorted(groups):
+        idx = list(groups[size])
+        rng.shuffle(idx)
+        out += [(size, idx[at:at + batch]) for at in range(0, len(idx), batch)]
+    rng.shuffle(out)
+    return out
+
+
+def main(argv=None) -> dict:
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0],
+                                 epilog="The learning rates and schedules are the published trainer's customary defaults, not measurements.")
+    ap.add_argument("root")
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--sparse", default="sparse/0")
+    ap.add_argument("--images", default="images")
+    ap.add_argument("--resolution", type=float, default=1.0, help="reduce the photographs by this factor (targets of round(W / r) x round(H / r))")
+    ap.add_argument("--hold", type=int, default=8, help="every this-many-th image by sorted name is held out for testing (0: none)")
+    ap.add_argument("--steps", type=int, default=30000)
+    ap.add_argument("--batch", type=int, default=1, help="training views per step, all of one output size")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--lambda-dssim", type=float, default=0.2)
+    ap.add_argument("--sh-degree", type=int, default=3)
+    ap.add_argument("--sh-degree-interval", type=int, default=1000, help="render one more SH band every this many steps (0: never)")
+    ap.add_argument("--lr-position", type=float, default=1.6e-4, help="times cameras_extent")
+    ap.add_argument("--lr-position-final", type=float, default=1.6e-6, help="times cameras_extent, reached at --steps")
+    ap.add_argument("--lr-dc", type=float, default=2.5e-3)
+    ap.add_argument("--lr-opacity", type=float, default=5e-2)
+    ap.add_argument("--lr-scaling", type=float, default=5e-3)
+    ap.add_argument("--lr-rotation", type=float, default=1e-3)
+    ap.add_argument("--strategy", choices=("adc", "mcmc"), default="adc")
+    ap.add_argument("--densify-interval", type=int, default=100, help="a density event every this many steps (0: never)")
+    ap.add_argument("--densify-from", type=int, default=500)
+    ap.add_argument("--densify-until", type=int, default=15000)
+    ap.add_argument("--densify-grad-threshold", type=float, default=None, help="adc: on the mean view-space gradient (default 2e-4 / --batch)")
+    ap.add_argument("--min-opacity", type=float, default=0.005)
+    ap.add_argument("--opacity-reset-interval", type=int, default=3000, help="adc: reset the opacities every this many steps (0: never)")
+    ap.add_argument("--cap-max", type=int, default=1_000_000, help="mcmc: the largest number of Gaussians")
+    ap.add_argument("--noise-lr", type=float, default=5e5, help="mcmc: position noise, times the position rate")
+    ap.add_argument("--opacity-reg", type=float, default=0.01, help="mcmc: weight of mean(sigmoid(opacity)) in the loss")
+    ap.add_argument("--scale-reg", type=float, default=0.01, help="mcmc: weight of mean(exp(scaling)) in the loss")
+    ap.add_argument("--antialiasing", action="store_true")
+    ap.add_argument("--filter-3d", action="store_true")
+    ap.add_argument("--filter-3d-interval", type=int, default=100)
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.batch < 1 or a.hold < 0 or a.densify_interval < 0 or a.sh_degree_interval < 0 or a.filter_3d_interval < 1:
+        sys.exit("--steps, --batch and --filter-3d-interval must be positive; --hold and the intervals must not be negative")
+    if not 0.0 <= a.lambda_dssim <= 1.0 or not 0 <= a.sh_degree <= 4 or not a.resolution > 0:
+        sys.exit("--lambda-dssim must be in [0, 1], --sh-degree in 0..4, --resolution positive")
+    if not torch.cuda.is_available():
+        sys.exit("train_colmap needs an MI355X: no ROCm device is visible (there is no CPU fallback)")
+    from latentsplat_amd.capture import Capture
+    from latentsplat_amd.losses import compute_ssim, photometric_loss
+    from latentsplat_amd.optim import SceneAdam, expon_lr
+    dev = torch.device("cuda:0")
+    capture = Capture.load(a.root, a.sparse, a.images, a.resolution, dev)
+    train, test = capture.split(a.hold)
+    if not train:
+        sys.exit(f"--hold {a.hold} leaves no training image among {len(capture)}")
+    extent = capture.cameras_extent
+    black = torch.zeros(3, device=dev)
+    scene = capture.initial_scene(a.sh_degree)
+    gaussians_first = scene.num_gaussians
+    rates = dict(_xyz=a.lr_position * extent, _features_dc=a.lr_dc, _features_rest=a.lr_dc / 20, _opacity=a.lr_opacity,
+                 _scaling=a.lr_scaling, _rotation=a.lr_rotation)
+    opt = SceneAdam([dict(params=[p], lr=rates[name], name=name) for name, p in scene.named_parameters() if p.numel()], lr=0.0, eps=1e-15)
+    xyz_group = next(g for g in opt.param_groups if g["name"] == "_xyz")
+    gen_dev = torch.Generator(device=dev).manual_seed(a.seed)
+    rng = random.Random(a.seed)
+    control = mcmc = None
+    if a.densify_interval > 0 and a.strategy == "adc":
+        from latentsplat_amd.density import DensityControl
+        control = DensityControl(scene)
+        threshold = 2e-4 / a.batch if a.densify_grad_threshold is None else a.densify_grad_threshold
+    if a.strategy == "mcmc":
+        from latentsplat_amd.mcmc import MCMCControl
+        mcmc = MCMCControl(scene, max(a.cap_max, scene.num_gaussians), a.min_opacity)
+    groups = capture.size_groups(train)
+    group_views = {size: capture.views(idx, black) for size, idx in groups.items()}
+    filter_3d, events = None, []
+
+    def refresh_filter():
+        nonlocal filter_3d
+        if a.filter_3d:
+            per_size = [scene.compute_filter_3d(v, size[1]) for size, v in group_views.items()]
+            filter_3d = per_size[0] if len(per_size) == 1 else torch.stack(per_size).amin(dim=0)
+
+    refresh_filter()
+    warm = min(WARMUP_STEPS, a.steps // 2)
+    losses, queue, t0 = [], [], None
+    for step in range(a.steps):
+        if step == warm:
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+        if not queue:
+            queue = batches(groups, a.batch, rng)
+        (H, W), idx = queue.pop()
+        views = capture.views(idx, black)
+        target, cover = capture.targets(idx), capture.coverage(idx)[:, None]
+        opt.zero_grad(set_to_none=True)
+        collect = control is not None and step < a.densify_until
+        means2D = torch.zeros((len(idx), scene.num_gaussians, 3), device=dev, requires_grad=True) if collect else None
+        kw = dict(means2D=means2D) if collect else {}
+        render, _, _, _, radii = scene.render(views, H, W, filter_3d=filter_3d, antialiasing=a.antialiasing, **kw)
+        loss = photometric_loss(render * cover, target * cover, a.lambda_dssim)
+        if mcmc is not None:
+            loss = loss + mcmc.regularizer(a.opacity_reg, a.scale_reg)
+        loss.backward()
+        xyz_group["lr"] = expon_lr(step, a.lr_position * extent, a.lr_position_final * extent, a.steps)
+        opt.step()
+        losses.append(loss.detach())
+        done = step + 1
+        event = a.densify_interval > 0 and a.densify_from < done <= a.densify_until and done % a.densify_interval == 0
+        if collect:
+            control.update(means2D.grad, radii)
+            if event:
+                size = 20.0 if a.opacity_reset_interval and done > a.opacity_reset_interval else 0.0
+                events.append(dict(step=done, **control.densify_and_prune(opt, threshold, a.min_opacity, extent, size, generator=gen_dev)))
+                refresh_filter()
+        if mcmc is not None:
+            if event:
+                events.append(dict(step=done, **mcmc.step(opt, gen_dev)))
+                refresh_filter()
+            mcmc.inject_noise(xyz_group["lr"], a.noise_lr, gen_dev)
+        if control is not None and a.opacity_reset_interval and done % a.opacity_reset_interval == 0 and done <= a.densify_until:
+            control.reset_opacity(opt)
+        if a.sh_degree_interval and done % a.sh_degree_interval == 0:
+            scene.oneup_sh_degree()
+        if a.filter_3d and done % a.filter_3d_interval == 0 and not event:
+            refresh_filter()
+    torch.cuda.synchronize(dev)
+    per_step = (time.perf_counter() - t0) / (a.steps - warm)
+    os.makedirs(a.out, exist_ok=True)
+    scene.save_ply(os.path.join(a.out, "point_cloud.ply"))
+    res = dict(loss_first=float(losses[0]), loss_last=float(losses[-1]), steps=a.steps, gaussians=scene.num_gaussians,
+               gaussians_first=gaussians_first, ms_per_step=1e3 * per_step, timed_steps=a.steps - warm, images=len(capture),
+               train_views=len(train), test_views=len(test), sizes=[list(s) for s in sorted(capture.size_groups())],
+               resolution=a.resolution, hold=a.hold, batch=a.batch, seed=a.seed, cameras_extent=extent, lambda_dssim=a.lambda_dssim,
+               strategy=a.strategy, density_events=events, sh_degree=a.sh_degree, active_sh_degree_last=scene.active_sh_degree,
+               antialiasing=bool(a.antialiasing), filter_3d=bool(a.filter_3d), format=capture.model.format)
+    if test:
+        psnr, ssim, names = [], [], []
+        with torch.no_grad():
+            for (H, W), idx in sorted(capture.size_groups(test).items()):
+                for at in range(0, len(idx), EVAL_BATCH):
+                    part = idx[at:at + EVAL_BATCH]
+                    cover = capture.coverage(part)[:, None]
+                    render = scene.render(capture.views(part, black), H, W, filter_3d=filter_3d, antialiasing=a.antialiasing)[0].clamp(0.0, 1.0) * cover
+                    target = capture.targets(part) * cover
+                    mse = ((render - target) ** 2).sum(dim=(1, 2, 3)) / (3.0 * cover.sum(dim=(1, 2, 3))).clamp_min(1.0)
+                    psnr += (-10.0 * torch.log10(mse.clamp_min(1e-12))).tolist()
+                    ssim += compute_ssim(target, render).tolist() if min(H, W) >= 11 else [None] * len(part)     # (an 11 x 11 window)
+                    names += [capture.names[k] for k in part]
+        scored = [s for s in ssim if s is not None]
+        res.update(psnr=sum(psnr) / len(psnr), ssim=sum(scored) / len(scored) if scored else None, test=dict(names=names, psnr=psnr, ssim=ssim))
+    with open(os.path.join(a.out, "metrics.json"), "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps({k: v for k, v in res.items() if k not in ("test", "density_events")}))
+    return res
+
+
+if __name__ == "__main__":
+    main()
