@@ -11,8 +11,9 @@
  *   points3D.bin  uint64 n, then per point   uint64 id, double xyz[3], uint8 rgb[3], double error, uint64 L, then
  *                 L x (uint32 image_id, uint32 point2D_idx)
  * The text files hold the same fields, blank separated, one record per line, `#` comments and empty lines between
- * records; an image is two lines, the second (its 2D observations) possibly empty.  The 2D observations and the tracks
- * are skipped, each skip checked against the file's size before seeking.
+ * records; an image is two lines, the second (its 2D observations) possibly empty.  lsr_colmap_count and the three
+ * lsr_colmap_read_cameras / _images / _points skip the 2D observations and the tracks, each skip checked against the
+ * file's size before seeking; the observations are read by lsr_colmap_count_observations / lsr_colmap_read_observations.
  *
  * Camera models (id, name, P, parameter order): 0 SIMPLE_PINHOLE 3 f cx cy; 1 PINHOLE 4 fx fy cx cy; 2 SIMPLE_RADIAL 4
  * f cx cy k; 3 RADIAL 5 f cx cy k1 k2; 4 OPENCV 8 fx fy cx cy k1 k2 p1 p2.  Any other model is LSR_EUNSUPPORTED, and
@@ -60,6 +61,21 @@ int lsr_colmap_read_cameras(const char *dir, uint32_t *ids, int32_t *models, int
 int lsr_colmap_read_images(const char *dir, uint32_t *ids, double *qvec, double *tvec, uint32_t *camera_ids, char *names,
                            int64_t *name_offsets, int64_t capacity, int64_t name_capacity);
 int lsr_colmap_read_points(const char *dir, uint64_t *ids, double *xyz, uint8_t *rgb, double *errors, int64_t capacity);
+
+/* The 2D observations of the images: which sparse point each image sees, and where.  Only observations that carry a point
+ * are counted and returned (binary: point3D_id != 2^64 - 1; text: != -1); the others are parsed and checked all the same.
+ * Both calls walk and check all three files as lsr_colmap_count does, so every refusal of that walk applies, and further
+ * refuse (LSR_EINVAL) a non-finite x or y, an observation line in images.txt that is not whole X Y POINT3D_ID triples, a
+ * binary observation count that the rest of the file cannot hold (checked before the loop is sized by it), and, in the
+ * read, more images than `image_capacity` or more observations with a point than `capacity`.
+ *   count: *total, written only on LSR_OK.
+ *   read:  offsets[image_capacity + 1] (image k, in file order, owns [offsets[k], offsets[k + 1]); entries beyond the
+ *          file's images repeat the total), xy[capacity][2] (COLMAP's measured position in source pixels, as stored),
+ *          point_ids[capacity]; each image's observations in their own order.  A point id that points3D does not hold is
+ *          NOT refused here (the files are walked one at a time): the caller that joins them checks it. */
+int lsr_colmap_count_observations(const char *dir, int64_t *total);
+int lsr_colmap_read_observations(const char *dir, int64_t *offsets, double *xy, uint64_t *point_ids, int64_t image_capacity,
+                                 int64_t capacity);
 
 /* What the calling thread's last lsr_colmap_* call refused, in words: the file, the record and the reason ("" after a call
  * that succeeded).  The pointer stays valid until the thread's next call into the reader. */

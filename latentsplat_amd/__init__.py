@@ -16,7 +16,8 @@ cloud's points in another: a persistent index over a reference cloud, in HIP), `
 ground-truth cloud: accuracy, completeness, Chamfer, precision / recall / F-score, and an area-weighted mesh sampler), ``images`` (photographs
 resampled onto the rasterizer's centred, distortion-free camera at the training resolution, with a coverage map, in HIP),
 ``capture`` (a photographed capture: the COLMAP sparse model through a strict host reader, prepared targets, a train / test
-split, camera tables and the initial scene) and ``synthetic`` (seeded scenes for tests / bench).
+split, camera tables and the initial scene), ``depth_sup`` (depth supervision for captures: sparse-point and monocular-prior
+inverse-depth targets, and the fused inverse-depth L1 loss in HIP) and ``synthetic`` (seeded scenes for tests / bench).
 """
 __version__ = "0.1.0"
 
@@ -44,6 +45,8 @@ _LAZY = {"rotate_sh": "sh_rotate", "GaussianAdapter": "gaussian_adapter", "Gauss
          "NearestIndex": "nn", "nearest": "nn",
          "cloud_metrics": "mesh_eval", "sample_mesh": "mesh_eval",
          "prepare_images": "images", "SourceCamera": "images",
+         "inverse_depth_loss": "depth_sup", "sparse_inverse_depth": "depth_sup", "align_depth_prior": "depth_sup",
+         "load_depth_prior": "depth_sup", "prepare_depth_priors": "depth_sup",
          "Capture": "capture", "read_colmap_model": "capture", "ColmapModel": "capture",
          "adam_step": "optim", "SceneAdam": "optim", "expon_lr": "optim", "visible_from_radii": "optim"}
 

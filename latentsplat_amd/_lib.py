@@ -1,5 +1,5 @@
 """ctypes binding of ``liblsr_hip.so`` (C ABI: include/lsr_rasterizer.h, include/lsr_adapter.h, include/lsr_latent.h, include/lsr_ply.h,
-include/lsr_sh_rotate.h, include/lsr_depth_head.h, include/lsr_scene.h, include/lsr_loss.h, include/lsr_density.h, include/lsr_optim.h, include/lsr_knn.h, include/lsr_mcmc.h, include/lsr_filter3d.h, include/lsr_bilagrid.h, include/lsr_transform.h, include/lsr_vq.h, include/lsr_pose.h, include/lsr_normals.h, include/lsr_mesh.h, include/lsr_nn.h, include/lsr_colmap.h, include/lsr_image.h).
+include/lsr_sh_rotate.h, include/lsr_depth_head.h, include/lsr_scene.h, include/lsr_loss.h, include/lsr_density.h, include/lsr_optim.h, include/lsr_knn.h, include/lsr_mcmc.h, include/lsr_filter3d.h, include/lsr_bilagrid.h, include/lsr_transform.h, include/lsr_vq.h, include/lsr_pose.h, include/lsr_normals.h, include/lsr_mesh.h, include/lsr_nn.h, include/lsr_colmap.h, include/lsr_image.h, include/lsr_depth_loss.h).
 
 The library is built in-tree by ``latentsplat_amd/csrc/Makefile`` (``__graft_entry__.build()``).
 There is no CPU fallback: if the shared object is missing or not loadable this module raises, and
@@ -311,6 +311,16 @@ class ImageDims(C.Structure):        # lsr_image_dims
 IMAGE_MAX_SUBSAMPLES, IMAGE_MAX_EXTENT = 16, 65536                  # LSR_IMAGE_MAX_*
 
 
+class DepthLossDims(C.Structure):    # lsr_depth_loss_dims (include/lsr_depth_loss.h)
+    _fields_ = [("num_views", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("align", C.c_int32),
+                ("normalize", C.c_int32), ("alpha_min", C.c_float), ("reserved0", C.c_int32), ("reserved1", C.c_int32)]
+
+
+DEPTH_ALIGN_GIVEN, DEPTH_ALIGN_FIT = 0, 1                           # LSR_DEPTH_ALIGN_*
+DEPTH_NORM_PIXELS, DEPTH_NORM_WEIGHTS = 0, 1                        # LSR_DEPTH_NORM_*
+DEPTH_LOSS_CHUNK = 2048                                             # LSR_DEPTH_LOSS_CHUNK: pixels of a view per workgroup
+
+
 def transform_record_floats(degree: int) -> int:
     """LSR_TRANSFORM_RECORD_FLOATS: the 20-float header and the band blocks 1..degree (20, 29, 54, 103, 184)."""
     return TRANSFORM_HEADER_FLOATS + sh_rotate_table_floats(degree) - 1
@@ -435,9 +445,14 @@ PROTOTYPES = {
     "lsr_colmap_read_cameras": (_INT, [_STR, _P, _P, _P, _P, _I64]),
     "lsr_colmap_read_images": (_INT, [_STR, _P, _P, _P, _P, _P, _P, _I64, _I64]),
     "lsr_colmap_read_points": (_INT, [_STR, _P, _P, _P, _P, _I64]),
+    "lsr_colmap_count_observations": (_INT, [_STR, _ptr_to(_I64)]),
+    "lsr_colmap_read_observations": (_INT, [_STR, _P, _P, _P, _I64, _I64]),
     "lsr_colmap_last_error": (_STR, None),
     "lsr_image_subsamples": (_INT, [_ptr_to(ImageDims), _ptr_to(ImageCamera)]),
     "lsr_image_prepare": (_INT, [_ptr_to(ImageDims), _ptr_to(ImageCamera), _P, _P, _P, _P, _P]),
+    "lsr_depth_loss_workspace_bytes": (_SZ, [_ptr_to(DepthLossDims)]),
+    "lsr_depth_loss_forward": (_INT, [_ptr_to(DepthLossDims)] + [_P] * 12),
+    "lsr_depth_loss_backward": (_INT, [_ptr_to(DepthLossDims)] + [_P] * 11),
 }
 EXPORTS = tuple(PROTOTYPES)
 

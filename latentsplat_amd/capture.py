@@ -45,6 +45,10 @@ class ColmapModel:
     xyz: np.ndarray                # (P, 3) float64
     rgb: np.ndarray                # (P, 3) uint8
     errors: np.ndarray             # (P,) float64
+    # the 2D observations that carry a point, read on request (read_colmap_model(observations=True)), else None
+    obs_offsets: Optional[np.ndarray] = None     # (I + 1,) int64: image k (file order) owns [obs_offsets[k], obs_offsets[k + 1])
+    obs_xy: Optional[np.ndarray] = None          # (M, 2) float64: COLMAP's measured position, in source pixels
+    obs_point_ids: Optional[np.ndarray] = None   # (M,) uint64: ids of points3D
 
 
 def _colmap_call(name: str, path, *args) -> None:
@@ -59,11 +63,13 @@ def _p(a: np.ndarray) -> C.c_void_p:
     return C.c_void_p(a.ctypes.data)
 
 
-def read_colmap_model(path) -> ColmapModel:
+def read_colmap_model(path, observations: bool = False) -> ColmapModel:
     """The sparse model in the directory ``path``: ``cameras / images / points3D`` as ``.bin`` (taken when ``cameras.bin``
-    is there) or ``.txt``.  Two phases, count and fill, both in the library; the 2D observations and the tracks are
-    skipped.  Models ``SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV``; anything malformed is refused with the
-    file, the record and the reason.  Host only."""
+    is there) or ``.txt``.  Two phases, count and fill, both in the library; the tracks are skipped, and so are the 2D
+    observations unless ``observations`` is set: then the model also carries, per image, the observations that have a 3D
+    point (``obs_offsets``, ``obs_xy``, ``obs_point_ids``), and one that names a point the model does not have is refused
+    with the image's name and the id.  Models ``SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV``; anything
+    malformed is refused with the file, the record and the reason.  Host only."""
     counts = _lib.ColmapCounts()
     _colmap_call("lsr_colmap_count", path, C.byref(counts))
     nc, ni, npts = counts.cameras, counts.images, counts.points
@@ -79,8 +85,22 @@ def read_colmap_model(path) -> ColmapModel:
     pt_ids, xyz = np.zeros(npts, np.uint64), np.zeros((npts, 3), np.float64)
     rgb, errors = np.zeros((npts, 3), np.uint8), np.zeros(npts, np.float64)
     _colmap_call("lsr_colmap_read_points", path, _p(pt_ids), _p(xyz), _p(rgb), _p(errors), npts)
-    return ColmapModel("binary" if counts.format == _lib.COLMAP_BINARY else "text", cam_ids, models, sizes, params, img_ids, q, t,
-                       img_cams, name_list, pt_ids, xyz, rgb, errors)
+    model = ColmapModel("binary" if counts.format == _lib.COLMAP_BINARY else "text", cam_ids, models, sizes, params, img_ids, q, t,
+                        img_cams, name_list, pt_ids, xyz, rgb, errors)
+    if observations:
+        total = C.c_int64(0)
+        _colmap_call("lsr_colmap_count_observations", path, C.byref(total))
+        m = total.value
+        obs_offsets, obs_xy, obs_ids = np.zeros(ni + 1, np.int64), np.zeros((m, 2), np.float64), np.zeros(m, np.uint64)
+        _colmap_call("lsr_colmap_read_observations", path, _p(obs_offsets), _p(obs_xy), _p(obs_ids), ni, m)
+        known = np.isin(obs_ids, pt_ids)
+        if not known.all():
+            at = int(np.flatnonzero(~known)[0])
+            image = int(np.searchsorted(obs_offsets, at, side="right")) - 1
+            raise _lib.LsrError(f"read_colmap_model({path}): image {name_list[image]!r} observes point {int(obs_ids[at])}, which the "
+                                f"model does not have")
+        model.obs_offsets, model.obs_xy, model.obs_point_ids = obs_offsets, obs_xy, obs_ids
+    return model
 
 
 # ---- host math ----
@@ -194,24 +214,26 @@ class Capture:
     @classmethod
     def load(cls, root, sparse: str = "sparse/0", images: str = "images", resolution: float = 1, device="cuda:0", *,
              near: Optional[float] = None, far: Optional[float] = None, background: Optional[Sequence[float]] = None,
-             batch: int = 8) -> "Capture":
+             batch: int = 8, observations: bool = False) -> "Capture":
         """``root / sparse`` holds the model, ``root / images`` the photographs under the model's image names.  With
         ``resolution = r`` the targets are ``round(Ws / r) x round(Hs / r)`` with focal lengths ``fx / r, fy / r``.
         ``near`` / ``far`` default to ``0.01`` / ``100`` times ``cameras_extent``.  ``background (3,)``: what RGBA
         photographs are composited over (default black).  The photographs go to the device as uint8, ``batch`` at a time
-        per camera, and only the float32 targets and coverage maps stay."""
+        per camera, and only the float32 targets and coverage maps stay.  ``observations``: read the model's 2D
+        observations too, which :meth:`sparse_depth` and :meth:`load_depth_priors` need."""
         self = object.__new__(cls)
         dev = torch.device(device)
         if dev.type != "cuda":
             raise _lib.LsrError("Capture.load needs a ROCm device (no CPU fallback for the image preparation)")
         if batch < 1:
             raise _lib.LsrError("batch must be positive")
-        model = read_colmap_model(os.path.join(str(root), sparse))
+        model = read_colmap_model(os.path.join(str(root), sparse), observations=observations)
         if len(model.names) == 0:
             raise _lib.LsrError(f"{root}: the model has no images")
         order = sorted(range(len(model.names)), key=lambda k: model.names[k])
         self.model, self.device, self.resolution = model, dev, resolution
         self.names = [model.names[k] for k in order]
+        self._rows = order                                        # image k of this capture is row _rows[k] of the model
         c2w = camera_to_world(model.qvec[order], model.tvec[order])
         centre, extent = cameras_extent(c2w[:, :3, 3])
         if not extent > 0.0:
@@ -219,7 +241,8 @@ class Capture:
         self.centre, self.cameras_extent = torch.from_numpy(centre.astype(np.float32)).to(dev), extent
         N = len(order)
         self.extrinsics = torch.from_numpy(c2w.astype(np.float32)).to(dev)
-        self.near = torch.full((N,), 0.01 * extent if near is None else float(near), dtype=torch.float32, device=dev)
+        self._near = 0.01 * extent if near is None else float(near)
+        self.near = torch.full((N,), self._near, dtype=torch.float32, device=dev)
         self.far = torch.full((N,), 100.0 * extent if far is None else float(far), dtype=torch.float32, device=dev)
         row_of = {int(cid): k for k, cid in enumerate(model.camera_ids)}
         cam_row = [row_of[int(model.image_camera_ids[k])] for k in order]
@@ -227,6 +250,13 @@ class Capture:
         self.source_cameras = [cams[r] for r in cam_row]
         intr = np.zeros((N, 3, 3), np.float32)
         self.sizes: List[Tuple[int, int]] = []
+        self._source_sizes = [tuple(int(v) for v in model.camera_sizes[r]) for r in cam_row]      # (Ws, Hs) per image
+        self._focal = [(cams[r].fx / resolution, cams[r].fy / resolution) for r in cam_row]       # of the target cameras, in pixels
+        # depth supervision (latentsplat_amd.depth_sup): built on request, per output size like the targets
+        self._sparse: Dict[Tuple[int, int], Tensor] = {}
+        self._sparse_built: set = set()
+        self._priors: Dict[Tuple[int, int], Tensor] = {}
+        self._prior_affine: Optional[Tensor] = None
         for k, r in enumerate(cam_row):
             Ws, Hs = (int(v) for v in model.camera_sizes[r])
             W, H = target_size(Ws, Hs, resolution)
@@ -315,6 +345,71 @@ class Capture:
     def coverage(self, idx: Sequence[int]) -> Tensor:
         """``(V, H, W)`` coverage of the images ``idx`` (1: the photograph covers the pixel, 0: it has nothing to say)."""
         return self._gather(self._coverage, idx)
+
+    def _sparse_map(self, k: int) -> np.ndarray:
+        from .depth_sup import sparse_inverse_depth
+        (H, W), (fx, fy) = self.sizes[k], self._focal[k]
+        return sparse_inverse_depth(self.model, self._rows[k], H, W, fx, fy, self._near)
+
+    def sparse_depth(self, idx: Sequence[int]) -> Tensor:
+        """``(V, H, W)`` float32: per image ``idx`` (one output size) the inverse depths of the sparse points it observes
+        (:func:`latentsplat_amd.depth_sup.sparse_inverse_depth` through the target camera, ``near`` as the cut), 0 where
+        there is none and where the coverage is 0.  Built on first use per image and kept.  Needs
+        ``Capture.load(..., observations=True)``."""
+        if self.model.obs_offsets is None:
+            raise _lib.LsrError("sparse_depth needs the model's observations: this capture was loaded without them "
+                                "(Capture.load(..., observations=True))")
+        idx = [int(k) for k in idx]
+        self._index(idx)
+        for k in idx:
+            if k not in self._sparse_built:
+                size, row = self._slot[k]
+                if size not in self._sparse:
+                    self._sparse[size] = torch.zeros_like(self._coverage[size])
+                m = torch.from_numpy(self._sparse_map(k)).to(self.device)
+                self._sparse[size][row] = m * (self._coverage[size][row] > 0)
+                self._sparse_built.add(k)
+        return self._gather(self._sparse, idx)
+
+    def load_depth_priors(self, folder) -> int:
+        """Read one monocular inverse-depth prior per image from ``folder``: a 16-bit file
+        (:func:`latentsplat_amd.depth_sup.load_depth_prior`) under the image's name, whole or without its extension, with
+        one of ``.npy .pgm .png .tif .tiff`` appended.  Each is resampled onto the image's target camera
+        (:func:`latentsplat_amd.depth_sup.prepare_depth_priors`; a prior of another size than the photograph is taken to
+        cover the same field of view) and aligned to the sparse points (``align_depth_prior``, then ``reliable_alignments``
+        over all images).  A missing file means that image has no prior: a zero map and the row ``(0, 0)``.  Returns the
+        number of priors read.  Needs ``Capture.load(..., observations=True)``."""
+        from .depth_sup import PRIOR_EXTENSIONS, align_depth_prior, load_depth_prior, prepare_depth_priors, reliable_alignments
+        if self.model.obs_offsets is None:
+            raise _lib.LsrError("load_depth_priors aligns the priors to the sparse points and needs the model's observations: "
+                                "this capture was loaded without them (Capture.load(..., observations=True))")
+        self._priors = {size: torch.zeros_like(c) for size, c in self._coverage.items()}
+        affine = np.zeros((len(self.names), 2), np.float64)
+        found = 0
+        for k, name in enumerate(self.names):
+            stems = [name, os.path.splitext(name)[0]]
+            path = next((p for p in (os.path.join(str(folder), s + e) for s in stems for e in PRIOR_EXTENSIONS) if os.path.isfile(p)), None)
+            if path is None:
+                continue
+            a = load_depth_prior(path)
+            (Ws, Hs), (H, W), (fx, fy), cam = self._source_sizes[k], self.sizes[k], self._focal[k], self.source_cameras[k]
+            sx, sy = a.shape[1] / Ws, a.shape[0] / Hs
+            scaled = SourceCamera(cam.model, cam.fx * sx, cam.fy * sy, cam.cx * sx, cam.cy * sy, cam.dist)
+            prior = prepare_depth_priors(a[None], scaled, H, W, fx, fy, self.device)[0]
+            size, row = self._slot[k]
+            self._priors[size][row] = prior
+            affine[k] = align_depth_prior(self.sparse_depth([k])[0], prior)
+            found += 1
+        self._prior_affine = torch.from_numpy(reliable_alignments(affine).astype(np.float32)).to(self.device)
+        return found
+
+    def depth_priors(self, idx: Sequence[int]) -> Tuple[Tensor, Tensor]:
+        """``(prior (V, H, W), affine (V, 2))`` of the images ``idx`` (one output size): the prepared priors and their
+        ``(scale, offset)`` rows, ``(0, 0)`` for an image without a usable prior: what
+        :func:`latentsplat_amd.depth_sup.inverse_depth_loss` takes as ``target`` and ``affine`` under ``align="given"``."""
+        if self._prior_affine is None:
+            raise _lib.LsrError("no depth priors have been loaded: Capture.load_depth_priors(folder)")
+        return self._gather(self._priors, idx), self._prior_affine[self._index(idx)]
 
     @property
     def points(self) -> Tuple[Tensor, Tensor]:

@@ -1,7 +1,9 @@
 // colmap_check.cpp — the COLMAP reader over a directory of models, as a stand-alone program for the host sanitizers
 // (`make colmap-check MODELS=dir`): every sub-directory of each argument (and the argument itself) that holds a
 // cameras.bin or cameras.txt is counted and, where the count succeeds, read into arrays of exactly the counted sizes, so
-// that a write past what phase one promised is a heap overflow the sanitizer sees.  Refusals are expected and printed;
+// that a write past what phase one promised is a heap overflow the sanitizer sees; the 2D observations likewise, through
+// lsr_colmap_count_observations / lsr_colmap_read_observations.  A model the first walk refuses is handed to the
+// observation walk all the same (it must refuse it too).  Refusals are expected and printed;
 // the exit status is 1 only when phase two contradicts phase one.
 #include <dirent.h>
 #include <stdio.h>
@@ -26,6 +28,11 @@ static int check(const std::string &dir, int *accepted) {
     int rc = lsr_colmap_count(dir.c_str(), &c);
     if (rc != LSR_OK) {
         printf("%s: refused (%d): %s\n", dir.c_str(), rc, lsr_colmap_last_error());
+        int64_t total = -1;
+        if (lsr_colmap_count_observations(dir.c_str(), &total) == LSR_OK) {
+            printf("%s: refused, but its observations were counted (%lld)\n", dir.c_str(), (long long)total);
+            return 1;
+        }
         return 0;
     }
     std::vector<uint32_t> cam_ids((size_t)c.cameras), img_ids((size_t)c.images), img_cams((size_t)c.images);
@@ -45,9 +52,30 @@ static int check(const std::string &dir, int *accepted) {
         printf("%s: counted, then refused (%d): %s\n", dir.c_str(), rc, lsr_colmap_last_error());
         return 1;
     }
+    // the observations: counted, read into arrays of exactly the counted sizes, and the offsets must end at the count
+    int64_t total = -1;
+    rc = lsr_colmap_count_observations(dir.c_str(), &total);
+    if (rc != LSR_OK) {
+        printf("%s: observations refused (%d): %s\n", dir.c_str(), rc, lsr_colmap_last_error());
+        return 0;
+    }
+    std::vector<int64_t> obs_offsets((size_t)c.images + 1);
+    std::vector<double> obs_xy((size_t)total * 2);
+    std::vector<uint64_t> obs_ids((size_t)total);
+    rc = lsr_colmap_read_observations(dir.c_str(), obs_offsets.data(), obs_xy.data(), obs_ids.data(), c.images, total);
+    if (rc != LSR_OK || obs_offsets[0] != 0 || obs_offsets[(size_t)c.images] != total) {
+        printf("%s: %lld observations counted, then refused or miscounted (%d): %s\n", dir.c_str(), (long long)total, rc,
+               lsr_colmap_last_error());
+        return 1;
+    }
+    if (total > 0 && lsr_colmap_read_observations(dir.c_str(), obs_offsets.data(), obs_xy.data(), obs_ids.data(), c.images,
+                                                  total - 1) == LSR_OK) {
+        printf("%s: a capacity of %lld observations was accepted for %lld\n", dir.c_str(), (long long)(total - 1), (long long)total);
+        return 1;
+    }
     ++*accepted;
-    printf("%s: %lld cameras, %lld images, %lld points (%s)\n", dir.c_str(), (long long)c.cameras, (long long)c.images,
-           (long long)c.points, c.format == LSR_COLMAP_BINARY ? "binary" : "text");
+    printf("%s: %lld cameras, %lld images, %lld points, %lld observations (%s)\n", dir.c_str(), (long long)c.cameras,
+           (long long)c.images, (long long)c.points, (long long)total, c.format == LSR_COLMAP_BINARY ? "binary" : "text");
     return 0;
 }
 

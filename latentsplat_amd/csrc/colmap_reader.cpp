@@ -129,6 +129,27 @@ void skip_line(File &f) {
     for (int c = f.byte(); c != EOF && c != '\n'; c = f.byte()) {}
 }
 
+// The next token of the current line into tok (kToken bytes).  1: a token; 0: the line (or the file) ended first, and the
+// line break is consumed; -1: an over-long token or a NUL byte.  After a token that the line break ended, *eol is set and
+// the next call must not be made for this line.
+int next_token(File &f, char *tok, bool *eol) {
+    int len = 0;
+    *eol = false;
+    for (;;) {
+        const int c = f.byte();
+        if (c == 0) return -1;
+        const bool blank = c == ' ' || c == '\t' || c == '\r';
+        if (c == EOF || c == '\n' || blank) {
+            if (c == EOF || c == '\n') *eol = true;
+            if (len > 0) { tok[len] = 0; return 1; }
+            if (*eol) return 0;
+            continue;
+        }
+        if (len == kToken - 1) return -1;
+        tok[len++] = (char)c;
+    }
+}
+
 bool parse_u64(const char *s, uint64_t *out) {
     if (!*s) return false;
     uint64_t v = 0;
@@ -263,12 +284,48 @@ struct ImageOut {
     int64_t capacity, name_capacity;
 };
 
+// offsets[image_capacity + 1], xy[capacity][2], point_ids[capacity]
+struct ObsOut { int64_t *offsets; double *xy; uint64_t *point_ids; int64_t image_capacity, capacity; };
+
 struct ImageWalk {
     const std::vector<uint32_t> *cameras;   // sorted
     const ImageOut *out;
     std::vector<uint32_t> ids;
     int64_t name_bytes = 0;
+    bool observations = false;              // parse the 2D observations instead of skipping them
+    const ObsOut *obs = nullptr;            // ... and store those that carry a point
+    int64_t obs_total = 0;                  // observations with a point so far
 };
+
+constexpr uint64_t kNoPoint = UINT64_MAX;   // images.bin: an observation without a 3D point (images.txt writes -1)
+
+// The observations of image record `at` begin: its offset.
+int begin_observations(ImageWalk *w, int64_t at) {
+    if (const ObsOut *o = w->obs) {
+        if (at >= o->image_capacity) return fail(LSR_EINVAL, "more images than the capacity %lld", (long long)o->image_capacity);
+        o->offsets[at] = w->obs_total;
+        o->offsets[at + 1] = w->obs_total;
+    }
+    return LSR_OK;
+}
+
+// Observation `k` of image record `at`; has_point: it carries the 3D point `point`.
+int take_observation(const char *file, ImageWalk *w, int64_t at, int64_t k, double x, double y, bool has_point, uint64_t point) {
+    if (!std::isfinite(x) || !std::isfinite(y))
+        return fail(LSR_EINVAL, "%s: observation %lld of image record %lld has a non-finite position", file, (long long)k, (long long)at);
+    if (!has_point) return LSR_OK;
+    if (const ObsOut *o = w->obs) {
+        if (w->obs_total >= o->capacity)
+            return fail(LSR_EINVAL, "%s: more observations with a point than the capacity %lld (image record %lld)", file,
+                        (long long)o->capacity, (long long)at);
+        o->xy[2 * w->obs_total] = x;
+        o->xy[2 * w->obs_total + 1] = y;
+        o->point_ids[w->obs_total] = point;
+        o->offsets[at + 1] = w->obs_total + 1;
+    }
+    ++w->obs_total;
+    return LSR_OK;
+}
 
 // name: NUL-terminated, len bytes without the terminator
 int take_image(const char *file, ImageWalk *w, uint32_t id, const double *q, const double *t, uint32_t camera, const char *name, int len) {
@@ -323,7 +380,23 @@ int images_bin(const std::string &dir, ImageWalk *w) {
             name[len++] = (char)c;
         }
         name[len] = 0;
-        if (!f.value(&m) || !f.skip(m, 24)) return fail(LSR_EINVAL, "%s: truncated in the observations of image record %lld", file, (long long)at);
+        if (!f.value(&m)) return fail(LSR_EINVAL, "%s: truncated in the observations of image record %lld", file, (long long)at);
+        if (!w->observations) {
+            if (!f.skip(m, 24)) return fail(LSR_EINVAL, "%s: truncated in the observations of image record %lld", file, (long long)at);
+        } else {
+            // the count against what is left of the file before the loop is sized by it
+            if (m > (uint64_t)(f.left() / 24))
+                return fail(LSR_EINVAL, "%s: truncated in the observations of image record %lld", file, (long long)at);
+            int rc = begin_observations(w, at);
+            for (int64_t k = 0; rc == LSR_OK && k < (int64_t)m; ++k) {
+                double xy[2];
+                uint64_t point;
+                if (!f.get(xy, sizeof(xy)) || !f.value(&point))
+                    return fail(LSR_EINVAL, "%s: truncated in the observations of image record %lld", file, (long long)at);
+                rc = take_observation(file, w, at, k, xy[0], xy[1], point != kNoPoint, point);
+            }
+            if (rc != LSR_OK) return rc;
+        }
         const int rc = take_image(file, w, id, q, t, camera, name, len);
         if (rc != LSR_OK) return rc;
     }
@@ -350,9 +423,37 @@ int images_txt(const std::string &dir, ImageWalk *w) {
         if (nt != 10 || !parse_u32(tok[0], &id) || !parse_u32(tok[8], &camera)) return fail(LSR_EINVAL, "%s: malformed image record %lld", file, at);
         for (int k = 0; k < 7; ++k)
             if (!parse_f64(tok[1 + k], &qt[k])) return fail(LSR_EINVAL, "%s: malformed image record %lld", file, at);
-        const int rc = take_image(file, w, id, qt, qt + 4, camera, tok[9], (int)strlen(tok[9]));
+        int rc = take_image(file, w, id, qt, qt + 4, camera, tok[9], (int)strlen(tok[9]));
         if (rc != LSR_OK) return rc;
-        if (!eof) skip_line(f);               // the 2D observations: possibly empty, never parsed
+        if (!w->observations) {
+            if (!eof) skip_line(f);           // the 2D observations: possibly empty, not parsed by this walk
+            continue;
+        }
+        rc = begin_observations(w, at);
+        if (rc != LSR_OK) return rc;
+        // the next line, whatever it holds, is this image's: X Y POINT3D_ID triples, -1 for an observation without a point
+        bool eol = eof;
+        for (int64_t k = 0; !eol; ++k) {
+            double xy[2] = {0.0, 0.0};
+            uint64_t point = 0;
+            bool has_point = true;
+            int field = 0;
+            for (; field < 3 && !eol; ++field) {
+                const int got = next_token(f, tok[0], &eol);
+                if (got < 0) return fail(LSR_EINVAL, "%s: an over-long token or a NUL byte", file);
+                if (got == 0) break;
+                bool ok;
+                if (field < 2) ok = parse_f64(tok[0], &xy[field]);
+                else if (!strcmp(tok[0], "-1")) { has_point = false; ok = true; }
+                else ok = parse_u64(tok[0], &point);
+                if (!ok) return fail(LSR_EINVAL, "%s: malformed observation %lld of image record %lld", file, (long long)k, at);
+            }
+            if (field == 0) break;            // the line ended after a whole triple (or held none)
+            if (field != 3) return fail(LSR_EINVAL, "%s: observation %lld of image record %lld is incomplete", file, (long long)k, at);
+            rc = take_observation(file, w, at, k, xy[0], xy[1], has_point, point);
+            if (rc != LSR_OK) return rc;
+        }
+        if (f.left() == 0) eof = true;
     }
     if (has_duplicates(w->ids)) return fail(LSR_EINVAL, "%s: an image id is given twice", file);
     return LSR_OK;
@@ -441,7 +542,8 @@ int read_cameras(const std::string &dir, int format, const CameraOut *out, std::
     return format == LSR_COLMAP_BINARY ? cameras_bin(dir, out, ids) : cameras_txt(dir, out, ids);
 }
 
-int read_images(const std::string &dir, int format, const ImageOut *out, int64_t *count, int64_t *name_bytes) {
+int read_images(const std::string &dir, int format, const ImageOut *out, int64_t *count, int64_t *name_bytes,
+                bool observations = false, const ObsOut *obs = nullptr, int64_t *obs_total = nullptr) {
     std::vector<uint32_t> cameras;
     int rc = read_cameras(dir, format, nullptr, &cameras);
     if (rc != LSR_OK) return rc;
@@ -449,10 +551,13 @@ int read_images(const std::string &dir, int format, const ImageOut *out, int64_t
     ImageWalk w;
     w.cameras = &cameras;
     w.out = out;
+    w.observations = observations;
+    w.obs = obs;
     rc = format == LSR_COLMAP_BINARY ? images_bin(dir, &w) : images_txt(dir, &w);
     if (rc != LSR_OK) return rc;
     *count = (int64_t)w.ids.size();
     *name_bytes = w.name_bytes;
+    if (obs_total) *obs_total = w.obs_total;
     return LSR_OK;
 }
 
@@ -460,6 +565,18 @@ int read_points(const std::string &dir, int format, const PointOut *out, int64_t
     std::vector<uint64_t> ids;
     const int rc = format == LSR_COLMAP_BINARY ? points_bin(dir, out, &ids) : points_txt(dir, out, &ids);
     if (rc == LSR_OK) *count = (int64_t)ids.size();
+    return rc;
+}
+
+// All three files walked and checked as lsr_colmap_count walks them, the observations parsed (and stored, with `obs`).
+int walk_observations(const char *dir, const ObsOut *obs, int64_t *total) {
+    int format = 0;
+    int64_t images = 0, name_bytes = 0, points = 0;
+    int rc = find_format(dir, &format);
+    if (rc == LSR_OK) rc = read_images(dir, format, nullptr, &images, &name_bytes, true, obs, total);
+    if (rc == LSR_OK) rc = read_points(dir, format, nullptr, &points);
+    if (rc == LSR_OK && obs && images < obs->image_capacity)          // (fewer images than the caller sized for: the tail)
+        for (int64_t k = images + 1; k <= obs->image_capacity; ++k) obs->offsets[k] = *total;
     return rc;
 }
 
@@ -516,6 +633,25 @@ int lsr_colmap_read_points(const char *dir, uint64_t *ids, double *xyz, uint8_t 
     int64_t count = 0;
     const int rc = find_format(dir, &format);
     return rc != LSR_OK ? rc : read_points(dir, format, &out, &count);
+}
+
+int lsr_colmap_count_observations(const char *dir, int64_t *total) {
+    g_detail[0] = 0;
+    if (!dir || !total) return fail(LSR_ENULL, "a NULL argument");
+    int64_t n = 0;
+    const int rc = walk_observations(dir, nullptr, &n);
+    if (rc == LSR_OK) *total = n;
+    return rc;
+}
+
+int lsr_colmap_read_observations(const char *dir, int64_t *offsets, double *xy, uint64_t *point_ids, int64_t image_capacity,
+                                 int64_t capacity) {
+    g_detail[0] = 0;
+    if (!dir || !offsets || (capacity > 0 && (!xy || !point_ids))) return fail(LSR_ENULL, "a NULL argument");
+    const ObsOut out = {offsets, xy, point_ids, image_capacity < 0 ? 0 : image_capacity, capacity < 0 ? 0 : capacity};
+    offsets[0] = 0;
+    int64_t n = 0;
+    return walk_observations(dir, &out, &n);
 }
 
 }  // extern "C"

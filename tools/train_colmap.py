@@ -20,14 +20,25 @@
      and every `--filter-3d-interval` steps (per output size, the smallest filter wins);
   7. `point_cloud.ply` and `metrics.json` in `--out`: `loss_first`, `loss_last`, `gaussians`, `ms_per_step` (after a
      warm-up), and on the held-out views `psnr` and `ssim` (`compute_ssim`) over the covered pixels: the render and the target
-     multiplied by the coverage, the squared error averaged over the covered values only.
+     multiplied by the coverage, the squared error averaged over the covered values only;
+  8. depth supervision, both off by default and both `inverse_depth_loss` on the depth and mask the
+     render already returns.  `--depth-sparse W`: the L1 on inverse depth at the pixels the model's own sparse points project
+     to (`capture.sparse_depth`), a mean over those points, times W times `cameras_extent` (gsplat's `depth_loss`; its
+     customary W is 1e-2).  `--depth-priors DIR`: one 16-bit monocular inverse-depth prior per image under the image's name
+     in DIR, brought to the scene's scale by the per-image scale and offset from the sparse points (`--depth-align given`,
+     the published rule) or by a least-squares fit against the render every step (`--depth-align fit`), a mean over the
+     pixels weighted by the coverage, times a weight on the `expon_lr` schedule from `--depth-prior-weight` to
+     `--depth-prior-weight-final` over the run.  `metrics.json` then also holds `depth_loss_first` / `depth_loss_last`: the
+     weighted depth terms of the first and the last step.
 
 usage: python tools/train_colmap.py ROOT --out DIR [--sparse sparse/0] [--images images] [--resolution 1] [--hold 8] [--steps 30000]
                                     [--batch 1] [--seed 0] [--lambda-dssim 0.2] [--sh-degree 3] [--sh-degree-interval 1000]
                                     [--strategy adc|mcmc] [--densify-interval 100] [--densify-from 500] [--densify-until 15000]
                                     [--densify-grad-threshold 2e-4/BATCH] [--min-opacity 0.005] [--opacity-reset-interval 3000]
                                     [--cap-max N] [--noise-lr 5e5] [--opacity-reg 0.01] [--scale-reg 0.01]
-                                    [--antialiasing] [--filter-3d] [--filter-3d-interval 100]"""
+                                    [--antialiasing] [--filter-3d] [--filter-3d-interval 100]
+                                    [--depth-sparse 0] [--depth-priors DIR] [--depth-prior-weight 1.0]
+                                    [--depth-prior-weight-final 0.01] [--depth-align given|fit]"""
 from __future__ import annotations
 
 import argparse
@@ -93,18 +104,31 @@ def main(argv=None) -> dict:
     ap.add_argument("--antialiasing", action="store_true")
     ap.add_argument("--filter-3d", action="store_true")
     ap.add_argument("--filter-3d-interval", type=int, default=100)
+    ap.add_argument("--depth-sparse", type=float, default=0.0, help="weight of the sparse-point inverse-depth loss, times cameras_extent (0: off; customary 1e-2)")
+    ap.add_argument("--depth-priors", default=None, help="a directory of 16-bit monocular inverse-depth priors, one per image name (default: off)")
+    ap.add_argument("--depth-prior-weight", type=float, default=1.0)
+    ap.add_argument("--depth-prior-weight-final", type=float, default=0.01, help="reached at --steps")
+    ap.add_argument("--depth-align", choices=("given", "fit"), default="given", help="priors: the per-image scale / offset from the sparse points, or a fit per step")
     a = ap.parse_args(argv)
     if a.steps < 1 or a.batch < 1 or a.hold < 0 or a.densify_interval < 0 or a.sh_degree_interval < 0 or a.filter_3d_interval < 1:
         sys.exit("--steps, --batch and --filter-3d-interval must be positive; --hold and the intervals must not be negative")
     if not 0.0 <= a.lambda_dssim <= 1.0 or not 0 <= a.sh_degree <= 4 or not a.resolution > 0:
         sys.exit("--lambda-dssim must be in [0, 1], --sh-degree in 0..4, --resolution positive")
+    if a.depth_sparse < 0 or not a.depth_prior_weight > 0 or not a.depth_prior_weight_final > 0:
+        sys.exit("--depth-sparse must not be negative; the two prior weights must be positive")
     if not torch.cuda.is_available():
         sys.exit("train_colmap needs an MI355X: no ROCm device is visible (there is no CPU fallback)")
     from latentsplat_amd.capture import Capture
     from latentsplat_amd.losses import compute_ssim, photometric_loss
     from latentsplat_amd.optim import SceneAdam, expon_lr
     dev = torch.device("cuda:0")
-    capture = Capture.load(a.root, a.sparse, a.images, a.resolution, dev)
+    depth_on = a.depth_sparse > 0 or a.depth_priors is not None
+    capture = Capture.load(a.root, a.sparse, a.images, a.resolution, dev, observations=depth_on)
+    if depth_on:
+        from latentsplat_amd.depth_sup import inverse_depth_loss
+    priors_found = capture.load_depth_priors(a.depth_priors) if a.depth_priors is not None else 0
+    if a.depth_priors is not None and priors_found == 0:
+        sys.exit(f"--depth-priors {a.depth_priors}: no prior was found for any of the {len(capture)} images")
     train, test = capture.split(a.hold)
     if not train:
         sys.exit(f"--hold {a.hold} leaves no training image among {len(capture)}")
@@ -138,7 +162,7 @@ def main(argv=None) -> dict:
 
     refresh_filter()
     warm = min(WARMUP_STEPS, a.steps // 2)
-    losses, queue, t0 = [], [], None
+    losses, depth_losses, queue, t0 = [], [], [], None
     for step in range(a.steps):
         if step == warm:
             torch.cuda.synchronize(dev)
@@ -152,8 +176,20 @@ def main(argv=None) -> dict:
         collect = control is not None and step < a.densify_until
         means2D = torch.zeros((len(idx), scene.num_gaussians, 3), device=dev, requires_grad=True) if collect else None
         kw = dict(means2D=means2D) if collect else {}
-        render, _, _, _, radii = scene.render(views, H, W, filter_3d=filter_3d, antialiasing=a.antialiasing, **kw)
+        render, _, mask, depth, radii = scene.render(views, H, W, filter_3d=filter_3d, antialiasing=a.antialiasing, **kw)
         loss = photometric_loss(render * cover, target * cover, a.lambda_dssim)
+        if depth_on:
+            depth_term = 0.0
+            if a.depth_sparse > 0:
+                depth_term = a.depth_sparse * extent * inverse_depth_loss(depth, mask, views, capture.sparse_depth(idx), normalize="weights")
+            if a.depth_priors is not None:
+                prior, affine = capture.depth_priors(idx)
+                weight = expon_lr(step, a.depth_prior_weight, a.depth_prior_weight_final, a.steps)
+                depth_term = depth_term + weight * inverse_depth_loss(depth, mask, views, prior, cover[:, 0].contiguous(),
+                                                                      affine if a.depth_align == "given" else None,
+                                                                      align=a.depth_align, normalize="pixels")
+            loss = loss + depth_term
+            depth_losses.append(depth_term.detach())
         if mcmc is not None:
             loss = loss + mcmc.regularizer(a.opacity_reg, a.scale_reg)
         loss.backward()
@@ -189,6 +225,9 @@ def main(argv=None) -> dict:
                resolution=a.resolution, hold=a.hold, batch=a.batch, seed=a.seed, cameras_extent=extent, lambda_dssim=a.lambda_dssim,
                strategy=a.strategy, density_events=events, sh_degree=a.sh_degree, active_sh_degree_last=scene.active_sh_degree,
                antialiasing=bool(a.antialiasing), filter_3d=bool(a.filter_3d), format=capture.model.format)
+    if depth_on:
+        res.update(depth_loss_first=float(depth_losses[0]), depth_loss_last=float(depth_losses[-1]), depth_sparse=a.depth_sparse,
+                   depth_priors=priors_found, depth_align=a.depth_align)
     if test:
         psnr, ssim, names = [], [], []
         with torch.no_grad():
