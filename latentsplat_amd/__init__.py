@@ -17,7 +17,8 @@ ground-truth cloud: accuracy, completeness, Chamfer, precision / recall / F-scor
 resampled onto the rasterizer's centred, distortion-free camera at the training resolution, with a coverage map, in HIP),
 ``capture`` (a photographed capture: the COLMAP sparse model through a strict host reader, prepared targets, a train / test
 split, camera tables and the initial scene), ``depth_sup`` (depth supervision for captures: sparse-point and monocular-prior
-inverse-depth targets, and the fused inverse-depth L1 loss in HIP) and ``synthetic`` (seeded scenes for tests / bench).
+inverse-depth targets, and the fused inverse-depth L1 loss in HIP), ``distortion`` (the depth distortion regulariser: pivoted
+depth moments of the Gaussians per view and the fused image-space pair term A M2 - M1^2, in HIP) and ``synthetic`` (seeded scenes for tests / bench).
 """
 __version__ = "0.1.0"
 
@@ -47,6 +48,8 @@ _LAZY = {"rotate_sh": "sh_rotate", "GaussianAdapter": "gaussian_adapter", "Gauss
          "prepare_images": "images", "SourceCamera": "images",
          "inverse_depth_loss": "depth_sup", "sparse_inverse_depth": "depth_sup", "align_depth_prior": "depth_sup",
          "load_depth_prior": "depth_sup", "prepare_depth_priors": "depth_sup",
+         "gaussian_depth_moments": "distortion", "distortion_loss": "distortion", "distortion_map": "distortion",
+         "depth_pivot": "distortion",
          "Capture": "capture", "read_colmap_model": "capture", "ColmapModel": "capture",
          "adam_step": "optim", "SceneAdam": "optim", "expon_lr": "optim", "visible_from_radii": "optim"}
 

@@ -1,5 +1,5 @@
 """ctypes binding of ``liblsr_hip.so`` (C ABI: include/lsr_rasterizer.h, include/lsr_adapter.h, include/lsr_latent.h, include/lsr_ply.h,
-include/lsr_sh_rotate.h, include/lsr_depth_head.h, include/lsr_scene.h, include/lsr_loss.h, include/lsr_density.h, include/lsr_optim.h, include/lsr_knn.h, include/lsr_mcmc.h, include/lsr_filter3d.h, include/lsr_bilagrid.h, include/lsr_transform.h, include/lsr_vq.h, include/lsr_pose.h, include/lsr_normals.h, include/lsr_mesh.h, include/lsr_nn.h, include/lsr_colmap.h, include/lsr_image.h, include/lsr_depth_loss.h).
+include/lsr_sh_rotate.h, include/lsr_depth_head.h, include/lsr_scene.h, include/lsr_loss.h, include/lsr_density.h, include/lsr_optim.h, include/lsr_knn.h, include/lsr_mcmc.h, include/lsr_filter3d.h, include/lsr_bilagrid.h, include/lsr_transform.h, include/lsr_vq.h, include/lsr_pose.h, include/lsr_normals.h, include/lsr_mesh.h, include/lsr_nn.h, include/lsr_colmap.h, include/lsr_image.h, include/lsr_depth_loss.h, include/lsr_distortion.h).
 
 The library is built in-tree by ``latentsplat_amd/csrc/Makefile`` (``__graft_entry__.build()``).
 There is no CPU fallback: if the shared object is missing or not loadable this module raises, and
@@ -321,6 +321,16 @@ DEPTH_NORM_PIXELS, DEPTH_NORM_WEIGHTS = 0, 1                        # LSR_DEPTH_
 DEPTH_LOSS_CHUNK = 2048                                             # LSR_DEPTH_LOSS_CHUNK: pixels of a view per workgroup
 
 
+class DistortionDims(C.Structure):   # lsr_distortion_dims (include/lsr_distortion.h)
+    _fields_ = [("num_images", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("reserved0", C.c_int32),
+                ("reserved1", C.c_int32), ("reserved2", C.c_int32)]
+
+
+DIST_LINEAR, DIST_NDC, DIST_DISPARITY = 0, 1, 2                     # LSR_DIST_*
+DIST_MAX_ROWS, DIST_MAX_VIEWS = 1 << 28, 65536                      # LSR_DIST_MAX_*
+DIST_THREADS, DIST_MAX_BLOCKS, DIST_CHUNK = 256, 2048, 2048         # LSR_DIST_THREADS / _MAX_BLOCKS / _CHUNK
+
+
 def transform_record_floats(degree: int) -> int:
     """LSR_TRANSFORM_RECORD_FLOATS: the 20-float header and the band blocks 1..degree (20, 29, 54, 103, 184)."""
     return TRANSFORM_HEADER_FLOATS + sh_rotate_table_floats(degree) - 1
@@ -453,6 +463,12 @@ PROTOTYPES = {
     "lsr_depth_loss_workspace_bytes": (_SZ, [_ptr_to(DepthLossDims)]),
     "lsr_depth_loss_forward": (_INT, [_ptr_to(DepthLossDims)] + [_P] * 12),
     "lsr_depth_loss_backward": (_INT, [_ptr_to(DepthLossDims)] + [_P] * 11),
+    "lsr_scene_depth_moments_workspace_bytes": (_SZ, [_I64, _I32]),
+    "lsr_scene_depth_moments_forward": (_INT, [_I64, _P, _I32, _P, _P, _I32, _P, _P, _P]),
+    "lsr_scene_depth_moments_backward": (_INT, [_I64, _P, _I32, _P, _P, _I32, _P, _P, _P, _P]),
+    "lsr_distortion_loss_workspace_bytes": (_SZ, [_ptr_to(DistortionDims)]),
+    "lsr_distortion_loss_forward": (_INT, [_ptr_to(DistortionDims)] + [_P] * 8),
+    "lsr_distortion_loss_backward": (_INT, [_ptr_to(DistortionDims)] + [_P] * 7),
 }
 EXPORTS = tuple(PROTOTYPES)
 

@@ -475,6 +475,75 @@ class GaussianScene(nn.Module):
         normals = gaussian_normals(views, xyz, scaling, rotation)
         return rasterize_views(views, height, width, self.active_sh_degree, xyz, cov, opacities, shs=shs, features=normals, **kw)
 
+    def _surface_inputs(self, who: str, scale_modifier, filter_3d, transforms, transform_idx, check_transforms, poses,
+                        antialiasing, kw):
+        """What :meth:`render_with_distortion` and :meth:`render_surface` share: the refusal of a caller's payload and the
+        (posed) raw parameters with their activation, ``(xyz, scaling, rotation, shs, opacities, cov)``."""
+        if kw.get("features") is not None or kw.get("feature_sh") is not None:
+            raise _lib.LsrError(f"{who}: the features payload is taken; features / feature_sh of the caller's own are refused "
+                                "(render them with render)")
+        kw.pop("features", None)
+        kw.pop("feature_sh", None)
+        if antialiasing:
+            kw["antialiasing"] = True
+        if transforms is not None or poses is not None:
+            xyz, rest, scaling, rotation = self._posed_parameters(transforms, transform_idx, filter_3d, check_transforms, poses)
+            shs, opacities, cov, _, _ = _ActivateScene.apply(self._features_dc, rest, self._opacity, scaling, rotation,
+                                                             float(scale_modifier), False)
+        else:
+            xyz, scaling, rotation = self._xyz, self._scaling, self._rotation
+            shs, opacities, cov, _, _ = self._activate(scale_modifier, False, filter_3d)
+        return xyz, scaling, rotation, shs, opacities, cov
+
+    def render_with_distortion(self, views: Tensor, height: int, width: int, space: str = "ndc", pivot: Optional[Tensor] = None,
+                               scale_modifier: float = 1.0, filter_3d: Optional[Tensor] = None,
+                               transforms: Optional[Tensor] = None, transform_idx: Optional[Tensor] = None,
+                               check_transforms: bool = True, poses=None, antialiasing: bool = False,
+                               check_near_far: bool = True, **kw):
+        """:meth:`render` with the depth moments of the Gaussians
+        (:func:`latentsplat_amd.distortion.gaussian_depth_moments`: ``(m', m'^2)``, ``m' = m - pivot``, ``m`` the depth in
+        ``space``) as the ``features`` payload: ``(color, moment_map, mask, depth, radii)``.  ``moment_map (V, 2, H, W)`` is
+        the blended ``(M1, M2)``, which with ``mask`` is what :func:`latentsplat_amd.distortion.distortion_loss` takes.
+        Every other keyword is :meth:`render`'s.
+
+        With ``transforms`` / ``poses`` the moments are those of the POSED positions.  The payload is taken, so a caller's
+        own ``features`` / ``feature_sh`` is refused.  Colour and moments are five payload channels: with ``means2D_abs``
+        the rasterizer's refusal of more than 4 payload channels applies unchanged.  Any depth mode may be in the view
+        table: nothing here reads ``depth``.  ``space="ndc"`` reads near / far from slots 42 / 43
+        (:func:`latentsplat_amd.distortion.with_near_far` for a NATIVE table) and checks them with one host read per call
+        unless ``check_near_far=False``.  The moments hand their gradient to the positions alone: a ``views`` that requires
+        grad is refused (the moments have no pose gradient, and a partial one would be silent)."""
+        from .distortion import gaussian_depth_moments
+        from .rasterizer import rasterize_views
+        xyz, _, _, shs, opacities, cov = self._surface_inputs("render_with_distortion", scale_modifier, filter_3d, transforms,
+                                                              transform_idx, check_transforms, poses, antialiasing, kw)
+        moments = gaussian_depth_moments(views, xyz, space, pivot, check_near_far)
+        return rasterize_views(views, height, width, self.active_sh_degree, xyz, cov, opacities, shs=shs, features=moments, **kw)
+
+    def render_surface(self, views: Tensor, height: int, width: int, space: str = "ndc", pivot: Optional[Tensor] = None,
+                       scale_modifier: float = 1.0, filter_3d: Optional[Tensor] = None, transforms: Optional[Tensor] = None,
+                       transform_idx: Optional[Tensor] = None, check_transforms: bool = True, poses=None,
+                       antialiasing: bool = False, check_near_far: bool = True, **kw):
+        """Both geometric regularisers from one render: ``(color, normal_map, moment_map, mask, depth, radii)``, the
+        ``normal_map (V, 3, H, W)`` of :meth:`render_with_normals` and the ``moment_map (V, 2, H, W)`` of
+        :meth:`render_with_distortion`.  The payload is normals and moments: five feature channels, eight with colour, which
+        is still inside the compositing kernels' 8-channel instances.  The two operator outputs are joined by one
+        ``torch.cat`` (a copy of 20 bytes per (view, Gaussian) each way; tools/bench_distortion.py times it).  The view table
+        must carry depth mode NATIVE, as for :meth:`render_with_normals`; ``means2D_abs`` is refused by the rasterizer, as
+        there."""
+        from .distortion import gaussian_depth_moments
+        from .normals import gaussian_normals
+        from .rasterizer import rasterize_views
+        xyz, scaling, rotation, shs, opacities, cov = self._surface_inputs("render_surface", scale_modifier, filter_3d,
+                                                                           transforms, transform_idx, check_transforms, poses,
+                                                                           antialiasing, kw)
+        normals = gaussian_normals(views, xyz, scaling, rotation)
+        moments = gaussian_depth_moments(views, xyz, space, pivot, check_near_far)
+        payload = torch.cat((normals, moments), dim=-1)
+        color, feature, mask, depth, radii = rasterize_views(views, height, width, self.active_sh_degree, xyz, cov, opacities,
+                                                             shs=shs, features=payload, **kw)
+        return color, feature[:, :3], feature[:, 3:], mask, depth, radii
+
     @torch.no_grad()
     def extract_mesh(self, views: Tensor, height: int, width: int, voxel_size: float, bounds=None, trunc: Optional[float] = None,
                      batch: int = 8, min_weight: float = 1.0, **render_kw):

@@ -81,6 +81,12 @@ that disagree, for the grids to absorb.  `fit.json` then holds `bilateral_grid`,
 normals with the normals of the rendered depth at the pixels covered more than `--normal-alpha-min` (default 0.5: a default,
 not a measurement).  `--flatten-reg W` adds W times `flatten_loss`, the mean shortest extent.  Together with `--absgrad` the
 normal term is refused (six payload channels).  `fit.json` then holds the four values and `normal_loss_first / _last`.
+`--dist-reg W` with W > 0 adds W times the depth distortion loss: from step `--dist-reg-from` (default 0)
+on, every step renders with `GaussianScene.render_with_distortion` (with `--normal-reg`: `render_surface`, both payloads in one
+render) and `distortion_loss` takes the blended depth moments and the mask.  The depths are measured in `--dist-space`
+(default ndc, the mapping of 2DGS, with the cameras' near / far) about `depth_pivot` at the mean of the scene's positions
+at the start.  Together with `--absgrad` it is refused (five payload channels).  `fit.json` then holds `dist_reg`,
+`dist_reg_from`, `dist_space` and `dist_loss_first / _last`.
 Without the two weights the run is the one it was.
 
 usage: python tools/fit_ply.py scene.ply --out DIR [--views 8] [--size 256] [--steps 200] [--noise 1.0] [--seed 0] [--distance 2.5]
@@ -91,7 +97,8 @@ usage: python tools/fit_ply.py scene.ply --out DIR [--views 8] [--size 256] [--s
                                [--strategy adc|mcmc] [--cap-max N] [--noise-lr 5e5] [--opacity-reg 0.01] [--scale-reg 0.01]
                                [--filter-3d] [--filter-3d-interval 100] [--antialiasing] [--absgrad]
                                [--bilateral-grid X Y L] [--bilateral-grid-lr 2e-3] [--tv-weight 10] [--target-jitter 0]
-                               [--normal-reg 0] [--normal-reg-from 0] [--normal-alpha-min 0.5] [--flatten-reg 0]"""
+                               [--normal-reg 0] [--normal-reg-from 0] [--normal-alpha-min 0.5] [--flatten-reg 0]
+                               [--dist-reg 0] [--dist-reg-from 0] [--dist-space ndc|linear|disparity]"""
 from __future__ import annotations
 
 import argparse
@@ -177,6 +184,12 @@ def main(argv=None) -> dict:
     ap.add_argument("--normal-alpha-min", type=float, default=0.5,
                     help="pixels the scene covers less than this take no part in the normal loss (a default, not a measurement)")
     ap.add_argument("--flatten-reg", type=float, default=0.0, help="weight of mean(min_k exp(scaling)) in the loss (0: off, the default)")
+    ap.add_argument("--dist-reg", type=float, default=0.0,
+                    help="weight of the depth distortion loss (0: off, the default): every step renders the depth moments of "
+                         "the Gaussians next to the colour")
+    ap.add_argument("--dist-reg-from", type=int, default=0, help="no distortion loss before this step")
+    ap.add_argument("--dist-space", choices=("ndc", "linear", "disparity"), default="ndc",
+                    help="what the distortion term measures depth in (ndc: the mapping of 2DGS)")
     ap.add_argument("--target-jitter", type=float, default=0.0,
                     help="S > 0: a seeded per-channel affine on every target view, gain in [1 - S, 1 + S], offset in [-S / 4, S / 4] (default 0: none)")
     a = ap.parse_args(argv)
@@ -186,6 +199,10 @@ def main(argv=None) -> dict:
         sys.exit("--normal-reg and --flatten-reg must not be negative and --normal-alpha-min must be positive")
     if a.normal_reg > 0.0 and a.absgrad:
         sys.exit("--normal-reg with --absgrad: colour and normals are six payload channels, the absolute gradient takes at most four")
+    if a.dist_reg < 0.0:
+        sys.exit("--dist-reg must not be negative")
+    if a.dist_reg > 0.0 and a.absgrad:
+        sys.exit("--dist-reg with --absgrad: colour and depth moments are five payload channels, the absolute gradient takes at most four")
     if not 0.0 <= a.lambda_dssim <= 1.0:
         sys.exit("--lambda-dssim must be in [0, 1]")
     if not 0.0 <= a.drop < 1.0 or a.densify_interval < 0 or a.opacity_reset_interval < 0 or a.sh_degree_interval < 0:
@@ -215,6 +232,10 @@ def main(argv=None) -> dict:
         ext, intr, near, far = circle_cameras(centre, extent, a.views, a.distance)
         views = build_view_table(ext, intr, near, far, torch.zeros(3, device=dev))
         target = scene.render(views, a.size, a.size, antialiasing=a.antialiasing)[0]
+        if a.dist_reg > 0.0:            # near / far where space="ndc" reads them (the NATIVE render does not), and the pivot
+            from latentsplat_amd.distortion import depth_pivot, distortion_loss, with_near_far
+            dist_views = with_near_far(views, near, far)
+            dist_pivot = depth_pivot(dist_views, scene._xyz.mean(dim=0), a.dist_space)
         if a.target_jitter > 0.0:       # a generator of its own: the perturbation below draws what it always drew
             gen_jitter = torch.Generator().manual_seed(a.seed + 0x5eed)
             gain = 1.0 + a.target_jitter * (2.0 * torch.rand(a.views, 3, generator=gen_jitter) - 1.0)
@@ -273,7 +294,7 @@ def main(argv=None) -> dict:
 
     refresh_filter(0, "start")
     warm = min(WARMUP_STEPS, a.steps // 2)
-    losses, normal_losses = [], []
+    losses, normal_losses, dist_losses = [], [], []
     t0 = None
     for step in range(a.steps):
         if step == warm:
@@ -282,6 +303,17 @@ def main(argv=None) -> dict:
         opt.zero_grad(set_to_none=True)
         with_normals = a.normal_reg > 0.0 and step >= a.normal_reg_from
         render_scene = scene.render_with_normals if with_normals else scene.render      # (without --normal-reg: the call it was)
+        with_dist = a.dist_reg > 0.0 and step >= a.dist_reg_from
+        if with_dist:                   # (--absgrad is refused above: no means2D_abs reaches these)
+            dist_kw = dict(space=a.dist_space, pivot=dist_pivot, check_near_far=False)
+            if with_normals:
+                def render_scene(v, h, w, **kw):
+                    color, nmap, moment_map, m, d, r = scene.render_surface(dist_views, h, w, **dist_kw, **kw)
+                    return color, (nmap, moment_map), m, d, r
+            else:
+                def render_scene(v, h, w, **kw):
+                    color, moment_map, m, d, r = scene.render_with_distortion(dist_views, h, w, **dist_kw, **kw)
+                    return color, (None, moment_map), m, d, r
         if densify and step < until:
             means2D = torch.zeros((a.views, scene.num_gaussians, 3), device=dev, requires_grad=True)
             stat = dict(means2D_abs=torch.zeros_like(means2D, requires_grad=True)) if a.absgrad else {}
@@ -291,6 +323,8 @@ def main(argv=None) -> dict:
             means2D = None
             render, normal_map, mask, depth, radii = render_scene(views, a.size, a.size, filter_3d=filter_3d,
                                                                   antialiasing=a.antialiasing)
+        if with_dist:
+            normal_map, moment_map = normal_map
         if grids is not None:
             grid_opt.zero_grad(set_to_none=True)
             render = grids(render, view_idx)
@@ -301,6 +335,10 @@ def main(argv=None) -> dict:
             normal_loss = normal_consistency_loss(normal_map, depth, mask, views, a.normal_alpha_min)
             normal_losses.append(normal_loss.detach())
             loss = loss + a.normal_reg * normal_loss
+        if with_dist:
+            dist_loss = distortion_loss(moment_map, mask)
+            dist_losses.append(dist_loss.detach())
+            loss = loss + a.dist_reg * dist_loss
         if a.flatten_reg > 0.0:
             loss = loss + a.flatten_reg * flatten_loss(scene._scaling)
         if grids is not None:
@@ -351,6 +389,10 @@ def main(argv=None) -> dict:
                    flatten_reg=a.flatten_reg)
         if normal_losses:
             res.update(normal_loss_first=float(normal_losses[0]), normal_loss_last=float(normal_losses[-1]))
+    if a.dist_reg > 0.0:
+        res.update(dist_reg=a.dist_reg, dist_reg_from=a.dist_reg_from, dist_space=a.dist_space)
+        if dist_losses:
+            res.update(dist_loss_first=float(dist_losses[0]), dist_loss_last=float(dist_losses[-1]))
     if densify:
         res.update(gaussians_first=gaussians_first, gaussians_last=scene.num_gaussians, densify_events=events)
     if mcmc is not None:

@@ -15,9 +15,13 @@ Files written by this project's own `export_ply` store the opacity as it is: pas
 `--normals OUT.npy` also writes `(2, V, 3, H, W)`: the rendered normal map (the Gaussians' shortest axes, turned toward the
 camera, blended as a payload and divided by the mask where it exceeds `--normal-alpha-min`) and the normals of the rendered
 depth (`depth_to_normals`, 0 where invalid) of the same views, both in camera space.
+`--distortion OUT.npy` also writes `(V, H, W)`: the depth distortion map `A M2 - M1^2` of the same views,
+from a render with the depth moments of the Gaussians as the payload: depths in `--dist-space` (default ndc, with the
+cameras' near / far), taken about `depth_pivot` at the scene's centre.
 
 usage: python tools/render_ply.py scene.ply --out renders [--views 8] [--size 256] [--distance 2.5] [--opacity logit]
-                                  [--antialiasing] [--normals OUT.npy] [--normal-alpha-min 0.5]"""
+                                  [--antialiasing] [--normals OUT.npy] [--normal-alpha-min 0.5]
+                                  [--distortion OUT.npy] [--dist-space ndc|linear|disparity]"""
 from __future__ import annotations
 
 import argparse
@@ -78,6 +82,8 @@ def main(argv=None) -> dict:
     ap.add_argument("--normals", default=None, metavar="OUT.npy",
                     help="also write the rendered normal map and the normals of the rendered depth, (2, V, 3, H, W)")
     ap.add_argument("--normal-alpha-min", type=float, default=0.5, help="(a default, not a measurement)")
+    ap.add_argument("--distortion", default=None, metavar="OUT.npy", help="also write the depth distortion map, (V, H, W)")
+    ap.add_argument("--dist-space", choices=("ndc", "linear", "disparity"), default="ndc")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         sys.exit("render_ply needs an MI355X: no ROCm device is visible (there is no CPU fallback)")
@@ -105,6 +111,14 @@ def main(argv=None) -> dict:
                 normal_map = torch.where(covered, normal_map / mask[:, None].clamp_min(1e-12), torch.zeros_like(normal_map))
                 from_depth, _ = depth_to_normals(depth, mask, views, a.normal_alpha_min)
                 both = torch.stack([normal_map, from_depth])
+            if a.distortion:    # a render with the depth moments as the payload, and its own mask
+                from latentsplat_amd.distortion import depth_pivot, distortion_map, gaussian_depth_moments, with_near_far
+                dist_views = with_near_far(views, near, far)
+                moments = gaussian_depth_moments(dist_views, s.means, a.dist_space, depth_pivot(dist_views, centre, a.dist_space))
+                _, moment_map, dist_mask, _, _ = rasterize_views(views, a.size, a.size, s.sh_degree, s.means, s.covariances,
+                                                                 s.opacities, shs=s.shs, features=moments,
+                                                                 antialiasing=a.antialiasing)
+                distortion = distortion_map(moment_map, dist_mask)
             depth = depth * near[:, None, None]        # (the table rescales the scene so that near == 1)
     finally:
         set_color_sh_convention(convention)
@@ -114,6 +128,8 @@ def main(argv=None) -> dict:
     np.save(os.path.join(a.out, "depth.npy"), depth.cpu().numpy())
     if a.normals:
         np.save(a.normals, both.cpu().numpy())
+    if a.distortion:
+        np.save(a.distortion, distortion.cpu().numpy())
     status = dict(status, gaussians=int(s.means.shape[0]), sh_degree=int(s.sh_degree), views=a.views, size=a.size,
                   visible=[int(v) for v in (radii > 0).sum(dim=1).tolist()], centre=[float(c) for c in centre.tolist()],
                   extent=float(extent), antialiasing=bool(a.antialiasing))

@@ -29,7 +29,14 @@
      the published rule) or by a least-squares fit against the render every step (`--depth-align fit`), a mean over the
      pixels weighted by the coverage, times a weight on the `expon_lr` schedule from `--depth-prior-weight` to
      `--depth-prior-weight-final` over the run.  `metrics.json` then also holds `depth_loss_first` / `depth_loss_last`: the
-     weighted depth terms of the first and the last step.
+     weighted depth terms of the first and the last step;
+  9. the two geometric regularisers, both off by default, from step `--reg-from` on.
+     `--normal-reg W`: W times `normal_consistency_loss` at the pixels covered more than `--normal-alpha-min`.  `--dist-reg W`:
+     W times `distortion_loss` with the capture's coverage map as the weight, the depths in `--dist-space` (default ndc, with
+     the capture's near / far) about `depth_pivot` at the centroid of the capture's sparse points.  One render carries what is
+     asked for: `render_with_normals`, `render_with_distortion`, or `render_surface` for both.  `metrics.json` then holds the
+     settings and `normal_loss_first / _last`, `dist_loss_first / _last`: the unweighted terms of the first and last step
+     they were on.
 
 usage: python tools/train_colmap.py ROOT --out DIR [--sparse sparse/0] [--images images] [--resolution 1] [--hold 8] [--steps 30000]
                                     [--batch 1] [--seed 0] [--lambda-dssim 0.2] [--sh-degree 3] [--sh-degree-interval 1000]
@@ -38,7 +45,9 @@ usage: python tools/train_colmap.py ROOT --out DIR [--sparse sparse/0] [--images
                                     [--cap-max N] [--noise-lr 5e5] [--opacity-reg 0.01] [--scale-reg 0.01]
                                     [--antialiasing] [--filter-3d] [--filter-3d-interval 100]
                                     [--depth-sparse 0] [--depth-priors DIR] [--depth-prior-weight 1.0]
-                                    [--depth-prior-weight-final 0.01] [--depth-align given|fit]"""
+                                    [--depth-prior-weight-final 0.01] [--depth-align given|fit]
+                                    [--normal-reg 0] [--dist-reg 0] [--reg-from 0] [--normal-alpha-min 0.5]
+                                    [--dist-space ndc|linear|disparity]"""
 from __future__ import annotations
 
 import argparse
@@ -109,7 +118,14 @@ def main(argv=None) -> dict:
     ap.add_argument("--depth-prior-weight", type=float, default=1.0)
     ap.add_argument("--depth-prior-weight-final", type=float, default=0.01, help="reached at --steps")
     ap.add_argument("--depth-align", choices=("given", "fit"), default="given", help="priors: the per-image scale / offset from the sparse points, or a fit per step")
+    ap.add_argument("--normal-reg", type=float, default=0.0, help="weight of the depth-normal consistency loss (0: off, the default)")
+    ap.add_argument("--dist-reg", type=float, default=0.0, help="weight of the depth distortion loss (0: off, the default)")
+    ap.add_argument("--reg-from", type=int, default=0, help="neither regulariser before this step")
+    ap.add_argument("--normal-alpha-min", type=float, default=0.5, help="(a default, not a measurement)")
+    ap.add_argument("--dist-space", choices=("ndc", "linear", "disparity"), default="ndc")
     a = ap.parse_args(argv)
+    if a.normal_reg < 0 or a.dist_reg < 0 or a.reg_from < 0 or not a.normal_alpha_min > 0:
+        sys.exit("--normal-reg, --dist-reg and --reg-from must not be negative and --normal-alpha-min must be positive")
     if a.steps < 1 or a.batch < 1 or a.hold < 0 or a.densify_interval < 0 or a.sh_degree_interval < 0 or a.filter_3d_interval < 1:
         sys.exit("--steps, --batch and --filter-3d-interval must be positive; --hold and the intervals must not be negative")
     if not 0.0 <= a.lambda_dssim <= 1.0 or not 0 <= a.sh_degree <= 4 or not a.resolution > 0:
@@ -150,6 +166,12 @@ def main(argv=None) -> dict:
     if a.strategy == "mcmc":
         from latentsplat_amd.mcmc import MCMCControl
         mcmc = MCMCControl(scene, max(a.cap_max, scene.num_gaussians), a.min_opacity)
+    if a.normal_reg > 0:
+        from latentsplat_amd.normals import normal_consistency_loss
+    if a.dist_reg > 0:
+        from latentsplat_amd.distortion import depth_pivot, distortion_loss, with_near_far
+        centroid = torch.from_numpy(capture.model.xyz.astype("float64").mean(axis=0))
+    normal_losses, dist_losses = [], []
     groups = capture.size_groups(train)
     group_views = {size: capture.views(idx, black) for size, idx in groups.items()}
     filter_3d, events = None, []
@@ -176,8 +198,30 @@ def main(argv=None) -> dict:
         collect = control is not None and step < a.densify_until
         means2D = torch.zeros((len(idx), scene.num_gaussians, 3), device=dev, requires_grad=True) if collect else None
         kw = dict(means2D=means2D) if collect else {}
-        render, _, mask, depth, radii = scene.render(views, H, W, filter_3d=filter_3d, antialiasing=a.antialiasing, **kw)
+        with_normals, with_dist = a.normal_reg > 0 and step >= a.reg_from, a.dist_reg > 0 and step >= a.reg_from
+        if with_dist:       # near / far where space="ndc" reads them (the NATIVE render does not), and the pivot of these views
+            views = with_near_far(views, capture.near[idx], capture.far[idx])
+            dist_kw = dict(space=a.dist_space, pivot=depth_pivot(views, centroid, a.dist_space), check_near_far=False)
+        if with_dist and with_normals:
+            render, normal_map, moment_map, mask, depth, radii = scene.render_surface(views, H, W, filter_3d=filter_3d,
+                                                                                      antialiasing=a.antialiasing, **dist_kw, **kw)
+        elif with_dist:
+            render, moment_map, mask, depth, radii = scene.render_with_distortion(views, H, W, filter_3d=filter_3d,
+                                                                                  antialiasing=a.antialiasing, **dist_kw, **kw)
+        elif with_normals:
+            render, normal_map, mask, depth, radii = scene.render_with_normals(views, H, W, filter_3d=filter_3d,
+                                                                               antialiasing=a.antialiasing, **kw)
+        else:               # (neither: the call it was)
+            render, _, mask, depth, radii = scene.render(views, H, W, filter_3d=filter_3d, antialiasing=a.antialiasing, **kw)
         loss = photometric_loss(render * cover, target * cover, a.lambda_dssim)
+        if with_normals:
+            normal_losses.append(normal_consistency_loss(normal_map, depth, mask, views, a.normal_alpha_min))
+            loss = loss + a.normal_reg * normal_losses[-1]
+            normal_losses[-1] = normal_losses[-1].detach()
+        if with_dist:
+            dist_losses.append(distortion_loss(moment_map, mask, cover[:, 0].contiguous()))
+            loss = loss + a.dist_reg * dist_losses[-1]
+            dist_losses[-1] = dist_losses[-1].detach()
         if depth_on:
             depth_term = 0.0
             if a.depth_sparse > 0:
@@ -228,6 +272,13 @@ def main(argv=None) -> dict:
     if depth_on:
         res.update(depth_loss_first=float(depth_losses[0]), depth_loss_last=float(depth_losses[-1]), depth_sparse=a.depth_sparse,
                    depth_priors=priors_found, depth_align=a.depth_align)
+    if a.normal_reg > 0 or a.dist_reg > 0:
+        res.update(normal_reg=a.normal_reg, dist_reg=a.dist_reg, reg_from=a.reg_from, normal_alpha_min=a.normal_alpha_min,
+                   dist_space=a.dist_space)
+        if normal_losses:
+            res.update(normal_loss_first=float(normal_losses[0]), normal_loss_last=float(normal_losses[-1]))
+        if dist_losses:
+            res.update(dist_loss_first=float(dist_losses[0]), dist_loss_last=float(dist_losses[-1]))
     if test:
         psnr, ssim, names = [], [], []
         with torch.no_grad():
