@@ -52,3 +52,24 @@ def quad(t: Tensor) -> Tensor:
 
 def workspace(nbytes: int, dev) -> Tensor:
     return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
+def loss_workspace(nbytes: int, dev) -> Tensor:
+    """The workspace of an image loss: never empty (``lsr_*_workspace_bytes`` is 0 for refused dims, and the call that
+    names the refusal wants a pointer), and 16 bytes are what torch aligns to 16."""
+    return workspace(max(nbytes, 16), dev)
+
+
+def upstream(name: str, t, device, what: str = "1 element on the images' device") -> Tensor:
+    """The upstream gradient of a scalar loss, which the kernel reads on the device: a one-element float32 tensor there,
+    detached and contiguous."""
+    if not torch.is_tensor(t) or t.device != device or t.dtype != torch.float32 or t.numel() != 1:
+        raise LsrError(f"{name} must be a float32 tensor of {what}")
+    return t.detach().contiguous()
+
+
+def results(want, shapes: dict, dev, out: Optional[dict] = None) -> dict:
+    """The tensors a forward writes, one per name in ``want``: the caller's from ``out`` where given, else a fresh one of
+    ``shapes[k]``, float32 (``valid`` is a uint8 mask)."""
+    return {k: out[k] if out is not None and k in out else
+            torch.empty(shapes[k], dtype=torch.uint8 if k == "valid" else torch.float32, device=dev) for k in want}

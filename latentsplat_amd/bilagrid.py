@@ -105,7 +105,7 @@ def tv_forward(grids: Tensor) -> Tensor:
     lib = _lib.load()
     dims = _dims(g)
     tv = torch.empty(1, dtype=torch.float32, device=g.device)
-    workspace = _args.workspace(max(lib.lsr_bilagrid_tv_workspace_bytes(C.byref(dims)), 16), g.device)
+    workspace = _args.loss_workspace(lib.lsr_bilagrid_tv_workspace_bytes(C.byref(dims)), g.device)
     with torch.cuda.device(g.device):
         _lib.call("lsr_bilagrid_tv_forward", C.byref(dims), ptr(g), ptr(workspace), ptr(tv), _args.stream(g))
     return tv
@@ -115,9 +115,7 @@ def tv_backward(grids: Tensor, grad_tv: Tensor) -> Tensor:
     """``lsr_bilagrid_tv_backward`` as it is: ``grad_tv * d tv / d grids``; ``grad_tv`` is a one-element float32 tensor on
     the device."""
     _check_grids("bilagrid_tv", grids)
-    if not torch.is_tensor(grad_tv) or grad_tv.device != grids.device or grad_tv.dtype != torch.float32 or grad_tv.numel() != 1:
-        raise _lib.LsrError("grad_tv must be a float32 tensor of one element on the grids' device")
-    g, up = grids.detach().contiguous(), grad_tv.detach().contiguous()
+    g, up = grids.detach().contiguous(), _args.upstream("grad_tv", grad_tv, grids.device, "one element on the grids' device")
     grad = torch.empty_like(g)
     with torch.cuda.device(g.device):
         _lib.call("lsr_bilagrid_tv_backward", C.byref(_dims(g)), ptr(g), ptr(up), ptr(grad), _args.stream(g))

@@ -356,45 +356,29 @@ struct TvShape {
 };
 
 __global__ __launch_bounds__(kBgThreads) void k_bg_tv_fwd(TvShape s, const float *__restrict__ g, double *__restrict__ slots) {
-    __shared__ double s_red[3 * kBgThreads / LSR_WAVE];
-    double sx = 0.0, sy = 0.0, sl = 0.0;
+    __shared__ double s_red[kBgThreads / LSR_WAVE][3];
+    double sum[3] = {0.0, 0.0, 0.0};                 // squared differences along x, y, l
     const int64_t stride = (int64_t)gridDim.x * kBgThreads;
     const int yx = s.Y * s.X;
     for (int64_t e = (int64_t)blockIdx.x * kBgThreads + threadIdx.x; e < s.total; e += stride) {
         const int cell = (int)(e % ((int64_t)s.L * yx));
         const int x = cell % s.X, y = cell / s.X % s.Y, l = cell / yx;
         const float v = g[e];
-        if (x + 1 < s.X) { const float d = g[e + 1] - v; sx += (double)d * (double)d; }
-        if (y + 1 < s.Y) { const float d = g[e + s.X] - v; sy += (double)d * (double)d; }
-        if (l + 1 < s.L) { const float d = g[e + yx] - v; sl += (double)d * (double)d; }
+        if (x + 1 < s.X) { const float d = g[e + 1] - v; sum[0] += (double)d * (double)d; }
+        if (y + 1 < s.Y) { const float d = g[e + s.X] - v; sum[1] += (double)d * (double)d; }
+        if (l + 1 < s.L) { const float d = g[e + yx] - v; sum[2] += (double)d * (double)d; }
     }
-    wave_all_each(Add(), sx, sy, sl);
-    const int wave = threadIdx.x / LSR_WAVE;
-    if ((threadIdx.x & (LSR_WAVE - 1)) == 0) { s_red[3 * wave] = sx; s_red[3 * wave + 1] = sy; s_red[3 * wave + 2] = sl; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        double t = s_red[threadIdx.x];
-        for (int w = 1; w < kBgThreads / LSR_WAVE; ++w) t += s_red[3 * w + threadIdx.x];
-        slots[3 * (int64_t)blockIdx.x + threadIdx.x] = t;
-    }
+    block_sum<kBgThreads, 3>(sum, s_red, slots + 3 * (int64_t)blockIdx.x);
 }
 
 // one workgroup: lane i adds the slots i, i + 256, ... of each axis, the lanes' sums are added in a fixed order
 __global__ __launch_bounds__(kBgThreads) void k_bg_tv_finish(const double *__restrict__ slots, int blocks, double inv_x, double inv_y,
                                                              double inv_l, float *tv) {
-    __shared__ double s_red[3 * kBgThreads / LSR_WAVE];
-    double sx = 0.0, sy = 0.0, sl = 0.0;
-    for (int b = threadIdx.x; b < blocks; b += kBgThreads) { sx += slots[3 * b]; sy += slots[3 * b + 1]; sl += slots[3 * b + 2]; }
-    wave_all_each(Add(), sx, sy, sl);
-    const int wave = threadIdx.x / LSR_WAVE;
-    if ((threadIdx.x & (LSR_WAVE - 1)) == 0) { s_red[3 * wave] = sx; s_red[3 * wave + 1] = sy; s_red[3 * wave + 2] = sl; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t[3] = {s_red[0], s_red[1], s_red[2]};
-        for (int w = 1; w < kBgThreads / LSR_WAVE; ++w)
-            for (int k = 0; k < 3; ++k) t[k] += s_red[3 * w + k];
-        *tv = (float)(t[0] * inv_x + t[1] * inv_y + t[2] * inv_l);
-    }
+    __shared__ double s_red[kBgThreads / LSR_WAVE][3];
+    double sum[3] = {0.0, 0.0, 0.0}, t[3];
+    for (int b = threadIdx.x; b < blocks; b += kBgThreads) { sum[0] += slots[3 * b]; sum[1] += slots[3 * b + 1]; sum[2] += slots[3 * b + 2]; }
+    block_sum<kBgThreads, 3, 1>(sum, s_red, t);
+    if (threadIdx.x == 0) *tv = (float)(t[0] * inv_x + t[1] * inv_y + t[2] * inv_l);
 }
 
 __global__ __launch_bounds__(kBgThreads) void k_bg_tv_bwd(TvShape s, const float *__restrict__ g, const float *__restrict__ grad_tv,

@@ -9,9 +9,10 @@
 //     output plane for itself, dl_store): the assignment of pixels to lanes, and with it the order of every sum, is the
 //     same either way, so a view gives the same bits alone, in a batch, and from a misaligned plane (H W % 4 != 0);
 //   * the per-pixel arithmetic is in double (the division included: the pass stays bound by its loads);
-//   * a lane adds its pixels in index order; the workgroup's sum is the wave butterfly of lsr_wave.h (wave_all_each), then
-//     the four waves in order, written to the workgroup's own slot;
-//   * a finishing launch gives a wave to a view: lane l adds the slots l, l + 64, ... in order, then the butterfly.
+//   * a lane adds its pixels in index order; the workgroup's sums are block_sum of lsr_wave.h (the wave butterfly, then
+//     the four waves in order), written to the workgroup's own slot;
+//   * a finishing launch gives a wave to a view (lsr_image_sum.h: lane l adds the slots l, l + 64, ... in order, then the
+//     butterfly).
 // The per-view table (a, b, 1 / N_v) is written by the finishing launches and read by the main pass (FIT) and the backward.
 // No atomics, no allocation, nothing read back.
 #include <float.h>
@@ -20,7 +21,7 @@
 #include <cmath>
 
 #include "lsr_depth_loss.h"
-#include "lsr_wave.h"
+#include "lsr_image_sum.h"
 
 namespace lsr {
 
@@ -30,7 +31,6 @@ constexpr int kDlGroups = kDlChunk / 4 / kDlThreads;     // groups of 4 pixels p
 constexpr int kDlWaves = kDlThreads / LSR_WAVE;
 constexpr int kDlTable = 4;                              // doubles per view: a, b, 1 / N_v (0: the row gives nothing), N_v
 constexpr int kDlMoments = 6;                            // count of w > 0, sums of w, w t, w I, w t^2, w t I
-constexpr int kDlFinishThreads = 1024;
 static_assert(kDlChunk == 4 * kDlThreads * kDlGroups, "a chunk is whole groups for every lane");
 
 struct DlShape {
@@ -117,24 +117,6 @@ __device__ __forceinline__ void dl_chunk(const DlShape &s, int &view, int &first
     first = (int)(b - v * per) * kDlChunk;
 }
 
-// The workgroup's sums of N values per lane into slot[N]: the butterfly, then the waves in order.
-template <int N>
-__device__ __forceinline__ void dl_block_sums(double (&v)[N], double *__restrict__ slot) {
-    __shared__ double s_red[kDlWaves][N];
-#pragma unroll
-    for (int k = 0; k < N; ++k) v[k] = wave_all(v[k], Add());
-    if ((threadIdx.x & (LSR_WAVE - 1)) == 0) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) s_red[threadIdx.x / LSR_WAVE][k] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < N) {
-        double t = s_red[0][threadIdx.x];
-        for (int w = 1; w < kDlWaves; ++w) t += s_red[w][threadIdx.x];
-        slot[threadIdx.x] = t;
-    }
-}
-
 struct DlArgs {
     DlShape s;
     float alpha_min;
@@ -147,6 +129,7 @@ struct DlArgs {
 
 // FIT, first pass: the moments of (w, target, I) per chunk.
 __global__ __launch_bounds__(kDlThreads) void k_dl_moments(DlArgs a) {
+    __shared__ double s_red[kDlWaves][kDlMoments];
     int view, first;
     dl_chunk(a.s, view, first);
     const int64_t base = (int64_t)view * a.s.pixels;
@@ -177,7 +160,7 @@ __global__ __launch_bounds__(kDlThreads) void k_dl_moments(DlArgs a) {
             m[5] += w * tt * I;
         }
     }
-    dl_block_sums<kDlMoments>(m, a.slots + (size_t)blockIdx.x * kDlMoments);
+    block_sum<kDlThreads, kDlMoments>(m, s_red, a.slots + (size_t)blockIdx.x * kDlMoments);
 }
 
 // FIT, second pass: a wave per view adds the view's moment slots and solves the 2 x 2 system.
@@ -185,13 +168,8 @@ __global__ __launch_bounds__(kDlThreads) void k_dl_fit(const double *__restrict_
                                                       float *__restrict__ affine_out) {
     const int view = (int)blockIdx.x * kDlWaves + (int)(threadIdx.x / LSR_WAVE), lane = threadIdx.x & (LSR_WAVE - 1);
     if (view >= s.V) return;                       // (a whole wave leaves: the butterfly below has all its lanes)
-    const double *p = slots + (size_t)view * s.chunks * kDlMoments;
-    double m[kDlMoments] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int c = lane; c < s.chunks; c += LSR_WAVE)
-#pragma unroll
-        for (int k = 0; k < kDlMoments; ++k) m[k] += p[(size_t)c * kDlMoments + k];
-#pragma unroll
-    for (int k = 0; k < kDlMoments; ++k) m[k] = wave_all(m[k], Add());
+    double m[kDlMoments];
+    image_slot_sums<kDlMoments>(slots + (size_t)view * s.chunks * kDlMoments, s.chunks, m);
     if (lane != 0) return;
     const double count = m[0], Sw = m[1], St = m[2], SI = m[3], Stt = m[4], StI = m[5];
     double fa = 0.0, fb = 0.0;
@@ -210,6 +188,7 @@ __global__ __launch_bounds__(kDlThreads) void k_dl_fit(const double *__restrict_
 
 // The main pass: sums of |r| and of w per chunk, and the map.
 __global__ __launch_bounds__(kDlThreads) void k_dl_fwd(DlArgs a) {
+    __shared__ double s_red[kDlWaves][2];
     int view, first;
     dl_chunk(a.s, view, first);
     const int64_t base = (int64_t)view * a.s.pixels;
@@ -243,29 +222,28 @@ __global__ __launch_bounds__(kDlThreads) void k_dl_fwd(DlArgs a) {
         }
         if (map) dl_store(map, al_m, i, n, make_float4(out[0], out[1], out[2], out[3]));
     }
-    dl_block_sums<2>(sums, a.slots + (size_t)blockIdx.x * 2);
+    block_sum<kDlThreads, 2>(sums, s_red, a.slots + (size_t)blockIdx.x * 2);
 }
 
-// One workgroup: wave w finishes the views w, w + 16, ... (lane l the slots l, l + 64, ... of the view, then the butterfly),
-// writes the view's table row and per_view; thread 0 then adds the waves' totals in order for the loss.
-__global__ __launch_bounds__(kDlFinishThreads) void k_dl_finish(const double *__restrict__ slots, DlShape s, int fit, int by_weights,
-                                                                const float *__restrict__ affine_in, double *__restrict__ table,
-                                                                float *loss, float *per_view, float *affine_out) {
-    constexpr int kWaves = kDlFinishThreads / LSR_WAVE;
+// The finish of lsr_image_sum.h in its order, with the loop written out here: wave w finishes the views w, w + 16, ...
+// (image_slot_sums), reads and writes the view's table row and per_view; thread 0 then adds the waves' totals in order
+// for the loss.
+__global__ __launch_bounds__(kFinishThreads) void k_dl_finish(const double *__restrict__ slots, DlShape s, int fit, int by_weights,
+                                                              const float *__restrict__ affine_in, double *__restrict__ table,
+                                                              float *loss, float *per_view, float *affine_out) {
+    constexpr int kWaves = kFinishThreads / LSR_WAVE;
     __shared__ double s_tot[kWaves];
     const int wave = threadIdx.x / LSR_WAVE, lane = threadIdx.x & (LSR_WAVE - 1);
     double tot = 0.0;
     for (int v = wave; v < s.V; v += kWaves) {
-        const double *p = slots + (size_t)v * s.chunks * 2;
-        double sr = 0.0, sw = 0.0;
-        for (int c = lane; c < s.chunks; c += LSR_WAVE) { sr += p[2 * (size_t)c]; sw += p[2 * (size_t)c + 1]; }
-        wave_all_each(Add(), sr, sw);
+        double sum[2];                              // of |r|, of w
+        image_slot_sums<2>(slots + (size_t)v * s.chunks * 2, s.chunks, sum);
         double fa = 1.0, fb = 0.0;
         if (fit) { fa = table[(size_t)v * kDlTable]; fb = table[(size_t)v * kDlTable + 1]; }
         else if (affine_in) { fa = (double)affine_in[2 * v]; fb = (double)affine_in[2 * v + 1]; }
-        const double N = by_weights ? sw : (double)s.pixels;
+        const double N = by_weights ? sum[1] : (double)s.pixels;
         const double inv = fa != 0.0 && N > 0.0 ? 1.0 / N : 0.0;
-        const double pv = inv != 0.0 ? sr * inv : 0.0;
+        const double pv = inv != 0.0 ? sum[0] * inv : 0.0;
         if (lane == 0) {
             double *row = table + (size_t)v * kDlTable;
             if (!fit) { row[0] = fa; row[1] = fb; }
@@ -404,7 +382,7 @@ int lsr_depth_loss_forward(const lsr_depth_loss_dims *dims, const float *depth, 
     }
     a.slots = (double *)(ws + L.main_slots);
     hipLaunchKernelGGL(k_dl_fwd, dim3(blocks), dim3(kDlThreads), 0, st, a);
-    hipLaunchKernelGGL(k_dl_finish, dim3(1), dim3(kDlFinishThreads), 0, st, (const double *)a.slots, s, fit,
+    hipLaunchKernelGGL(k_dl_finish, dim3(1), dim3(kFinishThreads), 0, st, (const double *)a.slots, s, fit,
                        (int)(dims->normalize == LSR_DEPTH_NORM_WEIGHTS), a.affine_in, a.table, loss, per_view, affine_out);
     return launch_status();
 }

@@ -14,19 +14,19 @@
 // store.  The backward walks the same loop, adds (g0 + 2 m' g1) dm/dz per view in order into one double per axis of the
 // row: written, no atomics.
 //
-// B, k_distl_fwd + k_distl_finish / k_distl_bwd, shaped like depth_loss.hip: a workgroup of 256 lanes owns LSR_DIST_CHUNK
+// B, k_distl_fwd + k_image_mean_finish / k_distl_bwd, shaped like depth_loss.hip: a workgroup of 256 lanes owns LSR_DIST_CHUNK
 // consecutive pixels of one view, a lane groups of 4 consecutive pixels counted from the start of the VIEW: one 16-byte
 // load per plane where the plane is 16-byte aligned and the group whole, single floats elsewhere; the assignment of
 // pixels to lanes is the same either way, so a view gives the same bits alone and in a batch.  d = alpha M2 - M1^2 is
 // formed in double (two products of float32 values are exact in double: the difference carries ONE rounding, whatever it
 // cancels), summed per chunk in a fixed order (the lane's pixels in order, the wave butterfly, the four waves in order)
-// into the chunk's own slot; k_distl_finish adds the slots of an image.
+// into the chunk's own slot; the finish of lsr_image_sum.h adds the slots of an image.
 #include <math.h>
 
 #include <cmath>
 
 #include "lsr_distortion.h"
-#include "lsr_wave.h"
+#include "lsr_image_sum.h"
 
 namespace lsr {
 
@@ -132,7 +132,6 @@ static unsigned dist_blocks(int64_t n) {
 
 constexpr int kDistlThreads = 256;
 constexpr int kDistlGroups = LSR_DIST_CHUNK / (4 * kDistlThreads);      // groups of 4 pixels per lane
-constexpr int kDistlFinishThreads = 1024;
 static_assert(kDistlGroups * 4 * kDistlThreads == LSR_DIST_CHUNK, "a chunk is whole groups for every lane");
 
 struct DistlShape {
@@ -170,14 +169,14 @@ struct DistlFwdArgs {
 };
 
 __global__ __launch_bounds__(kDistlThreads) void k_distl_fwd(DistlFwdArgs a) {
-    __shared__ double s_red[kDistlThreads / LSR_WAVE];
+    __shared__ double s_red[kDistlThreads / LSR_WAVE][1];
     const int image = (int)(blockIdx.x / (uint32_t)a.s.chunks), chunk = (int)(blockIdx.x % (uint32_t)a.s.chunks);
     const int64_t P = a.s.pixels;
     const float *M1 = a.moment_map + 2 * P * image, *M2 = M1 + P, *A = a.alpha + P * image;
     const float *Wt = a.weight ? a.weight + P * image : nullptr;
     float *Dm = a.distortion ? a.distortion + P * image : nullptr;
     const bool al1 = distl_aligned(M1), al2 = distl_aligned(M2), ala = distl_aligned(A), alw = distl_aligned(Wt), ald = distl_aligned(Dm);
-    double sum = 0.0;
+    double sum[1] = {0.0};
 #pragma unroll
     for (int k = 0; k < kDistlGroups; ++k) {
         const int64_t at = (int64_t)chunk * LSR_DIST_CHUNK + ((int64_t)k * kDistlThreads + threadIdx.x) * 4;
@@ -190,44 +189,13 @@ __global__ __launch_bounds__(kDistlThreads) void k_distl_fwd(DistlFwdArgs a) {
         const double d2 = (double)al.z * (double)m2.z - (double)m1.z * (double)m1.z;
         const double d3 = (double)al.w * (double)m2.w - (double)m1.w * (double)m1.w;
         // (entries past the plane hold 0 and add 0)
-        sum += (double)w.x * d0; sum += (double)w.y * d1; sum += (double)w.z * d2; sum += (double)w.w * d3;
+        sum[0] += (double)w.x * d0; sum[0] += (double)w.y * d1; sum[0] += (double)w.z * d2; sum[0] += (double)w.w * d3;
         if (Dm) distl_store4(Dm, at, left, ald, make_float4((float)d0, (float)d1, (float)d2, (float)d3));
     }
-    // the chunk's sum in a fixed order: the wave butterfly, then the waves in order
-    sum = wave_all(sum, Add());
-    if ((threadIdx.x & (LSR_WAVE - 1)) == 0) s_red[threadIdx.x / LSR_WAVE] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = s_red[0];
-        for (int w = 1; w < kDistlThreads / LSR_WAVE; ++w) t += s_red[w];
-        a.slots[blockIdx.x] = t;
-    }
+    block_sum<kDistlThreads, 1>(sum, s_red, a.slots + blockIdx.x);
 }
 
-// One workgroup: wave w adds the slots of images w, w + 16, ... (lane l the slots l, l + 64, ... of the image, in double),
-// then thread 0 adds the waves' totals in order.
-__global__ __launch_bounds__(kDistlFinishThreads) void k_distl_finish(const double *__restrict__ slots, int V, int slots_per_image,
-                                                                double inv_pixels, float *loss, float *per_view) {
-    constexpr int kWaves = kDistlFinishThreads / LSR_WAVE;
-    __shared__ double s_tot[kWaves];
-    const int wave = threadIdx.x / LSR_WAVE, lane = threadIdx.x & (LSR_WAVE - 1);
-    double tot = 0.0;
-    for (int v = wave; v < V; v += kWaves) {
-        const double *p = slots + (int64_t)v * slots_per_image;
-        double t = 0.0;
-        for (int i = lane; i < slots_per_image; i += LSR_WAVE) t += p[i];
-        t = wave_all(t, Add()) * inv_pixels;
-        if (lane == 0 && per_view) per_view[v] = (float)t;
-        tot += t;
-    }
-    if (lane == 0) s_tot[wave] = tot;
-    __syncthreads();
-    if (threadIdx.x == 0 && loss) {
-        double t = 0.0;
-        for (int w = 0; w < kWaves; ++w) t += s_tot[w];
-        *loss = (float)(t / V);
-    }
-}
+struct DistlUnit {};       // this unit's k_image_mean_finish
 
 struct DistlBwdArgs {
     DistlShape s;
@@ -352,7 +320,7 @@ int lsr_distortion_loss_forward(const lsr_distortion_dims *dims, const float *mo
     // (blocks: at most V H W / 2048 + V < 2^21)
     hipLaunchKernelGGL(k_distl_fwd, dim3((unsigned)dims->num_images * (unsigned)shape.chunks), dim3(kDistlThreads), 0, s, a);
     if (loss || per_view)
-        hipLaunchKernelGGL(k_distl_finish, dim3(1), dim3(kDistlFinishThreads), 0, s, (const double *)workspace, dims->num_images,
+        hipLaunchKernelGGL(k_image_mean_finish<DistlUnit>, dim3(1), dim3(kFinishThreads), 0, s, (const double *)workspace, dims->num_images,
                            shape.chunks, 1.0 / (double)shape.pixels, loss, per_view);
     return launch_status();
 }

@@ -93,6 +93,36 @@ __device__ __forceinline__ float wave_sum32(float (&v)[32]) {
     return v[0] + __shfl_xor(v[0], 32);
 }
 
+// Sums of N doubles per lane over a workgroup of THREADS (one LDS hop, one barrier); s_red: THREADS / 64 rows of N.
+// ORDER: wave_all of every value; lane 0 of wave w stores its N sums to s_red[w]; the barrier; then total k is
+// s_red[0][k] + s_red[1][k] + ..., the waves in order from wave 0.
+// The totals go to dst[k], which the caller passes (a workspace slot, a local array): with OWNERS = N thread k forms and
+// stores total k; with OWNERS = 1 thread 0 forms all N side by side and stores them in k order.  No other thread touches
+// dst, and s_red may be reused only after another barrier.
+template <int THREADS, int N, int OWNERS = N>
+__device__ __forceinline__ void block_sum(double (&v)[N], double (*s_red)[N], double *dst) {
+    static_assert(THREADS % LSR_WAVE == 0 && (OWNERS == N || OWNERS == 1), "whole waves; a total per thread, or all in thread 0");
+    constexpr int kWaves = THREADS / LSR_WAVE, kMine = N / OWNERS;
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = wave_all(v[k], Add());
+    if ((threadIdx.x & (LSR_WAVE - 1)) == 0) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) s_red[threadIdx.x / LSR_WAVE][k] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < OWNERS) {
+        const int first = OWNERS == 1 ? 0 : (int)threadIdx.x;
+        double t[kMine];
+#pragma unroll
+        for (int j = 0; j < kMine; ++j) t[j] = s_red[0][first + j * OWNERS];
+        for (int w = 1; w < kWaves; ++w)
+#pragma unroll
+            for (int j = 0; j < kMine; ++j) t[j] += s_red[w][first + j * OWNERS];
+#pragma unroll
+        for (int j = 0; j < kMine; ++j) dst[first + j * OWNERS] = t[j];
+    }
+}
+
 // ---- scans ----
 
 // Inclusive prefix sum over the 64 lanes of a wave.

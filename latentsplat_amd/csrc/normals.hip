@@ -10,13 +10,13 @@
 // store; the pass is bound by that store.  The backward walks the same loop, adds sign W^T g per view in order into three
 // doubles and runs the quaternion chain once: written, no atomics.
 //
-// B, k_nc_fwd + k_nc_finish / k_nc_bwd, shaped like photometric.hip: a workgroup of 256 lanes owns one 32 x 32 tile of one
+// B, k_nc_fwd + k_image_mean_finish / k_nc_bwd, shaped like photometric.hip: a workgroup of 256 lanes owns one 32 x 32 tile of one
 // image.  Thread 0 derives the view's ray (six affine coefficients and the sign) in double while the others stage
 // D = depth / alpha (NaN where alpha <= alpha_min or outside the image, so that "usable" is "finite") with its halo in
 // LDS, as doubles: the per-pixel arithmetic (two differences of D r, their cross product, its norm) is a few dozen double
 // operations against 36 bytes moved, and in double the outputs carry one rounding each, whatever the cross product cancels.
 // The forward sums e per tile in a fixed order (wave butterfly, then the four waves in order) into the tile's own
-// workspace slot and k_nc_finish adds the slots of an image; the backward computes, per stencil centre of the tile and a
+// workspace slot and the finish of lsr_image_sum.h adds the slots of an image; the backward computes, per stencil centre of the tile and a
 // 1-pixel ring around it, the four scalars its neighbours will want (dL/dP of that neighbour dotted with the neighbour's
 // ray), and every pixel then gathers four of them.  No atomics, no static state.
 #include <float.h>
@@ -24,8 +24,8 @@
 
 #include <cmath>
 
+#include "lsr_image_sum.h"
 #include "lsr_normals.h"
-#include "lsr_wave.h"
 
 namespace lsr {
 
@@ -173,7 +173,6 @@ constexpr int kNcThreads = 256;
 constexpr int kNcRows = kNcTile * kNcTile / kNcThreads;      // 4 output rows per lane
 constexpr int kNcFwdSpan = kNcTile + 2;              // the forward's D: a 1-pixel halo
 constexpr int kNcBwdSpan = kNcTile + 4;              // the backward's D: a 2-pixel halo
-constexpr int kNcFinishThreads = 1024;
 
 struct NcShape {
     int H, W, tiles_x, tiles_y;
@@ -214,16 +213,6 @@ __device__ static void nc_derive_ray(const float *__restrict__ view, int H, int 
     ray.x0 = rx[0]; ray.xx = rx[1] - rx[0]; ray.xy = rx[2] - rx[0];
     ray.y0 = ry[0]; ray.yx = ry[1] - ry[0]; ray.yy = ry[2] - ry[0];
     ray.sign = ray.xx * ray.yy - ray.xy * ray.yx > 0.0 ? -1.0 : 1.0;
-}
-
-// tile of this workgroup: image, first pixel
-__device__ __forceinline__ void nc_tile(const NcShape &s, int &image, int &y0, int &x0) {
-    const uint32_t b = blockIdx.x;
-    const uint32_t per_image = (uint32_t)(s.tiles_x * s.tiles_y);
-    const uint32_t p = b / per_image, t = b - p * per_image;
-    image = (int)p;
-    y0 = (int)(t / (uint32_t)s.tiles_x) * kNcTile;
-    x0 = (int)(t % (uint32_t)s.tiles_x) * kNcTile;
 }
 
 // dst[SPAN][SPAN] = depth / alpha around the tile with a HALO-pixel ring; NaN outside the image and where alpha <= alpha_min
@@ -275,11 +264,11 @@ struct NcFwdArgs {
 
 __global__ __launch_bounds__(kNcThreads) void k_nc_fwd(NcFwdArgs a) {
     __shared__ double s_D[kNcFwdSpan * kNcFwdSpan];
-    __shared__ double s_red[kNcThreads / LSR_WAVE];
+    __shared__ double s_red[kNcThreads / LSR_WAVE][1];
     __shared__ NcRay s_ray;
     const NcShape s = a.s;
     int image, y0, x0;
-    nc_tile(s, image, y0, x0);
+    image_tile(s.tiles_x, s.tiles_y, kNcTile, image, y0, x0);
     const int64_t pixels = (int64_t)s.H * s.W, base = (int64_t)image * pixels;
     if (threadIdx.x == 0) nc_derive_ray(a.views + (size_t)image * LSR_VIEW_FLOATS, s.H, s.W, s_ray);
     nc_stage<kNcFwdSpan, 1>(s_D, a.depth + base, a.alpha + base, s, y0, x0, a.alpha_min);
@@ -288,7 +277,7 @@ __global__ __launch_bounds__(kNcThreads) void k_nc_fwd(NcFwdArgs a) {
 
     const int col = threadIdx.x % kNcTile, row0 = threadIdx.x / kNcTile * kNcRows;
     const int gx = x0 + col;
-    double sum = 0.0;
+    double sum[1] = {0.0};
 #pragma unroll
     for (int o = 0; o < kNcRows; ++o) {
         const int gy = y0 + row0 + o;
@@ -301,7 +290,7 @@ __global__ __launch_bounds__(kNcThreads) void k_nc_fwd(NcFwdArgs a) {
                 n0 = st.m[0] * k; n1 = st.m[1] * k; n2 = st.m[2] * k;
                 if (a.normal_map) {                   // (NULL: the caller wants n~ and the mask alone)
                     const float *N = a.normal_map + 3 * base + at;
-                    sum += (double)a.alpha[base + at] - ((double)N[0] * n0 + (double)N[pixels] * n1 + (double)N[2 * pixels] * n2);
+                    sum[0] += (double)a.alpha[base + at] - ((double)N[0] * n0 + (double)N[pixels] * n1 + (double)N[2 * pixels] * n2);
                 }
             }
             if (a.depth_normals) {
@@ -311,41 +300,10 @@ __global__ __launch_bounds__(kNcThreads) void k_nc_fwd(NcFwdArgs a) {
             if (a.valid) a.valid[base + at] = st.valid ? 1 : 0;
         }
     }
-    // the tile's sum in a fixed order: the wave butterfly, then the waves in order
-    sum = wave_all(sum, Add());
-    if ((threadIdx.x & (LSR_WAVE - 1)) == 0) s_red[threadIdx.x / LSR_WAVE] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = s_red[0];
-        for (int w = 1; w < kNcThreads / LSR_WAVE; ++w) t += s_red[w];
-        a.slots[blockIdx.x] = t;
-    }
+    block_sum<kNcThreads, 1>(sum, s_red, a.slots + blockIdx.x);
 }
 
-// One workgroup: wave w adds the slots of images w, w + 16, ... (lane l the slots l, l + 64, ... of the image, in double),
-// then thread 0 adds the waves' totals in order.
-__global__ __launch_bounds__(kNcFinishThreads) void k_nc_finish(const double *__restrict__ slots, int V, int slots_per_image,
-                                                                double inv_pixels, float *loss, float *per_view) {
-    constexpr int kWaves = kNcFinishThreads / LSR_WAVE;
-    __shared__ double s_tot[kWaves];
-    const int wave = threadIdx.x / LSR_WAVE, lane = threadIdx.x & (LSR_WAVE - 1);
-    double tot = 0.0;
-    for (int v = wave; v < V; v += kWaves) {
-        const double *p = slots + (int64_t)v * slots_per_image;
-        double t = 0.0;
-        for (int i = lane; i < slots_per_image; i += LSR_WAVE) t += p[i];
-        t = wave_all(t, Add()) * inv_pixels;
-        if (lane == 0 && per_view) per_view[v] = (float)t;
-        tot += t;
-    }
-    if (lane == 0) s_tot[wave] = tot;
-    __syncthreads();
-    if (threadIdx.x == 0 && loss) {
-        double t = 0.0;
-        for (int w = 0; w < kWaves; ++w) t += s_tot[w];
-        *loss = (float)(t / V);
-    }
-}
+struct NcUnit {};          // this unit's k_image_mean_finish
 
 struct NcBwdArgs {
     NcShape s;
@@ -362,7 +320,7 @@ __global__ __launch_bounds__(kNcThreads) void k_nc_bwd(NcBwdArgs a) {
     __shared__ NcRay s_ray;
     const NcShape s = a.s;
     int image, y0, x0;
-    nc_tile(s, image, y0, x0);
+    image_tile(s.tiles_x, s.tiles_y, kNcTile, image, y0, x0);
     const int64_t pixels = (int64_t)s.H * s.W, base = (int64_t)image * pixels;
     if (threadIdx.x == 0) nc_derive_ray(a.views + (size_t)image * LSR_VIEW_FLOATS, s.H, s.W, s_ray);
     nc_stage<kNcBwdSpan, 2>(s_D, a.depth + base, a.alpha + base, s, y0, x0, a.alpha_min);
@@ -516,7 +474,7 @@ int lsr_normal_consistency_forward(const lsr_normal_dims *dims, const float *nor
     NcFwdArgs a{shape, dims->alpha_min, normal_map, depth, alpha, views, (double *)workspace, depth_normals, valid};
     hipLaunchKernelGGL(k_nc_fwd, dim3((unsigned)nc_tiles(*dims)), dim3(kNcThreads), 0, s, a);
     if (loss || per_view)
-        hipLaunchKernelGGL(k_nc_finish, dim3(1), dim3(kNcFinishThreads), 0, s, (const double *)workspace, dims->num_images,
+        hipLaunchKernelGGL(k_image_mean_finish<NcUnit>, dim3(1), dim3(kFinishThreads), 0, s, (const double *)workspace, dims->num_images,
                            shape.tiles_x * shape.tiles_y, 1.0 / ((double)dims->height * (double)dims->width), loss, per_view);
     return launch_status();
 }

@@ -15,12 +15,13 @@
 // zeros) and x - c keeps the low bits of most pixel values.  The backward is written in the same shifted variables (lsr_loss.h).
 // The pixel's own x and y (the L1 term, the backward's factors) come from global memory as they are.
 // Reductions, all in double and in a fixed order: a tile sums its S and |x - y| (wave shuffles, then the four waves in
-// order) into its own workspace slot; k_photo_finish adds the slots of an image.  No float atomics, no static state.
+// order) into its own workspace slot; k_photo_finish adds the slots of an image (lsr_image_sum.h).  No float atomics, no
+// static state.
 #include <math.h>
 
 #include <cmath>
 
-#include "lsr_wave.h"
+#include "lsr_image_sum.h"
 #include "lsr_loss.h"
 
 namespace lsr {
@@ -32,7 +33,6 @@ constexpr int kPhHalo = kPhTile + 2 * kPhR;      // 42
 constexpr int kPhThreads = 256;
 constexpr int kPhRows = kPhTile * kPhTile / kPhThreads;      // 4 output rows per lane
 constexpr int kPhSpan = kPhRows + 2 * kPhR;                  // 14 rows of the horizontal pass per lane
-constexpr int kPhFinishThreads = 1024;
 constexpr float kPhC1 = 0.01f * 0.01f, kPhC2 = 0.03f * 0.03f;
 
 // exp(-(k - 5)^2 / (2 * 1.5^2)) / sum, k = 0..10, rounded from double
@@ -46,16 +46,6 @@ struct PhotoShape {
     int H, W, tiles_x, tiles_y;
 };
 
-// tile of this workgroup: plane (v * C + c), first pixel
-__device__ __forceinline__ void ph_tile(const PhotoShape &s, int64_t &plane, int &y0, int &x0) {
-    const uint32_t b = blockIdx.x;
-    const uint32_t per_plane = (uint32_t)(s.tiles_x * s.tiles_y);
-    const uint32_t p = b / per_plane, t = b - p * per_plane;
-    plane = p;
-    y0 = (int)(t / (uint32_t)s.tiles_x) * kPhTile;
-    x0 = (int)(t % (uint32_t)s.tiles_x) * kPhTile;
-}
-
 // dst[42][42] = src - shift around the tile, `outside` beyond the image
 __device__ __forceinline__ void ph_stage(float *__restrict__ dst, const float *__restrict__ src, const PhotoShape &s, int y0,
                                          int x0, float shift, float outside) {
@@ -64,24 +54,6 @@ __device__ __forceinline__ void ph_stage(float *__restrict__ dst, const float *_
         const int gy = y0 + r - kPhR, gx = x0 + c - kPhR;
         const bool in = gy >= 0 && gy < s.H && gx >= 0 && gx < s.W;
         dst[i] = in ? src[(int64_t)gy * s.W + gx] - shift : outside;
-    }
-}
-
-// sum of a lane's two values over the workgroup, in a fixed order; valid in thread 0
-__device__ __forceinline__ void ph_block_sum(double &a, double &b, double *s_red) {
-    wave_all_each(Add(), a, b);
-    const int wave = threadIdx.x / LSR_WAVE;
-    if ((threadIdx.x & (LSR_WAVE - 1)) == 0) {
-        s_red[2 * wave] = a;
-        s_red[2 * wave + 1] = b;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        a = s_red[0]; b = s_red[1];
-        for (int w = 1; w < kPhThreads / LSR_WAVE; ++w) {
-            a += s_red[2 * w];
-            b += s_red[2 * w + 1];
-        }
     }
 }
 
@@ -99,11 +71,11 @@ struct PhotoFwdArgs {
 __global__ __launch_bounds__(kPhThreads) void k_photo_fwd(PhotoFwdArgs a) {
     __shared__ float s_in[2][kPhHalo * kPhHalo];
     __shared__ float s_h[5][kPhHalo * kPhTile];
-    __shared__ double s_red[2 * kPhThreads / LSR_WAVE];
+    __shared__ double s_red[kPhThreads / LSR_WAVE][2];
     const PhotoShape s = a.s;
-    int64_t plane;
+    int64_t plane;                                   // v * C + c
     int y0, x0;
-    ph_tile(s, plane, y0, x0);
+    image_tile(s.tiles_x, s.tiles_y, kPhTile, plane, y0, x0);
     const int64_t base = plane * s.H * s.W;
     ph_stage(s_in[0], a.image + base, s, y0, x0, a.shift, -a.shift);
     ph_stage(s_in[1], a.target + base, s, y0, x0, a.shift, -a.shift);
@@ -141,7 +113,7 @@ __global__ __launch_bounds__(kPhThreads) void k_photo_fwd(PhotoFwdArgs a) {
         }
     }
 
-    double sum_s = 0.0, sum_l = 0.0;
+    double sums[2] = {0.0, 0.0};                     // of S over the cropped region, of |x - y|
     const int gx = x0 + col;
 #pragma unroll
     for (int o = 0; o < kPhRows; ++o) {
@@ -156,8 +128,8 @@ __global__ __launch_bounds__(kPhThreads) void k_photo_fwd(PhotoFwdArgs a) {
             const double A1 = 2.0 * mu1 * mu2 + (double)kPhC1, A2 = 2.0 * s12 + (double)kPhC2;
             const double B1 = mu1 * mu1 + mu2 * mu2 + (double)kPhC1, B2 = s1 + s2 + (double)kPhC2;
             const double S = (A1 * A2) / (B1 * B2);
-            if (gy >= a.crop && gy < s.H - a.crop && gx >= a.crop && gx < s.W - a.crop) sum_s += S;
-            sum_l += (double)fabsf(a.image[at] - a.target[at]);
+            if (gy >= a.crop && gy < s.H - a.crop && gx >= a.crop && gx < s.W - a.crop) sums[0] += S;
+            sums[1] += (double)fabsf(a.image[at] - a.target[at]);
             if (a.ssim_map) a.ssim_map[at] = (float)S;
             if (a.saved) {
                 const double dS1 = -S / B2;                        // dS/ds1 = -A1 A2 / (B1 B2^2)
@@ -169,48 +141,27 @@ __global__ __launch_bounds__(kPhThreads) void k_photo_fwd(PhotoFwdArgs a) {
             }
         }
     }
-    ph_block_sum(sum_s, sum_l, s_red);
-    if (threadIdx.x == 0) a.slots[blockIdx.x] = make_double2(sum_s, sum_l);
+    double tile[2];
+    block_sum<kPhThreads, 2, 1>(sums, s_red, tile);
+    if (threadIdx.x == 0) a.slots[blockIdx.x] = make_double2(tile[0], tile[1]);
 }
 
-// One workgroup: wave w adds the slots of images w, w + 16, ... (lane l the slots l, l + 64, ... of the image, in double),
-// then thread 0 adds the waves' totals in order.
-__global__ __launch_bounds__(kPhFinishThreads) void k_photo_finish(const double2 *__restrict__ slots, int V, int slots_per_image,
-                                                                   double inv_count_s, double inv_count_l, float lambda,
-                                                                   float *loss, float *l1, float *ssim) {
-    constexpr int kWaves = kPhFinishThreads / LSR_WAVE;
-    __shared__ double s_tot[2 * kWaves];
-    const int wave = threadIdx.x / LSR_WAVE, lane = threadIdx.x & (LSR_WAVE - 1);
-    double tot_s = 0.0, tot_l = 0.0;
-    for (int v = wave; v < V; v += kWaves) {
-        const double2 *p = slots + (int64_t)v * slots_per_image;
-        double a = 0.0, b = 0.0;
-        for (int i = lane; i < slots_per_image; i += LSR_WAVE) {
-            const double2 t = p[i];
-            a += t.x; b += t.y;
-        }
-        wave_all_each(Add(), a, b);
-        a *= inv_count_s; b *= inv_count_l;
-        if (lane == 0) {
-            if (ssim) ssim[v] = (float)a;
-            if (l1) l1[v] = (float)b;
-        }
-        tot_s += a; tot_l += b;
-    }
-    if (lane == 0) {
-        s_tot[2 * wave] = tot_s;
-        s_tot[2 * wave + 1] = tot_l;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && loss) {
-        double a = 0.0, b = 0.0;
-        for (int w = 0; w < kWaves; ++w) {
-            a += s_tot[2 * w];
-            b += s_tot[2 * w + 1];
-        }
-        a /= V; b /= V;
-        *loss = (float)((1.0 - (double)lambda) * b + (double)lambda * (1.0 - a));
-    }
+// The finish (lsr_image_sum.h) over the slots' two sums: an image's mean S and mean |x - y|, the loss from their means.
+__global__ __launch_bounds__(kFinishThreads) void k_photo_finish(const double *__restrict__ slots, int V, int slots_per_image,
+                                                                 double inv_count_s, double inv_count_l, float lambda,
+                                                                 float *loss, float *l1, float *ssim) {
+    image_finish<2, 2>(slots, V, slots_per_image, loss != nullptr,
+                       [=](int v, int lane, const double (&sum)[2], double (&part)[2]) {
+                           part[0] = sum[0] * inv_count_s; part[1] = sum[1] * inv_count_l;
+                           if (lane == 0) {
+                               if (ssim) ssim[v] = (float)part[0];
+                               if (l1) l1[v] = (float)part[1];
+                           }
+                       },
+                       [=](const double (&t)[2]) {
+                           const double a = t[0] / V, b = t[1] / V;
+                           *loss = (float)((1.0 - (double)lambda) * b + (double)lambda * (1.0 - a));
+                       });
 }
 
 struct PhotoBwdArgs {
@@ -225,9 +176,9 @@ __global__ __launch_bounds__(kPhThreads) void k_photo_bwd(PhotoBwdArgs a) {
     __shared__ float s_in[3][kPhHalo * kPhHalo];
     __shared__ float s_h[3][kPhHalo * kPhTile];
     const PhotoShape s = a.s;
-    int64_t plane;
+    int64_t plane;                                   // v * C + c
     int y0, x0;
-    ph_tile(s, plane, y0, x0);
+    image_tile(s.tiles_x, s.tiles_y, kPhTile, plane, y0, x0);
     const int64_t base = plane * s.H * s.W;
 #pragma unroll
     for (int m = 0; m < 3; ++m) ph_stage(s_in[m], a.saved + m * a.map_stride + base, s, y0, x0, 0.0f, 0.0f);
@@ -333,7 +284,7 @@ int lsr_photometric_forward(const lsr_photometric_dims *dims, const float *image
     hipLaunchKernelGGL(k_photo_fwd, dim3((unsigned)photo_tiles(*dims)), dim3(kPhThreads), 0, s, a);
     if (loss || l1 || ssim) {
         const double cropped = (double)(dims->height - 2 * dims->crop) * (double)(dims->width - 2 * dims->crop);
-        hipLaunchKernelGGL(k_photo_finish, dim3(1), dim3(kPhFinishThreads), 0, s, (const double2 *)workspace, dims->num_images,
+        hipLaunchKernelGGL(k_photo_finish, dim3(1), dim3(kFinishThreads), 0, s, (const double *)workspace, dims->num_images,
                            dims->channels * shape.tiles_x * shape.tiles_y, 1.0 / (cropped * dims->channels),
                            1.0 / ((double)pixels * dims->channels), dims->lambda_dssim, loss, l1, ssim);
     }

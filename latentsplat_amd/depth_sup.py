@@ -214,13 +214,12 @@ def inverse_depth_forward(depth: Tensor, alpha: Tensor, views: Tensor, target: T
     if affine is not None:
         affine = _args.f32(_WHO, "affine", affine, (V, 2), dev).detach().contiguous()
     shapes = {"loss": (1,), "per_view": (V,), "inverse_depth": (V, H, W), "affine": (V, 2)}
-    res = {}
-    for k in want:
-        res[k] = out[k] if out is not None and k in out else torch.empty(shapes[k], dtype=torch.float32, device=dev)
+    res = _args.results(want, shapes, dev, out)
+    for k in res:
         _args.f32(_WHO, k, res[k], shapes[k], dev, contiguous=True)
     ws = (out or {}).get("workspace")
     if ws is None:
-        ws = _args.workspace(max(_lib.load().lsr_depth_loss_workspace_bytes(C.byref(dims)), 16), dev)
+        ws = _args.loss_workspace(_lib.load().lsr_depth_loss_workspace_bytes(C.byref(dims)), dev)
     with torch.cuda.device(dev):
         _lib.call("lsr_depth_loss_forward", C.byref(dims), ptr(depth), ptr(alpha), ptr(views), ptr(target), ptr(weight), ptr(affine),
                   ptr(ws), *(ptr(res.get(k)) for k in shapes), _args.stream(dev))

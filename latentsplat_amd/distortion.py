@@ -192,10 +192,10 @@ def distortion_loss_forward(moment_map: Tensor, alpha: Tensor, weight: Optional[
     V, H, W = alpha.shape
     dev = alpha.device
     shapes = {"loss": (1,), "per_view": (V,), "distortion": (V, H, W)}
-    res = {k: (out[k] if out is not None and k in out else torch.empty(shapes[k], dtype=torch.float32, device=dev)) for k in want}
+    res = _args.results(want, shapes, dev, out)
     ws = (out or {}).get("workspace")
     if ws is None:
-        ws = _args.workspace(max(_lib.load().lsr_distortion_loss_workspace_bytes(C.byref(dims)), 16), dev)
+        ws = _args.loss_workspace(_lib.load().lsr_distortion_loss_workspace_bytes(C.byref(dims)), dev)
     with torch.cuda.device(dev):
         _lib.call("lsr_distortion_loss_forward", C.byref(dims), ptr(moment_map), ptr(alpha), ptr(weight), ptr(ws),
                   *(ptr(res.get(k)) for k in shapes), _args.stream(dev))
@@ -207,9 +207,7 @@ def distortion_loss_backward(moment_map: Tensor, alpha: Tensor, grad_loss: Tenso
     """``lsr_distortion_loss_backward`` as it is: the gradients named in ``want``, written (into the tensors of ``out``
     where given).  ``grad_loss`` is a one-element float32 tensor on the device."""
     moment_map, alpha, weight, dims = _image_inputs(moment_map, alpha, weight)
-    if not torch.is_tensor(grad_loss) or grad_loss.device != alpha.device or grad_loss.dtype != torch.float32 or grad_loss.numel() != 1:
-        raise _lib.LsrError("grad_loss must be a float32 tensor of 1 element on the images' device")
-    grad_loss = grad_loss.detach().contiguous()
+    grad_loss = _args.upstream("grad_loss", grad_loss, alpha.device)
     like = {"moment_map": moment_map, "alpha": alpha}
     res = {k: (out[k] if out is not None and k in out else torch.empty_like(like[k])) for k in want}
     with torch.cuda.device(alpha.device):

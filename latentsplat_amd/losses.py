@@ -55,8 +55,8 @@ def photometric_forward(image: Tensor, target: Tensor, lambda_dssim: float = 0.2
         raise _lib.LsrError(f"unknown outputs {unknown}; expected some of {list(shapes)}")
     lib = _lib.load()
     dims = _dims(x.shape, lambda_dssim, cov_norm, crop)
-    out = {k: torch.empty(s, dtype=torch.float32, device=x.device) for k, s in shapes.items() if k in want}
-    workspace = _args.workspace(max(lib.lsr_photometric_workspace_bytes(C.byref(dims)), 16), x.device)
+    out = _args.results([k for k in shapes if k in want], shapes, x.device)
+    workspace = _args.loss_workspace(lib.lsr_photometric_workspace_bytes(C.byref(dims)), x.device)
     with torch.cuda.device(x.device):
         _lib.call("lsr_photometric_forward", C.byref(dims), ptr(x), ptr(y), ptr(workspace),
                   *(ptr(out.get(k)) for k in shapes), _args.stream(x))

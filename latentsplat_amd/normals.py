@@ -137,16 +137,10 @@ def normal_consistency_forward(normal_map: Tensor, depth: Tensor, alpha: Tensor,
     V, H, W = depth.shape
     dev = depth.device
     shapes = {"loss": (1,), "per_view": (V,), "depth_normals": (V, 3, H, W), "valid": (V, H, W)}
-    res = {}
-    for k in want:
-        if out is not None and k in out:
-            res[k] = out[k]
-        else:
-            res[k] = torch.empty(shapes[k], dtype=torch.uint8 if k == "valid" else torch.float32, device=dev)
-    lib = _lib.load()
+    res = _args.results(want, shapes, dev, out)
     ws = (out or {}).get("workspace")
     if ws is None:
-        ws = _args.workspace(max(lib.lsr_normal_consistency_workspace_bytes(C.byref(dims)), 16), dev)
+        ws = _args.loss_workspace(_lib.load().lsr_normal_consistency_workspace_bytes(C.byref(dims)), dev)
     with torch.cuda.device(dev):
         _lib.call("lsr_normal_consistency_forward", C.byref(dims), ptr(normal_map), ptr(depth), ptr(alpha), ptr(views), ptr(ws),
                   *(ptr(res.get(k)) for k in shapes), _args.stream(dev))
@@ -158,9 +152,7 @@ def normal_consistency_backward(normal_map: Tensor, depth: Tensor, alpha: Tensor
     """``lsr_normal_consistency_backward`` as it is: the gradients named in ``want``, written (into the tensors of ``out``
     where given).  ``grad_loss`` is a one-element float32 tensor on the device."""
     normal_map, depth, alpha, views, dims = _image_inputs(normal_map, depth, alpha, views, alpha_min)
-    if not torch.is_tensor(grad_loss) or grad_loss.device != depth.device or grad_loss.dtype != torch.float32 or grad_loss.numel() != 1:
-        raise _lib.LsrError("grad_loss must be a float32 tensor of 1 element on the images' device")
-    grad_loss = grad_loss.detach().contiguous()
+    grad_loss = _args.upstream("grad_loss", grad_loss, depth.device)
     like = {"normal_map": normal_map, "depth": depth, "alpha": alpha}
     res = {k: (out[k] if out is not None and k in out else torch.empty_like(like[k])) for k in want}
     with torch.cuda.device(depth.device):

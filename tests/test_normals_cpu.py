@@ -194,7 +194,7 @@ def test_gradcheck_of_both_restatements():
 
 
 def test_the_gpu_cases_reach_both_loops_of_the_finish_kernel():
-    """k_nc_finish (csrc/normals.hip): wave w of 16 adds the images w, w + 16, ..., lane l of 64 the tiles l, l + 64, ... of
+    """k_image_mean_finish (csrc/lsr_image_sum.h): wave w of 16 adds the images w, w + 16, ..., lane l of 64 the tiles l, l + 64, ... of
     an image.  What the GPU test's cases reach, so that nobody trims them without seeing what goes."""
     from tests.test_normals_gpu import FINISH_WAVES, PAST_THE_FINISH, SIZES, TILE, WAVE
     assert (FINISH_WAVES, WAVE, TILE) == (16, 64, 32)

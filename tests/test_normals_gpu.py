@@ -139,7 +139,7 @@ def test_only_the_rotation_receives_a_gradient(hip_device):
 B_KEYS = ("normal_map", "depth", "alpha", "views")
 GRAD_LOSS = 0.75
 SIZES = [(3, 3), (1, 5), (2, 7), (5, 4), (33, 31), (65, 34), (70, 97)]
-# (V, H, W, offcentre) past the loops of k_nc_finish, which no size above enters a second time: its 16 waves take the
+# (V, H, W, offcentre) past the loops of k_image_mean_finish (csrc/lsr_image_sum.h), which no size above enters a second time: its 16 waves take the
 # images w, w + 16, ... and a wave's 64 lanes the tiles l, l + 64, ... of an image (tests/test_normals_cpu.py asserts what
 # each case reaches).  One row of valid pixels under 65 tiles, 66 tiles with a partial last one, and 9 x 8 tiles with
 # interior ones.  At 3 x 2049 and 257 x 225 the tiles from the 65th on hold border pixels alone and their slots are 0: a
