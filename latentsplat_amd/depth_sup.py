@@ -304,6 +304,12 @@ def inverse_depth_loss(depth: Tensor, alpha: Tensor, views: Tensor, target: Tens
 
     ``outputs``: a dict that receives ``per_view (V,)``, ``inverse_depth (V, H, W)`` and ``affine (V, 2)`` (values only).
 
+    The loss reads the scene scale from slot 40 of ``views`` and has no gradient for the table: a ``views`` that requires
+    grad is refused, since a silent partial pose gradient is worse than a refusal (pass ``views.detach()``).
+
     Two HIP launches forward (four with ``"fit"``) and one backward; no atomics: the same bits every call, and a view's
     numbers do not depend on which other views share the call."""
+    if torch.is_tensor(views) and views.requires_grad:
+        raise _lib.LsrError("inverse_depth_loss: views requires grad, and this operator has no pose gradient (pass "
+                            "views.detach(); the rasterizer hands the table its own)")
     return _InverseDepth.apply(depth, alpha, views, target, weight, affine, align, normalize, float(alpha_min), outputs)

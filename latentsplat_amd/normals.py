@@ -12,11 +12,17 @@ rendered depth describes:
 3. :func:`normal_consistency_loss` penalises the angle between that map and the normals obtained by differentiating the
    rendered depth map (:func:`depth_to_normals`), in one fused pass each way.
 
-What receives no gradient, and why: the shortest axis is chosen by an argmin and turned by a sign, both piecewise constant,
-so :func:`gaussian_normals` hands a gradient to ``rotation`` alone (positions, scales and the view table get theirs through
-the rasterizer: the blending weights and the depth).  In the loss the leading ``alpha`` of ``e = alpha - <N, n~>`` is a
-constant weight, as the published regulariser detaches it; ``alpha`` receives a gradient only as the denominator of the
-expected depth.
+What receives no gradient, and why: the shortest axis is chosen by an argmin and turned by a sign, both piecewise constant
+in the positions and the scales, so :func:`gaussian_normals` hands a gradient to ``rotation`` alone (positions and scales
+get theirs through the rasterizer: the blending weights and the depth).  In the loss the leading ``alpha`` of
+``e = alpha - <N, n~>`` is a constant weight, as the published regulariser detaches it; ``alpha`` receives a gradient only
+as the denominator of the expected depth.
+
+The view table is NOT a constant of these operators: the normals are ``n_cam = R_view n_world``, smooth in the view
+rotation, and the loss builds its pixel rays from the view and projection matrices.  Neither operator has a table
+gradient, so both refuse a table that requires grad instead of returning a silent partial one (on a 200-Gaussian scene
+the omitted part was 27 % of the full table gradient's norm).  Pass ``views.detach()`` to them and the
+leaf to the render: the rasterizer hands the table its own gradient, which is then the partial one by the caller's choice.
 
 float32 ROCm tensors only; there is no CPU fallback."""
 from __future__ import annotations
@@ -50,6 +56,12 @@ def _scene_inputs(views, xyz, scaling, rotation):
         raise _lib.LsrError(f"gaussian_normals takes fewer than 2^28 Gaussians and 1..{_lib.NORMALS_MAX_VIEWS} views, got {n} and {V}")
     return (views.detach().contiguous(), xyz.detach().contiguous(), scaling.detach().contiguous(),
             _args.quad(rotation.detach().contiguous()))
+
+
+def _refuse_table_grad(who: str, views) -> None:
+    if torch.is_tensor(views) and views.requires_grad:
+        raise _lib.LsrError(f"{who}: views requires grad, and this operator has no pose gradient (pass views.detach(); the "
+                            "rasterizer hands the table its own)")
 
 
 def normals_forward(views: Tensor, xyz: Tensor, scaling: Tensor, rotation: Tensor, out: Optional[Tensor] = None) -> Tensor:
@@ -107,9 +119,11 @@ def gaussian_normals(views: Tensor, xyz: Tensor, scaling: Tensor, rotation: Tens
     the same bits); ``rotation (n, 4)`` any non-zero quaternion, raw or unit, in the scene's ``(w, x, y, z)`` order.  A row
     that is not finite gives 0.
 
-    Differentiable in ``rotation`` ONLY: the argmin and the sign are piecewise constant, so ``xyz``, ``scaling`` and
-    ``views`` receive no gradient from this operator.  Two HIP launches each way whatever the number of views; no atomics:
-    the same bits every call."""
+    Differentiable in ``rotation`` ONLY: the argmin and the sign are piecewise constant, so ``xyz`` and ``scaling``
+    receive no gradient from this operator.  The normals do depend on the view rotation (``n_cam = R_view n_world``) and
+    the operator has no gradient for it: a ``views`` that requires grad is refused, since a silent partial pose gradient is
+    worse than a refusal.  Two HIP launches each way whatever the number of views; no atomics: the same bits every call."""
+    _refuse_table_grad("gaussian_normals", views)
     return _GaussianNormals.apply(views, xyz, scaling, rotation)
 
 
@@ -195,7 +209,9 @@ def normal_consistency_loss(normal_map: Tensor, depth: Tensor, alpha: Tensor, vi
 
     Gradients go to ``normal_map``, ``depth`` and ``alpha``; the leading ``alpha`` of ``e`` is a constant weight in the
     backward, as the published regulariser detaches it, so ``alpha`` receives its gradient through ``depth / alpha`` alone.
-    Two HIP launches forward and one backward; no atomics: the same bits every call."""
+    The pixel rays depend on ``views`` and the loss has no gradient for it: a ``views`` that requires grad is refused (pass
+    ``views.detach()``).  Two HIP launches forward and one backward; no atomics: the same bits every call."""
+    _refuse_table_grad("normal_consistency_loss", views)
     return _NormalConsistency.apply(normal_map, depth, alpha, views, float(alpha_min))
 
 

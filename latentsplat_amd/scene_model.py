@@ -454,8 +454,11 @@ class GaussianScene(nn.Module):
         ``means2D_abs`` the rasterizer's refusal of more than 4 payload channels applies unchanged (take the absolute
         gradient from a plain :meth:`render`).  The view table must carry depth mode NATIVE (what ``build_view_table`` /
         ``make_view_table`` write by default): the loss reads ``depth`` as the blended view-space z; nothing is read back to
-        check it.  The normals hand a gradient to ``_rotation`` alone (the argmin and the sign are piecewise constant);
-        every other gradient is the rasterizer's."""
+        check it.  The normals hand a gradient to ``_rotation`` alone (the argmin and the sign are piecewise constant in
+        the positions and scales); every other gradient is the rasterizer's.  The normals are NOT constant in the view
+        rotation and have no gradient for it: a ``views`` that requires grad is refused, as by
+        :meth:`render_with_distortion` (for a camera gradient that leaves the normals' part out, call
+        ``gaussian_normals(views.detach(), ...)`` and :meth:`render` with ``features=``)."""
         from .normals import gaussian_normals
         from .rasterizer import rasterize_views
         if kw.get("features") is not None or kw.get("feature_sh") is not None:
@@ -530,7 +533,8 @@ class GaussianScene(nn.Module):
         is still inside the compositing kernels' 8-channel instances.  The two operator outputs are joined by one
         ``torch.cat`` (a copy of 20 bytes per (view, Gaussian) each way; tools/bench_distortion.py times it).  The view table
         must carry depth mode NATIVE, as for :meth:`render_with_normals`; ``means2D_abs`` is refused by the rasterizer, as
-        there."""
+        there.  Neither payload has a gradient for the view table, which both depend on: a ``views`` that requires grad is
+        refused, as by the two renders this one joins."""
         from .distortion import gaussian_depth_moments
         from .normals import gaussian_normals
         from .rasterizer import rasterize_views

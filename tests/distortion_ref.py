@@ -183,28 +183,14 @@ def layered_params(n: int, seed: int, z_lo: float, z_hi: float, K: int = 4) -> d
 
 
 def float64_chain(params: dict, views: np.ndarray, H: int, W: int, space: str, pivot=None, weight=None, grads: bool = True):
-    """render_with_distortion + distortion_loss in float64 on the host: the activation restated (tests/scene_params_ref.py),
-    operator A restated, the oracle's rasterizer per view with the moments as features, operator B restated.
+    """render_with_distortion + distortion_loss in float64 on the host, from the shared chain (tests/surface_chain_ref.py):
+    the activation restated (tests/scene_params_ref.py), operator A restated, the oracle's rasterizer per view with the moments
+    as features, operator B restated.
     ``(loss, distortion map (V, H, W), moment map, gradients of xyz, scaling, rotation, opacity)``."""
-    from oracle import torch_oracle as TO
-    from tests import scene_params_ref as sref
-    t = {k: torch.from_numpy(np.asarray(v, np.float64)).requires_grad_(grads) for k, v in params.items()}
-    rec = torch.from_numpy(views.astype(np.float64))
-    act = sref.forward64(t)
-    moments = depth_moments(rec, t["xyz"], space, None if pivot is None else torch.from_numpy(np.asarray(pivot, np.float64)))
-    maps = []
-    for v in range(rec.shape[0]):
-        r, s = rec[v], rec[v, 40]
-        _, feat, mask, _, _ = TO.rasterize(H, W, r[35], r[36], r[37:40], r[0:16], r[16:32], r[32:35], 0, t["xyz"] * s,
-                                           act["cov3D"] * s * s, act["opacities"], features=moments[v])
-        maps.append((feat, mask[0]))
-    mm, alpha = torch.stack([m[0] for m in maps]), torch.stack([m[1] for m in maps])
-    out = distortion(mm, alpha, None if weight is None else torch.from_numpy(np.asarray(weight, np.float64)))
-    g = {}
-    if grads:
-        out["loss"].backward()
-        g = {k: t[k].grad.numpy() for k in ("xyz", "scaling", "rotation", "opacity")}
-    return float(out["loss"].detach()), out["distortion"].detach().numpy(), mm.detach().numpy(), g
+    from tests import surface_chain_ref as chain
+    res = chain.chain(params, views, H, W, dict(dist=1.0), space=space, pivot=pivot, dist_weight=weight, grads=grads)
+    g = {k: res["grad"][k] for k in ("xyz", "scaling", "rotation", "opacity")} if grads else {}
+    return res["terms"]["dist"], res["maps"]["distortion"], res["maps"]["moment_map"], g
 
 
 def scene_of(params: dict, dev):

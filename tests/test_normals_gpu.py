@@ -129,9 +129,12 @@ def test_rows_that_are_not_finite_give_zero(hip_device):
 
 def test_only_the_rotation_receives_a_gradient(hip_device):
     from latentsplat_amd import gaussian_normals
-    leaves = [t.requires_grad_(True) for t in _dev(nref.scene_case(65, 2, seed=6), hip_device, A_KEYS)]
-    gaussian_normals(*leaves).square().sum().backward()
-    assert leaves[0].grad is None and leaves[1].grad is None and leaves[2].grad is None and leaves[3].grad is not None
+    views, *leaves = _dev(nref.scene_case(65, 2, seed=6), hip_device, A_KEYS)
+    leaves = [t.requires_grad_(True) for t in leaves]
+    with pytest.raises(_lib.LsrError, match="views requires grad"):       # the normals turn with the view: no silent partial gradient
+        gaussian_normals(views.clone().requires_grad_(True), *leaves)
+    gaussian_normals(views, *leaves).square().sum().backward()
+    assert leaves[0].grad is None and leaves[1].grad is None and leaves[2].grad is not None
 
 
 # ---- B ----
@@ -218,11 +221,14 @@ def test_every_optional_output_in_turn(hip_device):
 def test_loss_function_and_depth_to_normals(hip_device):
     from latentsplat_amd import depth_to_normals, normal_consistency_loss
     case, want, stock = _image_refs(3, 70, 97, True)
-    N, depth, alpha, views = (t.requires_grad_(True) for t in _dev(case, hip_device, B_KEYS))
+    N, depth, alpha, views = _dev(case, hip_device, B_KEYS)
+    for t in (N, depth, alpha):
+        t.requires_grad_(True)
+    with pytest.raises(_lib.LsrError, match="views requires grad"):       # the rays depend on the table: no silent partial gradient
+        normal_consistency_loss(N, depth, alpha, views.clone().requires_grad_(True), case["alpha_min"])
     loss = normal_consistency_loss(N, depth, alpha, views, case["alpha_min"])
     assert loss.shape == ()
     (loss * GRAD_LOSS).backward()
-    assert views.grad is None
     for k, t in (("grad_normal_map", N), ("grad_depth", depth), ("grad_alpha", alpha)):
         nref.held(k, t.grad.cpu().numpy(), want[k], stock[k], "autograd")
     normals, valid = depth_to_normals(depth.detach(), alpha.detach(), views.detach(), case["alpha_min"])
@@ -272,25 +278,13 @@ GRAD_TOL = 1e-3     # max |got - want| <= GRAD_TOL ||want||_2 per tensor: the ba
 
 
 def _float64_chain(params: dict, filt: np.ndarray, views: np.ndarray, H: int, W: int, antialiasing: bool, alpha_min: float):
-    """render_with_normals + normal_consistency_loss in float64 on the host: the filtered activation restated
-    (tests/filter3d_ref.py; a zero filter is the unfiltered map), operator A restated, the oracle's rasterizer per view, operator
-    B restated.  (loss, gradients of xyz, scaling, rotation, opacity)."""
-    from oracle import torch_oracle as TO
-    from tests import filter3d_ref as fref
-    t = {k: torch.from_numpy(np.asarray(v, np.float64)).requires_grad_(True) for k, v in params.items()}
-    rec = torch.from_numpy(views.astype(np.float64))
-    act = fref.forward64(t, torch.from_numpy(filt.astype(np.float64)).reshape(-1, 1))
-    normals = nref.gaussian_normals(rec, t["xyz"], t["scaling"], t["rotation"])
-    maps = []
-    for v in range(rec.shape[0]):
-        r, s = rec[v], rec[v, 40]
-        _, feat, mask, depth, _ = TO.rasterize(H, W, r[35], r[36], r[37:40], r[0:16], r[16:32], r[32:35], 0, t["xyz"] * s,
-                                               act["cov3D"] * s * s, act["opacities"], features=normals[v], antialiasing=antialiasing)
-        maps.append((feat, mask[0], depth[0]))
-    N, alpha, depth = (torch.stack([m[i] for m in maps]) for i in range(3))
-    loss = nref.consistency(N, depth, alpha, rec, alpha_min)["loss"]
-    loss.backward()
-    return float(loss.detach()), {k: t[k].grad.numpy() for k in ("xyz", "scaling", "rotation", "opacity")}
+    """render_with_normals + normal_consistency_loss in float64 on the host, from the shared chain
+    (tests/surface_chain_ref.py): the filtered activation restated (tests/filter3d_ref.py; a zero filter is the unfiltered
+    map), operator A restated, the oracle's rasterizer per view, operator B restated.  (loss, gradients of xyz, scaling,
+    rotation, opacity)."""
+    from tests import surface_chain_ref as chain
+    res = chain.chain(params, views, H, W, dict(normal=1.0), filt=filt, antialiasing=antialiasing, alpha_min=alpha_min)
+    return res["terms"]["normal"], {k: res["grad"][k] for k in ("xyz", "scaling", "rotation", "opacity")}
 
 
 @pytest.mark.parametrize("filtered,antialiasing", [(False, False), (True, True)])
